@@ -10,10 +10,23 @@ synthetic input from the survey's seeded generator (grok_amd/synth.py, seeds 10 
 Encode = image resident in HBM -> codestream resident in HBM; decode = codestream in HBM ->
 image in HBM; host T2 (packet headers, rate allocation) runs inside the step.  value = pixels
 of all ranks (2 x 8192^2 per rank per step) / max-over-ranks wall time.  Single-tile configs run
-as replicas (one C2 + C3 pair per GPU, no collective on the data path): scaling = "weak".  The
-line also carries C2 and C3 timed alone (`per_config`).
+as replicas (one C2 + C3 pair per GPU, no collective on the data path): scaling = "weak".
 
-The same JSON line carries auxiliary measurements:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what that figure needs: it
+builds the images and engines, runs one untimed step (the engines allocate their buffers and
+load their code objects), W warm-up steps and the K timed steps, writes the outputs of the last
+timed step if `--dump-outputs DIR` is given, and prints the result line (headline, per-stage
+HIP-event times of the timed steps and the rooflines derived from them).
+
+`--dump-outputs DIR`: what the timed path computed in its last step, as DIR/<name>.npy: per
+config <C>_codestream (the bytes, float32), <C>_decoded (the samples, float32) and <C>_summary
+(float64: codestream length, sum of its bytes, sum of the decoded samples).  An array above its
+share of 48 MB is a fixed seeded sample of its elements in index order (`sample()`); inputs are
+seeded, so equal arguments give equal inputs from run to run.
+
+`--full` adds everything else: the lossless / PSNR round-trip check before timing, C2 and C3
+timed alone (`per_config`), the T1 decoder's issue roofline (one more decode with the step
+counters on, instruction counts from llvm-objdump), and the auxiliary measurements:
   C4  configs[3]: 16384^2 16-bit mono, HTJ2K, 1024^2 tiles, TLM + PLT — with N > 1
       ranks tile rows are sharded (strong scaling): each rank codes its tile rows,
       rank 0 gathers the tile parts over RCCL, each rank decodes its own parts;
@@ -26,7 +39,8 @@ The same JSON line carries auxiliary measurements:
 `cpu_baseline`: the oracle (CPU restatement, byte-exact with Grok by the fixtures)
 on bounded crops of C2 / C3 / C4, median of 3 runs, at 1 and N host threads.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4] [--no-aux]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4] [--dump-outputs DIR]
+                       [--full [--no-aux] [--no-c5] [--no-cpu-baseline]]
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts N rank
 processes itself (torch.distributed.run) before touching the GPU.
 """
@@ -68,7 +82,7 @@ C5_WINDOWS = [(0, 0, 1024, 1024), (12345, 23456, 16441, 27552), (30000, 30000, 3
               (8000, 8000, 24384, 24384)]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -76,13 +90,21 @@ def parse():
     ap.add_argument("--size", type=int, default=0, help="override the config's image side")
     ap.add_argument("--config", default="C2+C3", choices=["C2+C3", "C2", "C3", "C4"],
                     help="C2+C3: the headline metric (one 5/3 and one 9/7 image per step)")
-    ap.add_argument("--no-aux", action="store_true", help="skip the auxiliary C3/C4/C5/batch measurements")
-    ap.add_argument("--no-c5", action="store_true", help="skip the C5 window-decode measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: round-trip check, configs timed alone, T1 issue roofline, auxiliary "
+                         "C4/C5/in-flight measurements, CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="--full without the auxiliary C3/C4/C5/batch measurements")
+    ap.add_argument("--no-c5", action="store_true", help="--full without the C5 window-decode measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="N for the N-thread CPU baseline (0: the host share)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group / timing plumbing only (CPU, gloo, no engine): for tests")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -223,16 +245,63 @@ def pmc_traffic(kernels, config="C2"):
     return tot, os.path.basename(f)
 
 
+# ----------------------------------------------------------------------------- outputs
+DUMP_BUDGET = 48 << 20   # bytes of sampled arrays per dump (the summaries are a few numbers)
+
+
+def sample(t, cap, seed):
+    """Tensor t flattened, as a float32 numpy array: all of it if it has at most cap elements,
+    else its elements at cap seeded positions in index order (the same for the same size)."""
+    import torch
+    flat = t.reshape(-1)
+    if flat.numel() > cap:
+        idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), cap))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.to(torch.float32).cpu().numpy()
+
+
+def coded_outputs(name, cs, n, y, cap):
+    """The arrays a caller of one encode + decode receives: the codestream cs[:n] (uint8) and
+    the decoded image y, each through sample(), and their float64 summary."""
+    import torch
+    cs = cs[:n]
+    return {name + "_codestream": sample(cs, cap, 1), name + "_decoded": sample(y, cap, 2),
+            name + "_summary": np.array([n, float(cs.sum(dtype=torch.float64)), float(y.sum(dtype=torch.float64))],
+                                        np.float64)}
+
+
+def dump_outputs(path, r):
+    outs = r.outputs(DUMP_BUDGET // 4 // (2 * len(getattr(r, "rs", (r,)))))
+    os.makedirs(path, exist_ok=True)
+    for name, a in outs.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------- runners
+def synth_image_threads(h, w, c, bits, seed, chunk=1024):
+    """grok_amd.synth.synth_image, its 1024-row chunks (each seeded by its first row) generated
+    on up to 8 host threads: the same image, set up in a fraction of the time."""
+    from concurrent.futures import ThreadPoolExecutor
+    from grok_amd.synth import synth_rows
+    out = np.empty((c, h, w), np.uint16)
+
+    def rows(y0):
+        y1 = min(h, y0 + chunk)
+        out[:, y0:y1, :] = synth_rows(y0, y1, w, c, bits, seed, h)
+    with ThreadPoolExecutor(max(1, min(8, len(os.sched_getaffinity(0))))) as ex:
+        list(ex.map(rows, range(0, h, chunk)))
+    return out
+
+
 class Runner:
     def __init__(self, name, size, rank, device):
         import torch
         import grok_amd as G
-        from grok_amd.synth import synth_image
         cfg = CONFIGS[name]
         size = size or cfg["size"]
         self.name, self.cfg, self.size = name, cfg, size
-        self.img = synth_image(size, size, cfg["comps"], cfg["bits"], cfg["seed"] + rank)
+        self.img = synth_image_threads(size, size, cfg["comps"], cfg["bits"], cfg["seed"] + rank)
         self.x = torch.from_numpy(self.img.astype(np.int32)).to(device).contiguous()
         self.out = torch.empty(self.x.numel() * 4 + (1 << 24), dtype=torch.uint8, device=device)
         self.y = torch.empty_like(self.x)
@@ -263,6 +332,9 @@ class Runner:
                 raise SystemExit("9/7 round trip PSNR %.2f dB too low (%s)" % (psnr, self.name))
             return psnr
         return None
+
+    def outputs(self, cap):
+        return coded_outputs(self.name, self.out, self.n, self.y, cap)
 
     def close(self):
         self.eng.close()
@@ -395,6 +467,11 @@ class ShardRunner:
             raise SystemExit("sharded lossless round trip FAILED (%s, gathered image)" % self.name)
         return None
 
+    def outputs(self, cap):
+        # rank 0's: the assembled codestream and the gathered image (u16 samples held as int16)
+        y = self.y_full
+        return coded_outputs(self.name, self.cs, self.n, (y.int() & 0xFFFF) if y.element_size() == 2 else y, cap)
+
     def close(self):
         if self.eng is not None:
             self.eng.close()
@@ -499,6 +576,9 @@ class PairRunner:
         self.n = self.rs[0][1].n + self.rs[1][1].n
         return psnr
 
+    def outputs(self, cap):
+        return {k: v for _, r in self.rs for k, v in r.outputs(cap).items()}
+
     def close(self):
         for _, r in self.rs:
             r.close()
@@ -580,8 +660,8 @@ def dry_main(args, world, rank, dist):
                           "scaling": "weak"}), flush=True)
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch(args))   # this process has not touched the GPU
@@ -611,14 +691,22 @@ def main():
         r = Runner(args.config, args.size, rank, device)
     else:
         r = ShardRunner("C4", args.size, rank, world, device, dist)
-    psnr = r.check()
+    # --full: the round trip checked (lossless, or PSNR); else that step alone, untimed, so that
+    # the engines hold their buffers and code objects whatever --warmup says
+    psnr = None
+    if args.full:
+        psnr = r.check()
+    else:
+        r.step()
     el, m = timed(r, args.steps, args.warmup, world, dist, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
     ms = el * 1000.0 / args.steps
     per_rank = world if not isinstance(r, ShardRunner) else 1   # replicas: every rank codes its own images
     value = r.pixels / 1e6 * per_rank * args.steps / el
     r_pixels = int(r.pixels)
     per_config = None
-    if isinstance(r, PairRunner):
+    if args.full and isinstance(r, PairRunner):
         # each config of the pair timed alone as well (same engines, same images)
         per_config = {}
         for name, rr in (("C2", r2), ("C3", r3)):
@@ -635,7 +723,7 @@ def main():
     # the T1 decoder's chain length: one more (untimed) decode with the step counters on
     dec_steps = None
     rs = r2 if isinstance(r, PairRunner) else r
-    if isinstance(rs, Runner) and not rs.cfg["params"].get("cblk_sty"):
+    if args.full and isinstance(rs, Runner) and not rs.cfg["params"].get("cblk_sty"):
         os.environ["GK_T1_STATS"] = "1"
         try:
             rs.eng.decode(rs.out, length=rs.n, out=rs.y)
@@ -651,7 +739,7 @@ def main():
     torch.cuda.empty_cache()
 
     aux = None
-    if not args.no_aux and args.config == "C2+C3":
+    if args.full and not args.no_aux and args.config == "C2+C3":
         aux = {}
         # the headline pair with both images in flight (one host thread and engine each)
         rp = InFlightRunner([Runner("C2", args.size, rank, device), Runner("C3", args.size, rank, device)])
@@ -824,7 +912,7 @@ def main():
                                  "(gk_t1dec.hip solo_block); the steps above are the lane-parallel waves'"}}
         if aux:
             res["aux"] = aux
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(host_threads(args))
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -81,7 +81,11 @@ class Fixture:
     def __init__(self, path):
         z = np.load(path)
         self.name = os.path.basename(path)[:-4]
-        self.img = z["img"].astype(np.int32)
+        if "img" in z.files:
+            self.img = z["img"].astype(np.int32)
+        else:   # a large seeded image is stored as its generator arguments (h, w, c, bits, seed)
+            from grok_amd.synth import synth_image
+            self.img = synth_image(*(int(v) for v in z["synth"])).astype(np.int32)
         self.bits = int(z["bits"])
         self.flags = str(z["flags"])
         self.cs = z["cs"].tobytes()

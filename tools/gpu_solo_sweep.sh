@@ -15,7 +15,8 @@ m = d["stages_ms"]
 print("solo", sys.argv[1], "value", d["value"], "ms", d["ms_per_step"], "enc_t1", m["enc_t1_ms"], "cm", m.get("enc_t1_cm_ms"), "coder", m.get("enc_t1_coder_ms"), "enc_t2", m["enc_t2_ms"], "dec_t2", m["dec_t2_ms"], flush=True)
 PY
 done
-timeout -k 10 500 python bench.py > gpurun_out/r06c_bench.json 2> gpurun_out/r06c_bench.err || exit $?
+LOG=${BENCH_LOG:-bench_full}   # the whole bench line (--full) goes to $LOG.json, its stderr to $LOG.err
+timeout -k 10 500 python bench.py --full > "$LOG.json" 2> "$LOG.err" || exit $?
 python -c "
-import json; t=open('gpurun_out/r06c_bench.json').read(); d=json.loads(t[t.index('{'):])
+import json; t=open('$LOG.json').read(); d=json.loads(t[t.index('{'):])
 print('value', d['value'], d['ms_per_step'], {k: v['value'] for k, v in d.get('per_config', {}).items()}, {k: v['value'] for k, v in d.get('aux', {}).items()})"
