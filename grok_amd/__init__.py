@@ -24,7 +24,10 @@ GK_MAX_LAYERS = 100
 EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_encode_tiles", "gk_main_header",
            "gk_jp2_header", "gk_decode_header", "gk_probe_header", "gk_decode", "gk_decode_window", "gk_get_timings",
            "gk_last_error", "gk_version", "gk_set_decode_layers", "gk_set_decode_reduce",
-           "gk_set_window_rule", "gk_set_subsampling", "gk_probe_components", "gk_header_components")
+           "gk_set_window_rule", "gk_set_subsampling", "gk_probe_components", "gk_header_components",
+           "gk_probe_colour", "gk_header_colour", "gk_header_icc", "gk_set_decode_colour", "gk_probe_icc",
+           "gk_probe_stream_components")
+GK_MAX_CHANNELS = 256
 
 
 class Poc(ctypes.Structure):
@@ -71,6 +74,18 @@ class Timings(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("dwt_bytes", "cs_bytes", "t1_bytes", "t1_steps_max", "t1_steps_total",
                                                "t1_symbols", "t1_solo_blocks", "t1_solo_decisions",
                                                "t1_solo_decisions_max")]
+
+
+class ColourInfo(ctypes.Structure):
+    """gk_colour_info (include/grok_amd.h): colour description of a JP2 file / codestream."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("colour_space", "enumcs", "meth", "icc_len", "has_palette",
+                                               "palette_entries", "palette_columns", "has_cdef", "num_comps",
+                                               "num_channels")] + \
+               [("typ", ctypes.c_uint16 * GK_MAX_CHANNELS), ("asoc", ctypes.c_uint16 * GK_MAX_CHANNELS)]
+
+    def channels(self):
+        """[(typ, asoc)] per output channel (cdef Typ / Asoc, or Grok's defaults)."""
+        return [(self.typ[k], self.asoc[k]) for k in range(min(self.num_channels, GK_MAX_CHANNELS))]
 
 
 _lib = None
@@ -123,6 +138,19 @@ def load_library(build_if_missing=True):
     lib.gk_probe_components.argtypes = [ctypes.c_void_p, ctypes.c_size_t] + [P(ctypes.c_uint32)] * 4 + [ctypes.c_uint32]
     lib.gk_header_components.restype = ctypes.c_int
     lib.gk_header_components.argtypes = [ctypes.c_void_p] + [P(ctypes.c_uint32)] * 4 + [ctypes.c_uint32]
+    lib.gk_probe_colour.restype = ctypes.c_int
+    lib.gk_probe_colour.argtypes = [ctypes.c_void_p, ctypes.c_size_t, P(ColourInfo), ctypes.c_char_p, ctypes.c_size_t]
+    lib.gk_probe_icc.restype = ctypes.c_int
+    lib.gk_probe_icc.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]
+    lib.gk_probe_stream_components.restype = ctypes.c_int
+    lib.gk_probe_stream_components.argtypes = [ctypes.c_void_p, ctypes.c_size_t] + [P(ctypes.c_uint32)] * 4 + \
+        [ctypes.c_uint32]
+    lib.gk_header_colour.restype = ctypes.c_int
+    lib.gk_header_colour.argtypes = [ctypes.c_void_p, P(ColourInfo)]
+    lib.gk_header_icc.restype = ctypes.c_int
+    lib.gk_header_icc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]
+    lib.gk_set_decode_colour.restype = ctypes.c_int
+    lib.gk_set_decode_colour.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -212,14 +240,42 @@ def probe_header(cs):
     return info
 
 
+def probe_colour(cs):
+    """gk_probe_colour: ColourInfo of host codestream / JP2 bytes (colour space, ICC length, palette,
+    output channels with their cdef types), no engine or GPU needed.  Malformed colour boxes raise
+    ValueError with a message naming the box."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    info = ColourInfo()
+    msg = ctypes.create_string_buffer(512)
+    if lib.gk_probe_colour(b.ctypes.data, len(b), ctypes.byref(info), msg, 512) != 0:
+        raise ValueError(msg.value.decode())
+    return info
+
+
+def probe_icc(cs):
+    """gk_probe_icc: the ICC profile bytes (colr METH 2) of host JP2 bytes, b"" without one."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    n = ctypes.c_size_t()
+    if lib.gk_probe_icc(b.ctypes.data, len(b), None, 0, ctypes.byref(n)) == -1:
+        probe_colour(cs)   # (raises with the reason)
+    buf = np.empty(max(n.value, 1), np.uint8)
+    if n.value and lib.gk_probe_icc(b.ctypes.data, len(b), buf.ctypes.data, buf.size, ctypes.byref(n)) != 0:
+        raise ValueError("gk_probe_icc failed")
+    return buf[:n.value].tobytes()
+
+
 def probe_components(cs, precision=False):
-    """gk_probe_components: [(dx, dy)] per component of host codestream / JP2 bytes (SIZ XRsiz /
-    YRsiz); with precision=True [(dx, dy, prec, signed)]."""
+    """gk_probe_components: [(dx, dy)] per output channel of host codestream / JP2 bytes (SIZ XRsiz /
+    YRsiz; the channels a JP2 palette / channel definition makes of the components); with
+    precision=True [(dx, dy, prec, signed)]."""
     lib = load_library()
     b = np.frombuffer(bytes(cs), np.uint8)
     dx, dy, pr, sg = [(ctypes.c_uint32 * 16384)() for _ in range(4)]
     n = lib.gk_probe_components(b.ctypes.data, len(b), dx, dy, pr, sg, 16384)
     if n < 0:
+        probe_header(cs)   # (raises with the reason)
         raise ValueError("gk_probe_components failed")
     if precision:
         return [(dx[c], dy[c], pr[c], bool(sg[c])) for c in range(n)]
@@ -509,6 +565,30 @@ class Engine:
             self._err("gk_decode_header")
         return info
 
+    def colour_info(self):
+        """gk_header_colour: ColourInfo of the stream the last read_header / decode read."""
+        info = ColourInfo()
+        if self.lib.gk_header_colour(self.ctx, ctypes.byref(info)) != 0:
+            self._err("gk_header_colour")
+        return info
+
+    def icc_profile(self):
+        """gk_header_icc: the ICC profile bytes (colr METH 2) of that stream, b"" without one."""
+        n = ctypes.c_size_t()
+        self.lib.gk_header_icc(self.ctx, None, 0, ctypes.byref(n))
+        if not n.value:
+            return b""
+        buf = np.empty(n.value, np.uint8)
+        if self.lib.gk_header_icc(self.ctx, buf.ctypes.data, buf.size, ctypes.byref(n)) != 0:
+            self._err("gk_header_icc")
+        return buf.tobytes()
+
+    def set_decode_colour(self, apply):
+        """gk_set_decode_colour: apply a JP2 file's palette and channel definition on decode (True,
+        the default: planes are the output channels) or return the codestream's components (False)."""
+        if self.lib.gk_set_decode_colour(self.ctx, int(bool(apply))) != 0:
+            self._err("gk_set_decode_colour")
+
     def decode_window(self, cs, window, length=None, out=None, sample_bytes=0):
         """gk_decode_window: window = (x0, y0, x1, y1).  Returns a (C, y1-y0, x1-x0) numpy
         array (int32, or 8/16-bit with sample_bytes 1/2), or fills ``out`` (a torch cuda
@@ -572,7 +652,8 @@ class Engine:
             self._err("gk_set_window_rule")
 
     def decode(self, cs, length=None, out=None, row0=0, sample_bytes=0):
-        """cs: bytes (host) or torch cuda uint8 tensor (+length).  Returns a (C, H, W)
+        """cs: bytes (host) or torch cuda uint8 tensor (+length).  C counts the output channels
+        (a JP2 palette / channel definition applied, see set_decode_colour).  Returns a (C, H, W)
         numpy array (int32, or 8/16-bit with sample_bytes 1/2), or fills ``out`` (torch
         cuda tensor; its element size selects the sample type) in place.  ``out`` may be
         a (C, rows, W) slab holding image rows [row0, row0+rows) when cs carries only the

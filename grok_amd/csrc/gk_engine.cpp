@@ -2475,9 +2475,12 @@ static void write_main_header(std::vector<uint8_t>& o, const Plan& P, size_t* tl
 
 // ---------------------------------------------------------------------------
 // JP2 file format (ISO 15444-1 Annex I): the boxes Grok writes around the codestream
-// (FileFormatCompress.cpp:43-265, 619-665, 936-953) and the box walk that finds it
-// (FileFormatDecompress.cpp:632-672).  No colour conversion is applied (sRGB / greyscale
-// enumerated spaces, as grk_compress records for PNM input, PNMFormat.cpp:439-442).
+// (FileFormatCompress.cpp:43-265, 619-665, 936-953; sRGB / greyscale enumerated spaces, as
+// grk_compress records for PNM input, PNMFormat.cpp:439-442) and the box walk that finds it
+// (FileFormatDecompress.cpp:632-672).  On decode the jp2h colour boxes are read and applied as
+// FileFormatDecompress does: colr gives the reported colour space and ICC profile, pclr + cmap
+// expand palette indices (gk_colour.hip), cdef reorders the channels.  No colour space
+// conversion is applied (Grok leaves sYCC / e-YCC -> RGB to its command-line tools).
 // ---------------------------------------------------------------------------
 static const uint32_t BOX_JP = 0x6a502020, BOX_FTYP = 0x66747970, BOX_JP2H = 0x6a703268, BOX_IHDR = 0x69686472,
                       BOX_COLR = 0x636f6c72, BOX_JP2C = 0x6a703263, BRAND_JP2 = 0x6a703220;
@@ -2504,30 +2507,288 @@ static void write_jp2_prefix(std::vector<uint8_t>& o, const Plan& P, uint64_t cs
         put32(o, L < (1ull << 32) ? (uint32_t)L : 0); put32(o, BOX_JP2C);
     }
 }
-// JP2 file -> [off, off + len) of its contiguous codestream box; false for a raw codestream
-static bool jp2_locate(ByteSrc& S, size_t& off, size_t& len) {
+// The colour boxes of a JP2 header box (jp2h), as FileFormatDecompress reads them: colr
+// (read_colr :1028-1149), pclr (read_palette_clr :1483-1548), cmap (read_component_mapping
+// :1437-1482) and cdef (read_channel_definition :931-1027); ihdr / bpcc are kept as read.
+struct Jp2Colour {
+    bool jp2 = false;
+    bool has_ihdr = false;
+    uint32_t ihdr_w = 0, ihdr_h = 0, ihdr_nc = 0, ihdr_bpc = 0;
+    std::vector<uint8_t> bpcc;
+    bool has_colr = false;          // a colr box was accepted (the first one wins)
+    uint32_t meth = 0, enumcs = 0;
+    std::vector<uint8_t> icc;
+    bool has_pclr = false;
+    uint32_t ne = 0, npc = 0;
+    std::vector<uint8_t> pprec;     // palette column precisions
+    std::vector<uint32_t> lut;      // ne rows of npc columns
+    bool has_cmap = false;
+    struct Map { uint16_t cmp; uint8_t mtyp, pcol; };
+    std::vector<Map> cmap;
+    bool has_cdef = false;
+    struct Def { uint16_t cn, typ, asoc; };
+    std::vector<Def> cdef;
+    // GRK_COLOR_SPACE of the composited image (FileFormatDecompress::readHeader :218-256)
+    uint32_t colour_space(uint32_t nc) const {
+        (void)nc;
+        if (!jp2) return 0;   // (a raw codestream carries no colour specification: GRK_CLRSPC_UNKNOWN)
+        if (meth == 2 && !icc.empty()) return 9;   // GRK_CLRSPC_ICC
+        switch (enumcs) {
+            case 12: return 6;   // CMYK
+            case 16: return 2;   // sRGB
+            case 17: return 3;   // grey
+            case 18: return 4;   // sYCC
+            case 24: return 5;   // e-YCC
+            default: return 0;   // unknown
+        }
+    }
+};
+static const uint32_t BOX_BPCC = 0x62706363, BOX_PCLR = 0x70636c72, BOX_CMAP = 0x636d6170, BOX_CDEF = 0x63646566;
+static void jp2_read_colr(ByteSrc& S, size_t p, size_t n, Jp2Colour& C) {
+    if (n < 3) throw GkError("colr box: bad size");
+    if (C.has_colr) return;   // I.5.3.3: every colour specification box after the first is ignored
+    const uint32_t meth = S.at(p);
+    if (meth == 1) {
+        if (n < 7) throw GkError("colr box: bad size");
+        const uint32_t cs = S.be32(p + 3);
+        if (cs != 0 && cs != 12 && cs != 14 && cs != 16 && cs != 17 && cs != 18 && cs != 24) return;   // box ignored
+        if (cs == 14) throw GkError("colr box: the CIELab enumerated colour space (EnumCS 14) and its parameters are not supported");
+        C.meth = 1; C.enumcs = cs; C.has_colr = true;
+    } else if (meth == 2) {
+        if (n == 3) throw GkError("colr box: ICC profile of length zero");
+        C.icc.resize(n - 3);
+        for (size_t i = 0; i < n - 3; ++i) C.icc[i] = S.at(p + 3 + i);
+        C.meth = 2; C.has_colr = true;
+    }   // any other METH: the whole box is ignored (Table I.9)
+}
+static void jp2_read_pclr(ByteSrc& S, size_t p, size_t n, Jp2Colour& C) {
+    if (C.has_pclr) throw GkError("pclr box: only one palette box is allowed");
+    if (n < 3) throw GkError("pclr box: too short");
+    C.ne = S.be16(p); C.npc = S.at(p + 2);
+    if (C.ne == 0 || C.ne > 1024) throw GkError("pclr box: " + std::to_string(C.ne) + " palette entries (NE must be 1..1024)");
+    if (C.npc == 0) throw GkError("pclr box: no palette columns (NPC 0)");
+    if (n < 3 + (size_t)C.npc) throw GkError("pclr box: too short");
+    C.pprec.resize(C.npc);
+    for (uint32_t i = 0; i < C.npc; ++i) {
+        const uint32_t b = S.at(p + 3 + i);
+        C.pprec[i] = (uint8_t)((b & 0x7f) + 1);
+        if (C.pprec[i] > 16)   // maxSupportedPrecisionGRK
+            throw GkError("pclr box: column precision " + std::to_string(C.pprec[i]) + " above 16 bits is not supported (Grok's limit)");
+        if (b & 0x80) throw GkError("pclr box: signed palette column not supported");
+    }
+    size_t q = 3 + (size_t)C.npc;
+    C.lut.resize((size_t)C.ne * C.npc);
+    for (uint32_t j = 0; j < C.ne; ++j)
+        for (uint32_t i = 0; i < C.npc; ++i) {
+            const uint32_t nb = (C.pprec[i] + 7u) >> 3;
+            if (n < q + nb) throw GkError("pclr box: too short for its entries");
+            uint32_t v = 0;
+            for (uint32_t b = 0; b < nb; ++b) v = (v << 8) | S.at(p + q + b);
+            C.lut[(size_t)j * C.npc + i] = v;
+            q += nb;
+        }
+    C.has_pclr = true;
+}
+static void jp2_read_cmap(ByteSrc& S, size_t p, size_t n, Jp2Colour& C) {
+    if (!C.has_pclr) throw GkError("cmap box: a pclr box must come before the cmap box");
+    if (C.has_cmap) throw GkError("cmap box: only one component mapping box is allowed");
+    if (n < (size_t)C.npc * 4) throw GkError("cmap box: too short");
+    C.cmap.resize(C.npc);
+    for (uint32_t i = 0; i < C.npc; ++i) {
+        C.cmap[i].cmp = (uint16_t)S.be16(p + 4 * i);
+        C.cmap[i].mtyp = S.at(p + 4 * i + 2);
+        C.cmap[i].pcol = S.at(p + 4 * i + 3);
+        if (C.cmap[i].mtyp > 1)
+            throw GkError("cmap box: mapping type " + std::to_string(C.cmap[i].mtyp) + " of channel " + std::to_string(i) + " (MTYP must be 0 or 1)");
+    }
+    C.has_cmap = true;
+}
+static void jp2_read_cdef(ByteSrc& S, size_t p, size_t n, Jp2Colour& C) {
+    if (C.has_cdef) throw GkError("cdef box: only one channel definition box is allowed");
+    if (n < 2) throw GkError("cdef box: too short");
+    const uint32_t N = S.be16(p);
+    if (!N) throw GkError("cdef box: no channel definitions");
+    if (n < 2 + (size_t)N * 6) throw GkError("cdef box: too short");
+    C.cdef.resize(N);
+    for (uint32_t i = 0; i < N; ++i) {
+        Jp2Colour::Def& d = C.cdef[i];
+        d.cn = (uint16_t)S.be16(p + 2 + 6 * i); d.typ = (uint16_t)S.be16(p + 4 + 6 * i); d.asoc = (uint16_t)S.be16(p + 6 + 6 * i);
+        if (d.typ > 2 && d.typ != 65535) throw GkError("cdef box: illegal channel type " + std::to_string(d.typ));
+        if (d.asoc > 3 && d.asoc != 65535) throw GkError("cdef box: illegal channel association " + std::to_string(d.asoc));
+    }
+    for (uint32_t i = 0; i < N; ++i)
+        for (uint32_t j = 0; j < N; ++j) {
+            const Jp2Colour::Def &a = C.cdef[i], &b = C.cdef[j];
+            if (i != j && a.cn == b.cn && a.typ != b.typ) throw GkError("cdef box: channel " + std::to_string(a.cn) + " described twice with different types");
+            if (i != j && a.cn != b.cn && a.typ == b.typ && a.asoc == b.asoc && (a.typ != 65535 || a.asoc != 65535))
+                throw GkError("cdef box: channels " + std::to_string(a.cn) + " and " + std::to_string(b.cn) + " share one type / association pair");
+        }
+    C.has_cdef = true;
+}
+// one box header at pos: payload [pos + hdr, pos + L) inside [pos, end)
+static void jp2_box(ByteSrc& S, size_t pos, size_t end, uint64_t& L, uint32_t& T, size_t& hdr) {
+    L = S.be32(pos); T = S.be32(pos + 4); hdr = 8;
+    if (L == 1) {
+        if (pos + 16 > end) throw GkError("corrupt JP2 box header");
+        L = ((uint64_t)S.be32(pos + 8) << 32) | S.be32(pos + 12);
+        hdr = 16;
+    } else if (L == 0) {
+        L = end - pos;   // last box
+    }
+    if (L < hdr || L > end - pos) throw GkError("corrupt JP2 box length");
+}
+static void jp2_read_jp2h(ByteSrc& S, size_t pos, size_t end, Jp2Colour& C) {
+    while (pos + 8 <= end) {
+        uint64_t L; uint32_t T; size_t hdr;
+        jp2_box(S, pos, end, L, T, hdr);
+        const size_t p = pos + hdr, n = (size_t)L - hdr;
+        if (T == BOX_IHDR) {
+            if (n != 14) throw GkError("ihdr box: bad size");
+            C.has_ihdr = true; C.ihdr_h = S.be32(p); C.ihdr_w = S.be32(p + 4); C.ihdr_nc = S.be16(p + 8); C.ihdr_bpc = S.at(p + 10);
+        } else if (T == BOX_BPCC) {
+            C.bpcc.resize(n);
+            for (size_t i = 0; i < n; ++i) C.bpcc[i] = S.at(p + i);
+        } else if (T == BOX_COLR) jp2_read_colr(S, p, n, C);
+        else if (T == BOX_PCLR) jp2_read_pclr(S, p, n, C);
+        else if (T == BOX_CMAP) jp2_read_cmap(S, p, n, C);
+        else if (T == BOX_CDEF) jp2_read_cdef(S, p, n, C);
+        pos += (size_t)L;
+    }
+}
+// JP2 file -> [off, off + len) of its contiguous codestream box; false for a raw codestream.
+// With col, the colour boxes of the jp2h box in front of it (FileFormatDecompress::read_jp2h).
+static bool jp2_locate(ByteSrc& S, size_t& off, size_t& len, Jp2Colour* col = nullptr) {
     if (S.len < 12 || S.be32(0) != 12 || S.be32(4) != BOX_JP) return false;
     if (S.be32(8) != 0x0d0a870a) throw GkError("corrupt JP2 signature box");
     size_t pos = 12;
     bool ftyp = false;
     while (pos + 8 <= S.len) {
-        uint64_t L = S.be32(pos);
-        const uint32_t T = S.be32(pos + 4);
-        size_t hdr = 8;
-        if (L == 1) {
-            if (pos + 16 > S.len) throw GkError("corrupt JP2 box header");
-            L = ((uint64_t)S.be32(pos + 8) << 32) | S.be32(pos + 12);
-            hdr = 16;
-        } else if (L == 0) {
-            L = S.len - pos;   // last box
-        }
-        if (L < hdr || L > S.len - pos) throw GkError("corrupt JP2 box length");
+        uint64_t L; uint32_t T; size_t hdr;
+        jp2_box(S, pos, S.len, L, T, hdr);
         if (!ftyp && T != BOX_FTYP) throw GkError("malformed JP2: second box must be the file type box");
         ftyp = true;
-        if (T == BOX_JP2C) { off = pos + hdr; len = (size_t)L - hdr; return true; }
+        if (T == BOX_JP2H && col) jp2_read_jp2h(S, pos + hdr, pos + (size_t)L, *col);
+        if (T == BOX_JP2C) { off = pos + hdr; len = (size_t)L - hdr; if (col) col->jp2 = true; return true; }
         pos += (size_t)L;
     }
     throw GkError("JP2 file without a contiguous codestream box");
+}
+
+// What the colour boxes make of the codestream's components: FileFormatDecompress::check_color
+// (:1150-1297), apply_palette_clr (:1299-1436) and apply_channel_definition (:876-930) resolved
+// into the list of output channels, in output order.
+struct ColourOut {
+    bool palette = false, cdef = false;   // boxes that apply
+    struct Ch {
+        uint32_t src = 0;          // codestream component
+        bool direct = true;        // its samples (MTYP 0 / no palette), or palette column col of them
+        uint32_t col = 0;
+        uint32_t prec = 0, sgnd = 0;
+        uint32_t typ = 0, asoc = 0;
+    };
+    std::vector<Ch> ch;
+    bool active() const { return palette || cdef; }
+    uint32_t max_prec() const { uint32_t m = 0; for (const Ch& c : ch) m = std::max(m, c.prec); return m; }
+};
+static ColourOut resolve_colour(const Jp2Colour& C, const Plan& W) {
+    ColourOut O;
+    const uint32_t nc = W.nc;
+    // a pclr without a cmap is dropped (applyColour :383-388; Part 1, I.5.3.4: both or none)
+    const bool pal = C.has_pclr && C.has_cmap;
+    std::vector<Jp2Colour::Map> map = C.cmap;
+    if (C.has_cdef) {
+        const uint32_t nch = pal ? C.npc : nc;
+        for (const auto& d : C.cdef) {
+            if (d.cn >= nch) throw GkError("cdef box: channel index " + std::to_string(d.cn) + " out of range (" + std::to_string(nch) + " channels)");
+            if (d.asoc == 65535) continue;
+            if (d.asoc > 0 && (uint32_t)(d.asoc - 1) >= nch)
+                throw GkError("cdef box: association " + std::to_string(d.asoc) + " out of range (" + std::to_string(nch) + " channels)");
+        }
+        for (uint32_t k = 0; k < nch; ++k) {
+            bool found = false;
+            for (const auto& d : C.cdef) found = found || d.cn == k;
+            if (!found) throw GkError("cdef box: incomplete channel definitions (channel " + std::to_string(k) + " is missing)");
+        }
+    }
+    if (pal) {
+        const uint32_t n = C.npc;
+        for (uint32_t i = 0; i < n; ++i)
+            if (map[i].cmp >= nc) throw GkError("cmap box: component index " + std::to_string(map[i].cmp) + " out of range (" + std::to_string(nc) + " components)");
+        std::vector<uint8_t> used(n, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t pc = map[i].pcol;
+            if (map[i].mtyp > 1) throw GkError("cmap box: MTYP must be 0 or 1");
+            if (pc >= n) throw GkError("cmap box: palette column " + std::to_string(pc) + " out of range (NPC " + std::to_string(n) + ")");
+            if (used[pc] && map[i].mtyp == 1) throw GkError("cmap box: palette column " + std::to_string(pc) + " is mapped twice");
+            if (map[i].mtyp == 0 && pc != 0) throw GkError("cmap box: direct mapping of channel " + std::to_string(i) + " with a non-zero palette column");
+            used[pc] = 1;
+        }
+        for (uint32_t i = 0; i < n; ++i)
+            if (!used[i] && map[i].mtyp != 0) throw GkError("cmap box: channel " + std::to_string(i) + " has no mapping");
+        if (nc == 1) {   // ("weird" mappings of single-component files are repaired, :1269-1290)
+            bool all = true;
+            for (uint32_t i = 0; i < n; ++i) all = all && used[i];
+            if (!all) for (uint32_t i = 0; i < n; ++i) { map[i].mtyp = 1; map[i].pcol = (uint8_t)i; }
+        }
+        // apply_palette_clr's own checks
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t c = map[i].cmp;
+            if (W.c_prec(c) > C.ne)
+                throw GkError("pclr box: the precision of component " + std::to_string(c) + " (" + std::to_string(W.c_prec(c)) +
+                              " bits) is greater than the number of palette entries (" + std::to_string(C.ne) + "): Grok's rule (apply_palette_clr)");
+            if (map[i].mtyp == 1 && W.c_sgnd(c)) throw GkError("cmap box: a palette-mapped component cannot be signed");
+        }
+    }
+    if (!pal && !C.has_cdef) {
+        O.ch.resize(nc);
+        for (uint32_t c = 0; c < nc; ++c) {
+            O.ch[c].src = c; O.ch[c].prec = W.c_prec(c); O.ch[c].sgnd = W.c_sgnd(c);
+            O.ch[c].typ = c < 3 ? 0 : 65535; O.ch[c].asoc = c < 3 ? c + 1 : 65535;
+        }
+        return O;
+    }
+    if (W.subsampled())
+        throw GkError(std::string(pal ? "pclr / cmap" : "cdef") + " box on a stream whose components are subsampled is not supported");
+    auto comp_ch = [&](uint32_t c) {   // (GrkImage::create's defaults, GrkImage.cpp:52-67)
+        ColourOut::Ch h;
+        h.src = c; h.prec = W.c_prec(c); h.sgnd = W.c_sgnd(c);
+        h.typ = c < 3 ? 0 : 65535; h.asoc = c < 3 ? c + 1 : 65535;
+        return h;
+    };
+    if (pal) {
+        O.palette = true;
+        O.ch.resize(C.npc);
+        for (uint32_t i = 0; i < C.npc; ++i) {   // (:1359-1389: channel i lands in slot i, or in its palette column)
+            ColourOut::Ch h = comp_ch(map[i].cmp);
+            h.direct = map[i].mtyp == 0; h.col = map[i].pcol;
+            O.ch[h.direct ? i : map[i].pcol] = h;
+        }
+        for (uint32_t i = 0; i < C.npc; ++i) { O.ch[i].prec = C.pprec[i]; O.ch[i].sgnd = 0; }
+    } else {
+        O.ch.resize(nc);
+        for (uint32_t c = 0; c < nc; ++c) O.ch[c] = comp_ch(c);
+    }
+    if (C.has_cdef) {
+        O.cdef = true;
+        std::vector<Jp2Colour::Def> info = C.cdef;
+        const uint32_t n = (uint32_t)info.size(), nch = (uint32_t)O.ch.size();
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t asoc = info[i].asoc, cn = info[i].cn;
+            if (cn >= nch) continue;
+            O.ch[cn].typ = info[i].typ; O.ch[cn].asoc = asoc;
+            if (info[i].typ != 0 || asoc == 0) continue;
+            if (asoc > nch) continue;
+            const uint32_t ai = (uint16_t)(asoc - 1);
+            if (cn != ai) {
+                std::swap(O.ch[cn], O.ch[ai]);
+                for (uint32_t j = i + 1; j < n; ++j) {   // later definitions follow the swap (:918-927)
+                    if (info[j].cn == cn) info[j].cn = (uint16_t)ai;
+                    else if (info[j].cn == ai) info[j].cn = (uint16_t)cn;
+                }
+            }
+        }
+    }
+    return O;
 }
 
 }  // namespace
@@ -2566,6 +2827,14 @@ struct HostBuf {
 
 struct gk_ctx {
     uint32_t dec_layers = 0;   // quality layers to decode (0 = all; grk_dparameters::cp_layer)
+    // JP2 colour boxes (pclr + cmap, cdef): applied on decode (gk_set_decode_colour); col_inner:
+    // the call in progress is the component decode under decode_colour, col_whole: which needs
+    // every tile (its palette stage expands the whole image)
+    bool dec_colour = true, col_inner = false, col_whole = false;
+    Jp2Colour hdr_col;         // the last gk_decode_header's colour boxes and output channels
+    ColourOut hdr_out;
+    uint32_t hdr_ncs = 0;      // its codestream component count
+    std::vector<uint8_t> col_blob;   // palette stage: channel table + palette as uploaded
     // the decode in progress has a window: Grok then takes its partial-tile inverse
     // (CodeStreamDecompress.cpp:389, WaveletReverse.cpp:2237-2246), whose 5/3 single odd sample
     // across is H >> 1 (:1551-1554) where the whole-tile path has H / 2 (:583)
@@ -2597,6 +2866,7 @@ struct gk_ctx {
     DevBuf dscratch, dnmse, dord, dweight, dord_enc;
     HostBuf hinfo, hseg, hhdr, hpasses, hord, hweight, hord_enc;
     DevBuf dstage1, dstage2;   // decode: batched tile-part / packet header fetches (device input)
+    DevBuf dcol_src, dcol_out, dcol_tab;   // palette stage: index / component planes, host-bound output, tables
     HostBuf hstage1, hstage2;
     int16_t* nmse_tab = nullptr;   // device copy of the nmsedec tables (4 x 128)
     hipEvent_t ev[32];
@@ -4220,6 +4490,133 @@ struct TilePass {
     bool partial = false;
 };
 static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
+                        const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
+                        const TilePass* pass);
+// Decode of a JP2 file whose colour boxes apply (FileFormatDecompress::applyColour :378-401).
+// A cdef alone costs nothing: the caller's plane pointers are permuted and the components are
+// decoded straight into them.  With a palette the components are decoded into engine-owned
+// planes of the narrowest sample type the egress writes and k_jp2_palette (gk_colour.hip)
+// expands them into the caller's planes on the same stream; only the samples of the decoded
+// rectangle (the image, the window, either reduced) are expanded.
+static void decode_colour(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
+                          const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
+                          const Jp2Colour& C, const ColourOut& O, const Plan& W) {
+    struct Inner {
+        gk_ctx* c;
+        Inner(gk_ctx* c_, bool whole) : c(c_) { c->col_inner = true; c->col_whole = whole; }
+        ~Inner() { c->col_inner = false; c->col_whole = false; }
+    };
+    const uint32_t nout = (uint32_t)O.ch.size();
+    if (!O.palette) {   // the channels are a permutation of the components
+        std::vector<void*> cp(W.nc, nullptr);
+        std::vector<uint32_t> sp(W.nc, 0);
+        for (uint32_t k = 0; k < nout; ++k) { cp[O.ch[k].src] = comps[k]; sp[O.ch[k].src] = strides[k]; }
+        Inner in(ctx, false);
+        decode_impl(ctx, cs, len, cs_on_device, cp.data(), sp.data(), sample_bytes, out_on_device, win, nullptr);
+        return;
+    }
+    hipStream_t st = ctx->st;
+    const uint32_t red = ctx->dec_reduce;
+    auto cdp = [&](uint64_t v) { return (uint32_t)((v + ((1ull << red) - 1)) >> red); };
+    uint32_t ow, oh;
+    if (win) {
+        if (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h) throw GkError("bad decode window");
+        ow = cdp((uint64_t)win[2] + W.x0) - cdp((uint64_t)win[0] + W.x0);
+        oh = cdp((uint64_t)win[3] + W.y0) - cdp((uint64_t)win[1] + W.y0);
+        if (!ow || !oh) throw GkError("the window is empty at this reduction");
+    } else {
+        ow = cdp((uint64_t)W.x0 + W.w) - cdp(W.x0);
+        oh = cdp((uint64_t)W.y0 + W.h) - cdp(W.y0);
+    }
+    // component planes: one sign -> the 8 / 16-bit type of the largest precision, else int32
+    bool any_signed = false;
+    for (uint32_t c = 0; c < W.nc; ++c) any_signed = any_signed || W.c_sgnd(c);
+    const uint32_t sb_in = (!any_signed && W.prec <= 16) ? (W.prec + 7) / 8 : 4;
+    const int stype = sample_type(sb_in, W.prec, false);
+    bool direct_signed = false;
+    for (const auto& h : O.ch) direct_signed = direct_signed || (h.direct && W.c_sgnd(h.src));
+    if ((sample_bytes == 1 || sample_bytes == 2) && direct_signed)
+        throw GkError("8 / 16-bit output of a signed component beside palette channels: use int32 planes");
+    const int dtype = sample_type(sample_bytes, O.max_prec(), false);
+    const size_t es_in = gk_sample_size(stype), es_out = gk_sample_size(dtype);
+    const uint32_t pstride = (ow + 15) & ~15u;   // rows aligned for the kernel's vector accesses
+    const size_t plane_in = (((size_t)pstride * oh * es_in) + 255) & ~(size_t)255;
+    uint8_t* src = (uint8_t*)ctx->dcol_src.get(plane_in * W.nc);
+    {
+        std::vector<void*> cp(W.nc);
+        std::vector<uint32_t> sp(W.nc, pstride);
+        for (uint32_t c = 0; c < W.nc; ++c) cp[c] = src + plane_in * c;
+        Inner in(ctx, true);
+        decode_impl(ctx, cs, len, cs_on_device, cp.data(), sp.data(), sb_in == 4 ? 0 : sb_in, 1, win, nullptr);
+    }
+    // destination planes: the caller's device planes, or a staging copied to the host afterwards
+    std::vector<uint8_t*> dst(nout);
+    std::vector<uint32_t> dstr(nout);
+    const size_t plane_out = (((size_t)pstride * oh * es_out) + 255) & ~(size_t)255;
+    if (out_on_device) {
+        for (uint32_t k = 0; k < nout; ++k) { dst[k] = (uint8_t*)comps[k]; dstr[k] = strides[k]; }
+    } else {
+        uint8_t* stage = (uint8_t*)ctx->dcol_out.get(plane_out * nout);
+        for (uint32_t k = 0; k < nout; ++k) { dst[k] = stage + plane_out * k; dstr[k] = pstride; }
+    }
+    uint32_t vec = 1;
+    for (uint32_t k = 0; k < nout; ++k)
+        if (((uintptr_t)dst[k] % (GK_PAL_PIX * es_out)) || (dstr[k] % GK_PAL_PIX)) vec = 0;
+    // one launch per palette-mapped component (as a rule one); the first takes the direct channels
+    std::vector<uint32_t> idx_comps;
+    for (const auto& h : O.ch)
+        if (!h.direct && std::find(idx_comps.begin(), idx_comps.end(), h.src) == idx_comps.end()) idx_comps.push_back(h.src);
+    uint32_t maxp = 0;
+    for (uint8_t pr : C.pprec) maxp = std::max<uint32_t>(maxp, pr);
+    const uint32_t eb = maxp <= 8 ? 1 : 2;
+    const uint32_t ew = gk_pal_entry_words(C.npc, eb);
+    std::vector<std::vector<GkPalChan>> groups(std::max<size_t>(1, idx_comps.size()));
+    for (uint32_t k = 0; k < nout; ++k) {
+        const ColourOut::Ch& h = O.ch[k];
+        GkPalChan pc{};
+        pc.dst = dst[k]; pc.dst_stride = dstr[k]; pc.col = h.col; pc.direct = h.direct ? 1 : 0;
+        pc.src = src + plane_in * h.src; pc.src_stride = pstride;
+        const size_t g = h.direct ? 0 : (size_t)(std::find(idx_comps.begin(), idx_comps.end(), h.src) - idx_comps.begin());
+        groups[g].push_back(pc);
+    }
+    const size_t chan_bytes = (nout * sizeof(GkPalChan) + 15) & ~(size_t)15;
+    const size_t tab_bytes = (size_t)C.ne * ew * 4;
+    ctx->col_blob.assign(chan_bytes + tab_bytes, 0);
+    {
+        GkPalChan* hc = (GkPalChan*)ctx->col_blob.data();
+        for (const auto& g : groups) for (const auto& pc : g) *hc++ = pc;
+        uint8_t* ht = ctx->col_blob.data() + chan_bytes;
+        for (uint32_t j = 0; j < C.ne; ++j)
+            for (uint32_t i = 0; i < C.npc; ++i) {
+                const uint32_t v = C.lut[(size_t)j * C.npc + i];
+                uint8_t* e = ht + (size_t)j * ew * 4 + (size_t)i * eb;
+                e[0] = (uint8_t)v;
+                if (eb == 2) e[1] = (uint8_t)(v >> 8);
+            }
+    }
+    uint8_t* dblob = (uint8_t*)ctx->dcol_tab.get(ctx->col_blob.size());
+    HIPCHK(hipMemcpyAsync(dblob, ctx->col_blob.data(), ctx->col_blob.size(), hipMemcpyHostToDevice, st));
+    size_t c0 = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        if (groups[g].empty()) continue;
+        GkPalArgs a{};
+        a.npal = idx_comps.empty() ? 0 : (uint32_t)groups[g].size();
+        if (!idx_comps.empty()) { a.idx = src + plane_in * idx_comps[g]; a.idx_stride = pstride; }
+        a.w = ow; a.h = oh;
+        a.chans = (const GkPalChan*)dblob + c0; a.nchan = (uint32_t)groups[g].size();
+        a.table = (const uint32_t*)(dblob + chan_bytes); a.ne = C.ne; a.entry_words = ew; a.elem_bytes = eb;
+        a.vec_store = vec;
+        gk_launch_jp2_palette(st, stype, dtype, a);
+        c0 += groups[g].size();
+    }
+    launch_check(__LINE__);
+    if (!out_on_device)
+        for (uint32_t k = 0; k < nout; ++k)
+            HIPCHK(hipMemcpy2DAsync(comps[k], (size_t)strides[k] * es_out, dst[k], (size_t)pstride * es_out, (size_t)ow * es_out, oh,
+                                    hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+}
+static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
                         const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win = nullptr,
                         const TilePass* pass = nullptr) {
     hipStream_t st = ctx->st;
@@ -4240,9 +4637,11 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     ByteSrc S;
     S.len = len; S.st = st;
     if (cs_on_device) S.dev = cs; else S.host = cs;
+    Jp2Colour col;
     {
         size_t joff = 0, jlen = 0;
-        if (jp2_locate(S, joff, jlen)) {   // JP2 file: decode its codestream box
+        const bool colour = ctx->dec_colour && !ctx->col_inner && !pass;
+        if (jp2_locate(S, joff, jlen, colour ? &col : nullptr)) {   // JP2 file: decode its codestream box
             cs += joff; len = jlen;
             S = ByteSrc(); S.len = len; S.st = st;
             if (cs_on_device) S.dev = cs; else S.host = cs;
@@ -4250,6 +4649,13 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     }
     Header Hd;
     parse_header(S, Hd);
+    if (col.jp2 && (col.has_pclr || col.has_cdef)) {   // colour boxes that change the channels
+        const ColourOut co = resolve_colour(col, Hd.want);
+        if (co.active()) {
+            decode_colour(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, col, co, Hd.want);
+            return;
+        }
+    }
     if (pass && pass->coding) {   // the pass's tiles: their own coding and quantisation
         Hd.cod = pass->coding->cod; Hd.ccod = pass->coding->ccod; Hd.qbody = pass->coding->qbody;
         read_cod_fields(Hd.cod, Hd.want.p);
@@ -4298,6 +4704,8 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
         }
     }
     merge_tile_parts(Hd);
+    if (ctx->col_whole && !win && !pass && Hd.parts.size() != P.tiles.size())
+        throw GkError("a palette (pclr / cmap boxes) on a stream that holds only some of its tiles is not supported");
     if (pass) {
         std::vector<TilePart> keep;
         for (auto& TP : Hd.parts)
@@ -5404,30 +5812,102 @@ int gk_main_header(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters*
     }
 }
 
+// The header of a codestream or JP2 file with its colour boxes: Hd the codestream's, col the
+// jp2h boxes, out the output channels (those of the boxes when apply, else the components).
+static bool read_header_colour(ByteSrc& S, const uint8_t* cs, bool on_device, bool apply, Header& Hd, Jp2Colour& col,
+                               ColourOut& out) {
+    size_t joff = 0, jlen = 0;
+    const bool jp2 = jp2_locate(S, joff, jlen, &col);
+    if (jp2) {
+        hipStream_t st = S.st;
+        S = ByteSrc(); S.len = jlen; S.st = st;
+        if (on_device) S.dev = cs + joff; else S.host = cs + joff;
+    }
+    parse_header(S, Hd);
+    Jp2Colour none;
+    out = resolve_colour(apply ? col : none, Hd.want);
+    return jp2;
+}
+static void fill_image_info(gk_image_info* info, const Header& Hd, const ColourOut& out) {
+    info->w = Hd.want.w; info->h = Hd.want.h; info->numcomps = Hd.want.nc; info->prec = Hd.want.prec;
+    info->sgnd = Hd.want.sgnd; info->x0 = Hd.want.x0; info->y0 = Hd.want.y0;
+    if (out.active()) {   // the output channels: their count, the widest precision, channel 0's sign
+        info->numcomps = (uint32_t)out.ch.size(); info->prec = out.max_prec(); info->sgnd = out.ch[0].sgnd;
+    }
+}
+static void fill_colour_info(gk_colour_info* ci, const Jp2Colour& col, const ColourOut& out, uint32_t ncs) {
+    memset(ci, 0, sizeof(*ci));
+    ci->colour_space = col.colour_space(ncs);
+    ci->enumcs = col.enumcs; ci->meth = col.meth; ci->icc_len = (uint32_t)col.icc.size();
+    ci->has_palette = out.palette ? 1 : 0;
+    ci->palette_entries = col.ne; ci->palette_columns = col.npc;
+    ci->has_cdef = out.cdef ? 1 : 0;
+    ci->num_comps = ncs; ci->num_channels = (uint32_t)out.ch.size();
+    for (size_t k = 0; k < out.ch.size() && k < GK_MAX_CHANNELS; ++k) {
+        ci->typ[k] = (uint16_t)out.ch[k].typ; ci->asoc[k] = (uint16_t)out.ch[k].asoc;
+    }
+}
+
 int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, gk_image_info* info) {
     if (!ctx || !cs || !info) return -1;
     try {
         (void)hipSetDevice(ctx->device);
         ByteSrc S; S.len = len; S.st = ctx->st;
         if (cs_on_device) S.dev = cs; else S.host = cs;
-        size_t joff = 0, jlen = 0;
-        if (jp2_locate(S, joff, jlen)) {
-            S = ByteSrc(); S.len = jlen; S.st = ctx->st;
-            if (cs_on_device) S.dev = cs + joff; else S.host = cs + joff;
-        }
         Header Hd;
-        parse_header(S, Hd);
-        info->w = Hd.want.w; info->h = Hd.want.h; info->numcomps = Hd.want.nc; info->prec = Hd.want.prec;
-        info->sgnd = Hd.want.sgnd; info->x0 = Hd.want.x0; info->y0 = Hd.want.y0;
-        ctx->hdr_dx.assign(Hd.want.nc, 1); ctx->hdr_dy.assign(Hd.want.nc, 1);
-        ctx->hdr_prec.assign(Hd.want.nc, 0); ctx->hdr_sgnd.assign(Hd.want.nc, 0);
-        for (uint32_t c = 0; c < Hd.want.nc; ++c) {
-            ctx->hdr_dx[c] = Hd.want.sx(c); ctx->hdr_dy[c] = Hd.want.sy(c);
-            ctx->hdr_prec[c] = Hd.want.c_prec(c); ctx->hdr_sgnd[c] = Hd.want.c_sgnd(c);
+        Jp2Colour col;
+        ColourOut out;
+        read_header_colour(S, cs, cs_on_device != 0, ctx->dec_colour, Hd, col, out);
+        fill_image_info(info, Hd, out);
+        const uint32_t n = (uint32_t)out.ch.size();
+        ctx->hdr_dx.assign(n, 1); ctx->hdr_dy.assign(n, 1);
+        ctx->hdr_prec.assign(n, 0); ctx->hdr_sgnd.assign(n, 0);
+        for (uint32_t k = 0; k < n; ++k) {
+            ctx->hdr_dx[k] = Hd.want.sx(out.ch[k].src); ctx->hdr_dy[k] = Hd.want.sy(out.ch[k].src);
+            ctx->hdr_prec[k] = out.ch[k].prec; ctx->hdr_sgnd[k] = out.ch[k].sgnd;
         }
+        ctx->hdr_col = std::move(col); ctx->hdr_out = std::move(out); ctx->hdr_ncs = Hd.want.nc;
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_header_colour(gk_ctx* ctx, gk_colour_info* ci) {
+    if (!ctx || !ci) return -1;
+    if (!ctx->hdr_ncs) { ctx->err = "gk_header_colour: no header has been read"; return -1; }
+    fill_colour_info(ci, ctx->hdr_col, ctx->hdr_out, ctx->hdr_ncs);
+    return 0;
+}
+
+int gk_header_icc(gk_ctx* ctx, uint8_t* buf, size_t cap, size_t* len) {
+    if (!ctx) return -1;
+    const std::vector<uint8_t>& icc = ctx->hdr_col.icc;
+    if (len) *len = icc.size();
+    if (icc.size() > cap || (!buf && !icc.empty())) { ctx->err = "ICC profile buffer too small"; return -2; }
+    if (!icc.empty()) memcpy(buf, icc.data(), icc.size());
+    return 0;
+}
+
+int gk_set_decode_colour(gk_ctx* ctx, int apply) {
+    if (!ctx) return -1;
+    ctx->dec_colour = apply != 0;
+    return 0;
+}
+
+int gk_probe_colour(const uint8_t* cs, size_t len, gk_colour_info* ci, char* msg, size_t msg_cap) {
+    if (!cs || !ci) return -1;
+    try {
+        ByteSrc S; S.len = len; S.host = cs;
+        Header Hd;
+        Jp2Colour col;
+        ColourOut out;
+        read_header_colour(S, cs, false, true, Hd, col, out);
+        fill_colour_info(ci, col, out, Hd.want.nc);
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
         return -1;
     }
 }
@@ -5455,13 +5935,11 @@ int gk_probe_header(const uint8_t* cs, size_t len, gk_image_info* info, gk_cpara
     if (!cs || !info) return -1;
     try {
         ByteSrc S; S.len = len; S.host = cs;
-        size_t joff = 0, jlen = 0;
-        const bool jp2 = jp2_locate(S, joff, jlen);
-        if (jp2) { S = ByteSrc(); S.len = jlen; S.host = cs + joff; }
         Header Hd;
-        parse_header(S, Hd);
-        info->w = Hd.want.w; info->h = Hd.want.h; info->numcomps = Hd.want.nc; info->prec = Hd.want.prec;
-        info->sgnd = Hd.want.sgnd; info->x0 = Hd.want.x0; info->y0 = Hd.want.y0;
+        Jp2Colour col;
+        ColourOut out;
+        const bool jp2 = read_header_colour(S, cs, false, true, Hd, col, out);
+        fill_image_info(info, Hd, out);
         info->sample_bytes = 0;
         if (coding) {
             const Params& p = Hd.want.p;
@@ -5522,22 +6000,45 @@ int gk_set_subsampling(gk_ctx* ctx, uint32_t numcomps, const uint32_t* dx, const
     return 0;
 }
 
+static int probe_components(const uint8_t* cs, size_t len, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd,
+                            uint32_t cap, bool apply) {
+    if (!cs) return -1;
+    try {
+        ByteSrc S; S.len = len; S.host = cs;
+        Header Hd;
+        Jp2Colour col;
+        ColourOut out;
+        read_header_colour(S, cs, false, apply, Hd, col, out);
+        for (uint32_t c = 0; c < out.ch.size() && c < cap; ++c) {
+            if (dx) dx[c] = Hd.want.sx(out.ch[c].src);
+            if (dy) dy[c] = Hd.want.sy(out.ch[c].src);
+            if (prec) prec[c] = out.ch[c].prec;
+            if (sgnd) sgnd[c] = out.ch[c].sgnd;
+        }
+        return (int)out.ch.size();
+    } catch (const GkError&) {
+        return -1;
+    }
+}
 int gk_probe_components(const uint8_t* cs, size_t len, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd,
                         uint32_t cap) {
+    return probe_components(cs, len, dx, dy, prec, sgnd, cap, true);
+}
+int gk_probe_stream_components(const uint8_t* cs, size_t len, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd,
+                               uint32_t cap) {
+    return probe_components(cs, len, dx, dy, prec, sgnd, cap, false);
+}
+int gk_probe_icc(const uint8_t* cs, size_t len, uint8_t* buf, size_t cap, size_t* icc_len) {
     if (!cs) return -1;
     try {
         ByteSrc S; S.len = len; S.host = cs;
         size_t joff = 0, jlen = 0;
-        if (jp2_locate(S, joff, jlen)) { S = ByteSrc(); S.len = jlen; S.host = cs + joff; }
-        Header Hd;
-        parse_header(S, Hd);
-        for (uint32_t c = 0; c < Hd.want.nc && c < cap; ++c) {
-            if (dx) dx[c] = Hd.want.sx(c);
-            if (dy) dy[c] = Hd.want.sy(c);
-            if (prec) prec[c] = Hd.want.c_prec(c);
-            if (sgnd) sgnd[c] = Hd.want.c_sgnd(c);
-        }
-        return (int)Hd.want.nc;
+        Jp2Colour col;
+        jp2_locate(S, joff, jlen, &col);
+        if (icc_len) *icc_len = col.icc.size();
+        if (col.icc.size() > cap || (!buf && !col.icc.empty())) return -2;
+        if (!col.icc.empty()) memcpy(buf, col.icc.data(), col.icc.size());
+        return 0;
     } catch (const GkError&) {
         return -1;
     }

@@ -100,3 +100,30 @@ void gk_launch_ht_enc(hipStream_t st, const int32_t* coef, const GkBlock* blocks
                       uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide = false);
 void gk_launch_ht_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* ids, int32_t* coef,
                       uint32_t nblocks, int* err, bool wide = false);
+// JP2 palette expansion (gk_colour.hip).  One output channel: palette column `col` of the launch's
+// index plane, or (direct) a copy of the component plane `src`.
+struct GkPalChan {
+    void* dst;             // output plane (the launch's destination sample type)
+    const void* src;       // direct: the component's plane (the launch's source sample type)
+    uint32_t dst_stride, src_stride;   // row strides in samples
+    uint32_t col, direct;
+};
+struct GkPalArgs {
+    const void* idx;       // index plane, row stride idx_stride samples (unused when npal = 0)
+    uint32_t idx_stride;
+    uint32_t w, h;
+    const GkPalChan* chans;   // device memory: nchan channels, npal of them palette-mapped
+    uint32_t nchan, npal;
+    const uint32_t* table;    // device memory: ne entries of entry_words dwords (gk_pal_entry_words)
+    uint32_t ne, entry_words, elem_bytes;
+    uint32_t vec_store;       // every dst and its row stride are aligned to GK_PAL_PIX samples
+    uint32_t rows;            // (set by the launcher)
+};
+#define GK_PAL_PIX 8
+#define GK_PAL_LDS_BYTES 65536u   // tables up to this size are staged in LDS
+// dwords per table entry: the columns padded to dwords, then to an odd count
+uint32_t gk_pal_entry_words(uint32_t npc, uint32_t elem_bytes);
+// stype / dtype: GK_U8, GK_U16 or GK_S32 planes in / out; idx, every src and their strides must be
+// aligned to GK_PAL_PIX samples.  Returns the table path taken: 0 LDS (one dword per entry),
+// 1 LDS, 2 global gather; < 0: nothing to do.
+int gk_launch_jp2_palette(hipStream_t st, int stype, int dtype, const GkPalArgs& args);

@@ -208,6 +208,12 @@ struct CodecObj : Obj {
     bool tile_decoded = false;               // grk_decompress_tile cropped `out` to a tile
     std::vector<uint32_t> cdx, cdy;          // the stream's component subsampling (SIZ XRsiz / YRsiz)
     std::vector<uint32_t> cprec, csgnd;      // and precision / signedness (Ssiz)
+    // JP2 colour boxes (FileFormatDecompress::readHeader :198-280, applyColour :378-401): the
+    // header image shows the codestream's components; a decompress turns it into the output
+    // channels of the palette / channel definition, whose description these hold
+    gk_colour_info colour{};
+    bool colour_applies = false;             // a pclr + cmap or a cdef changes the channels
+    std::vector<uint32_t> oprec, osgnd;      // the output channels' precision / signedness
     ~CodecObj() override {
         if (stream) grk_object_unref(stream);
         if (image) grk_object_unref(&image->obj);
@@ -336,8 +342,8 @@ ImageObj* region_image(CodecObj* C, uint32_t x0, uint32_t y0, uint32_t x1, uint3
         q.w = reduced(ceil_div(x1, q.dx), r) - q.x0; q.h = reduced(ceil_div(y1, q.dy), r) - q.y0;
         q.prec = (uint8_t)C->cprec[k]; q.sgnd = C->csgnd[k] != 0;
     }
-    GRK_COLOR_SPACE cs = GRK_CLRSPC_UNKNOWN;
-    if (C->coding.cod_format == 2) cs = C->info.numcomps < 3 ? GRK_CLRSPC_GRAY : GRK_CLRSPC_SRGB;
+    // the colr box's space (GRK_CLRSPC_ICC with a METH 2 profile); unknown for a raw codestream
+    const GRK_COLOR_SPACE cs = (GRK_COLOR_SPACE)C->colour.colour_space;
     // sample memory is attached by the decompress call (Grok allocates the composite's planes
     // at decompress time too), so a header read of a 32768^2 .jp2 holds no planes
     ImageObj* o = new_image((uint16_t)C->info.numcomps, p.data(), cs, false);
@@ -366,6 +372,28 @@ bool reshape_image(ImageObj* o, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t 
         }
     }
     return true;
+}
+
+// FileFormatDecompress::applyColour on the composited image, in place (callers hold the pointer):
+// the components become the output channels of the palette (their precisions, unsigned) in the
+// channel definition's order, each with its cdef type and association.  The planes are attached
+// by reshape_image afterwards and filled by the engine, which applies the boxes itself.
+void apply_colour_shape(CodecObj* C, ImageObj* o) {
+    if (!C->colour_applies || o->img.color_applied) return;
+    const uint32_t n = C->colour.num_channels;
+    const grk_image_comp first = o->comps[0];
+    for (auto& c : o->comps) { free(c.data); c.data = nullptr; }
+    o->comps.assign(n, first);
+    for (uint32_t k = 0; k < n; ++k) {
+        grk_image_comp& c = o->comps[k];
+        c.data = nullptr;
+        c.prec = (uint8_t)C->oprec[k]; c.sgnd = C->osgnd[k] != 0;
+        c.type = (GRK_COMPONENT_TYPE)C->colour.typ[k];
+        c.association = (GRK_COMPONENT_ASSOC)C->colour.asoc[k];
+    }
+    o->img.comps = o->comps.data();
+    o->img.numcomps = (uint16_t)n;
+    o->img.color_applied = true;
 }
 
 }  // namespace
@@ -620,13 +648,30 @@ bool grk_decompress_read_header(grk_codec* codec, grk_header_info* hi) {
             error("%s", msg);
             return false;
         }
+        if (gk_probe_colour(C->data.data(), C->data.size(), &C->colour, msg, sizeof msg) != 0) {
+            error("%s", msg);
+            return false;
+        }
+        C->colour_applies = C->colour.has_palette || C->colour.has_cdef;
+        if (C->colour.num_channels > GK_MAX_CHANNELS) { error("more than %d output channels", GK_MAX_CHANNELS); return false; }
+        // (gk_probe_header reported the output channels; the header image has the codestream's components)
+        C->oprec.assign(C->info.numcomps, C->info.prec); C->osgnd.assign(C->info.numcomps, C->info.sgnd);
+        if (gk_probe_components(C->data.data(), C->data.size(), nullptr, nullptr, C->oprec.data(), C->osgnd.data(),
+                                C->info.numcomps) < 0) {
+            error("cannot read the output channels");
+            return false;
+        }
+        C->info.numcomps = C->colour.num_comps;
         C->cdx.assign(C->info.numcomps, 1); C->cdy.assign(C->info.numcomps, 1);
         C->cprec.assign(C->info.numcomps, C->info.prec); C->csgnd.assign(C->info.numcomps, C->info.sgnd);
-        if (gk_probe_components(C->data.data(), C->data.size(), C->cdx.data(), C->cdy.data(), C->cprec.data(),
-                                C->csgnd.data(), C->info.numcomps) < 0) {
+        if (gk_probe_stream_components(C->data.data(), C->data.size(), C->cdx.data(), C->cdy.data(), C->cprec.data(),
+                                       C->csgnd.data(), C->info.numcomps) < 0) {
             error("cannot read the component subsampling");
             return false;
         }
+        C->info.prec = 0;
+        for (uint32_t p : C->cprec) C->info.prec = std::max(C->info.prec, p);
+        C->info.sgnd = C->csgnd[0];
         C->header_read = true;
         if (C->dp.cp_reduce >= C->coding.numresolution) {
             error("reduce %u must be less than the number of resolutions %u", C->dp.cp_reduce, C->coding.numresolution);
@@ -635,6 +680,19 @@ bool grk_decompress_read_header(grk_codec* codec, grk_header_info* hi) {
         // the composited image: the image area on the canvas (components reduced by cp_reduce)
         C->out = region_image(C, C->info.x0, C->info.y0, C->info.x0 + C->info.w, C->info.y0 + C->info.h);
         if (!C->out) return false;
+        if (C->colour.icc_len) {   // the colr box's ICC profile travels in the image's meta (:272-280)
+            grk_image_meta* m = grk_image_meta_new();
+            m->color.icc_profile_buf = (uint8_t*)malloc(C->colour.icc_len);
+            size_t n = 0;
+            if (!m->color.icc_profile_buf ||
+                gk_probe_icc(C->data.data(), C->data.size(), m->color.icc_profile_buf, C->colour.icc_len, &n) != 0) {
+                grk_object_unref(&m->obj);
+                error("cannot read the ICC profile");
+                return false;
+            }
+            m->color.icc_profile_len = (uint32_t)n;
+            C->out->img.meta = m;
+        }
     }
     if (hi) {
         const gk_cparameters& k = C->coding;
@@ -684,6 +742,7 @@ bool grk_decompress(grk_codec* codec, grk_plugin_tile* tile) {
     if (tile) { error("plugin tiles are not used: the tile pipeline runs in this library"); return false; }
     if (!C->header_read && !grk_decompress_read_header(codec, nullptr)) return false;
     const uint32_t OX = C->info.x0, OY = C->info.y0;   // composited images are canvas rectangles
+    apply_colour_shape(C, C->out);
     if (C->has_win) {
         // (the components: the window's canvas rectangle reduced by cp_reduce)
         if (!reshape_image(C->out, C->win[0] + OX, C->win[1] + OY, C->win[2] + OX, C->win[3] + OY, C->dp.cp_reduce))
@@ -724,6 +783,7 @@ bool grk_decompress_tile(grk_codec* codec, uint16_t tileIndex) {
         }
     }
     // (with cp_reduce the components take the tile's rectangle reduced, CodeStreamDecompress.cpp:471-481)
+    apply_colour_shape(C, C->out);
     if (!reshape_image(C->out, w[0] + OX, w[1] + OY, w[2] + OX, w[3] + OY, C->dp.cp_reduce)) return false;
     C->tile_decoded = true;
     // wholeTileDecompress stays set unless a window was (CodeStreamDecompress.cpp:389)

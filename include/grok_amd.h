@@ -212,6 +212,48 @@ int gk_probe_components(const uint8_t* cs, size_t len, uint32_t* dx, uint32_t* d
  * component count. */
 int gk_header_components(gk_ctx* ctx, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd, uint32_t cap);
 
+/* JP2 colour boxes (jp2h: colr, pclr, cmap, cdef; FileFormatDecompress::readHeader :198-280 and
+ * applyColour :378-401).  A decode applies them as Grok's library does: a palette (pclr + cmap)
+ * expands the mapped components into its columns (apply_palette_clr :1299-1436, indices clamped
+ * to the palette) and a cdef reorders the channels (apply_channel_definition :876-930), so
+ * gk_decode_header / gk_probe_header report the OUTPUT channel count and the widest channel
+ * precision, gk_header_components / gk_probe_components each channel's precision and sign, and
+ * gk_decode / gk_decode_window write one plane per output channel (8 / 16-bit planes sized by the
+ * widest channel).  Files without pclr + cmap / cdef, and raw codestreams, decode as before. */
+#define GK_MAX_CHANNELS 256   /* channels described in gk_colour_info (more are counted, not described) */
+typedef struct gk_colour_info {
+    uint32_t colour_space;     /* GRK_COLOR_SPACE: 0 unknown, 2 sRGB, 3 grey, 4 sYCC, 5 e-YCC, 6 CMYK, 9 ICC */
+    uint32_t enumcs;           /* colr EnumCS as read (METH 1), else 0 */
+    uint32_t meth;             /* colr METH of the accepted box (1 / 2), 0: none accepted */
+    uint32_t icc_len;          /* bytes of the METH 2 profile (gk_header_icc) */
+    uint32_t has_palette;      /* pclr + cmap present and applied */
+    uint32_t palette_entries, palette_columns;   /* pclr NE / NPC (also of a pclr dropped for want of a cmap) */
+    uint32_t has_cdef;         /* cdef present and applied */
+    uint32_t num_comps;        /* components of the codestream */
+    uint32_t num_channels;     /* output channels */
+    uint16_t typ[GK_MAX_CHANNELS];    /* per output channel: cdef Typ (0 colour, 1 opacity, 2 premultiplied opacity, */
+    uint16_t asoc[GK_MAX_CHANNELS];   /* 65535 unspecified) and Asoc (0 whole image, 1..3 colour, 65535 none);
+                                         without a cdef Grok's defaults: colour 1..3, then unspecified */
+} gk_colour_info;
+/* Colour description of host codestream / JP2 bytes, no device needed (like gk_probe_header);
+ * < 0 with the reason, naming the box, in msg. */
+int gk_probe_colour(const uint8_t* cs, size_t len, gk_colour_info* info, char* msg, size_t msg_cap);
+/* The ICC profile of host JP2 bytes, no device needed: as gk_header_icc. */
+int gk_probe_icc(const uint8_t* cs, size_t len, uint8_t* buf, size_t cap, size_t* icc_len);
+/* gk_probe_components for the codestream's own components, the colour boxes not applied (what a
+ * header read shows before Grok's applyColour has run). */
+int gk_probe_stream_components(const uint8_t* cs, size_t len, uint32_t* dx, uint32_t* dy, uint32_t* prec,
+                               uint32_t* sgnd, uint32_t cap);
+/* gk_probe_colour for the stream the last gk_decode_header read. */
+int gk_header_colour(gk_ctx* ctx, gk_colour_info* info);
+/* Its ICC profile (colr METH 2; grk_image_meta's color.icc_profile_buf): *len receives the size,
+ * the bytes are copied when cap holds them (-2 otherwise). */
+int gk_header_icc(gk_ctx* ctx, uint8_t* buf, size_t cap, size_t* len);
+/* apply = 1 (default): later gk_decode_header / gk_decode / gk_decode_window calls apply the
+ * palette and channel definition.  apply = 0: they return the codestream's components untouched
+ * (the colour description is still read). */
+int gk_set_decode_colour(gk_ctx* ctx, int apply);
+
 /* Inverse 5/3 rule of later gk_decode_window calls.  whole_tile = 0 (default): Grok's partial-tile
  * inverse, which a window set through setDecompressWindow selects for every tile
  * (CodeStreamDecompress.cpp:389; a one-sample-wide resolution on an odd coordinate shifts its
