@@ -26,8 +26,9 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_last_error", "gk_version", "gk_set_decode_layers", "gk_set_decode_reduce",
            "gk_set_window_rule", "gk_set_subsampling", "gk_probe_components", "gk_header_components",
            "gk_probe_colour", "gk_header_colour", "gk_header_icc", "gk_set_decode_colour", "gk_probe_icc",
-           "gk_probe_stream_components")
+           "gk_probe_stream_components", "gk_set_decode_display", "gk_probe_display")
 GK_MAX_CHANNELS = 256
+GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE = 1, 2   # gk_set_decode_display flags
 
 
 class Poc(ctypes.Structure):
@@ -81,7 +82,8 @@ class ColourInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("colour_space", "enumcs", "meth", "icc_len", "has_palette",
                                                "palette_entries", "palette_columns", "has_cdef", "num_comps",
                                                "num_channels")] + \
-               [("typ", ctypes.c_uint16 * GK_MAX_CHANNELS), ("asoc", ctypes.c_uint16 * GK_MAX_CHANNELS)]
+               [("typ", ctypes.c_uint16 * GK_MAX_CHANNELS), ("asoc", ctypes.c_uint16 * GK_MAX_CHANNELS),
+                ("display_applied", ctypes.c_uint32)]
 
     def channels(self):
         """[(typ, asoc)] per output channel (cdef Typ / Asoc, or Grok's defaults)."""
@@ -151,6 +153,12 @@ def load_library(build_if_missing=True):
     lib.gk_header_icc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]
     lib.gk_set_decode_colour.restype = ctypes.c_int
     lib.gk_set_decode_colour.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.gk_set_decode_display.restype = ctypes.c_int
+    lib.gk_set_decode_display.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.gk_probe_display.restype = ctypes.c_int
+    lib.gk_probe_display.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, P(ImageInfo),
+                                     P(ColourInfo)] + [P(ctypes.c_uint32)] * 4 + [ctypes.c_uint32, ctypes.c_char_p,
+                                                                                  ctypes.c_size_t]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -264,6 +272,38 @@ def probe_icc(cs):
     if n.value and lib.gk_probe_icc(b.ctypes.data, len(b), buf.ctypes.data, buf.size, ctypes.byref(n)) != 0:
         raise ValueError("gk_probe_icc failed")
     return buf[:n.value].tobytes()
+
+
+class DisplayInfo:
+    """What probe_display reports: the output of a decode under the display flags."""
+
+    def __init__(self, info, colour, chans, reduce):
+        self.info, self.colour = info, colour
+        self.channels = [(dx, dy) for dx, dy, _, _ in chans]          # (dx, dy) per output channel
+        self.precisions = [pr for _, _, pr, _ in chans]
+        self.signed = [bool(sg) for _, _, _, sg in chans]
+        self.shapes = [comp_shape(info.w, info.h, dx, dy, (info.x0, info.y0), reduce) for dx, dy, _, _ in chans]
+        self.colour_space = colour.colour_space
+        self.converted = bool(colour.display_applied & GK_DISPLAY_RGB)
+        self.upsampled = bool(colour.display_applied & GK_DISPLAY_UPSAMPLE)
+
+
+def probe_display(cs, rgb=False, upsample=False, reduce=0):
+    """gk_probe_display: what a decode of host codestream / JP2 bytes returns under
+    Engine.set_decode_display(rgb, upsample) and set_decode_reduce(reduce), no engine or GPU
+    needed: a DisplayInfo with the channel shapes (rows, cols), precisions, signs, colour space
+    (GRK_COLOR_SPACE) and the converted / upsampled flags.  Raises ValueError with the refusal."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    info, colour = ImageInfo(), ColourInfo()
+    dx, dy, pr, sg = [(ctypes.c_uint32 * 16384)() for _ in range(4)]
+    msg = ctypes.create_string_buffer(512)
+    flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0)
+    n = lib.gk_probe_display(b.ctypes.data, len(b), flags, int(reduce), ctypes.byref(info), ctypes.byref(colour),
+                             dx, dy, pr, sg, 16384, msg, 512)
+    if n < 0:
+        raise ValueError(msg.value.decode())
+    return DisplayInfo(info, colour, [(dx[c], dy[c], pr[c], sg[c]) for c in range(n)], int(reduce))
 
 
 def probe_components(cs, precision=False):
@@ -588,6 +628,15 @@ class Engine:
         the default: planes are the output channels) or return the codestream's components (False)."""
         if self.lib.gk_set_decode_colour(self.ctx, int(bool(apply))) != 0:
             self._err("gk_set_decode_colour")
+
+    def set_decode_display(self, rgb=False, upsample=False):
+        """gk_set_decode_display: what grk_decompress does to the decoded image, on the GPU.  rgb:
+        sYCC (4:4:4, 4:2:2, 4:2:0), e-sYCC and CMYK images decode to RGB planes; upsample: subsampled
+        components are replicated to the image grid (grk_decompress -u).  Sticky; read_header,
+        subsampling and colour_info then describe the output, so decode returns one (C, H, W) array."""
+        flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0)
+        if self.lib.gk_set_decode_display(self.ctx, flags) != 0:
+            self._err("gk_set_decode_display")
 
     def decode_window(self, cs, window, length=None, out=None, sample_bytes=0):
         """gk_decode_window: window = (x0, y0, x1, y1).  Returns a (C, y1-y0, x1-x0) numpy

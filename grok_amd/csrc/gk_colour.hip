@@ -1,4 +1,5 @@
-// gk_colour.hip — JP2 palette expansion on decode (pclr + cmap boxes).
+// gk_colour.hip — JP2 palette expansion on decode (pclr + cmap boxes), and the display stage
+// (sYCC / e-sYCC / CMYK to RGB, chroma upsampling: second half of the file).
 //
 // FileFormatDecompress::apply_palette_clr (FileFormatDecompress.cpp:1299-1436) walks the index
 // plane once per output channel and writes int32 planes.  k_jp2_palette reads each index sample
@@ -151,4 +152,316 @@ int gk_launch_jp2_palette(hipStream_t st, int stype, int dtype, const GkPalArgs&
     else if (stype == GK_U16) launch_s<uint16_t>(st, dtype, a, mode, grid, lds);
     else launch_s<int32_t>(st, dtype, a, mode, grid, lds);
     return mode;
+}
+
+// ---------------------------------------------------------------------------
+// Display stage: what Grok's CLI does to the decoded image (GrkDecompress::postProcess,
+// grk_decompress.cpp:1300-1506), on the device.
+//
+// k_ycc_rgb  color_sycc_to_rgb / color_esycc_to_rgb (bin/common/color.cpp:86-418, 1027-1086)
+// k_cmyk_rgb color_cmyk_to_rgb (:970-1024)
+// k_upsample upsample_image_components (bin/common/convert.cpp:209-360)
+//
+// All three are gathers: no LDS, no cross-lane traffic.  As in k_jp2_palette a thread owns
+// GK_PAL_PIX consecutive samples of a row (16 bytes per lane of 16-bit samples, 8 of 8-bit, two
+// 16-byte accesses of int32), loaded and stored as one vector where the rows are aligned (the
+// engine's source planes always are) and sample by sample in the last, partial vector of a row.
+// In the subsampled sYCC modes the thread's block is PIX columns of one row (4:2:2) or of a row
+// pair (4:2:0): the PIX / 2 (+ 1 with an odd origin) chroma samples under it are loaded once,
+// their three integer terms computed once, and used for the 2 or 4 pixels they cover.
+//
+// Arithmetic.  The reference is host code compiled without contraction: sYCC and e-sYCC in
+// double, CMYK in float, each product and sum rounded on its own, the cast truncating.  hipcc
+// contracts a * b + c into an FMA in device code by default, so every function below that does
+// floating-point arithmetic carries `#pragma clang fp contract(off)` (the pragma rather than
+// per-operation intrinsics: HIP's __dmul_rn / __dadd_rn are plain operators to the compiler and
+// would be contracted all the same).
+//
+// Which chroma sample a pixel takes (sycc422_to_rgb :170-254, sycc420_to_rgb :256-377), with
+// ofx / ofy the parities of the image origin, rx = x - ofx, ry = y - ofy:
+//   4:2:2  x < ofx: Cb = Cr = 0 as passed in (-offset after the subtraction, not neutral),
+//          else chroma[y][rx / 2]; an unpaired last column takes the next sample, which is the
+//          same expression.
+//   4:2:0  y < ofy: the whole row takes 0; else chroma[ry / 2][rx / 2] and 0 for x < ofx, except
+//          - ofx = ofy = 1 (:316-320): column 0 takes 0 in the first row of a pair but
+//            chroma[ry / 2][0] in the second, and an unpaired last row (:344-357) ignores ofx:
+//            chroma[ry / 2][x / 2] from column 0 on;
+//          - ofy = 1, ofx = 0: column 0 of the first row of each pair takes 0.
+//          (For ofx != ofy the reference's loops leave the planes; DESIGN.md says what is kept.)
+namespace {
+struct Rgb { int32_t r, g, b; };
+
+// the chroma terms of sycc_to_rgb (:91-107): (int32_t)(1.402 * cr), (int32_t)(0.344 * cb + 0.714 * cr),
+// (int32_t)(1.772 * cb) after the offset subtraction
+__device__ __forceinline__ Rgb sycc_terms(int32_t cb, int32_t cr, int32_t offset) {
+#pragma clang fp contract(off)
+    cb -= offset;
+    cr -= offset;
+    Rgb t;
+    t.r = (int32_t)(1.402 * (double)cr);
+    const double g0 = 0.344 * (double)cb, g1 = 0.714 * (double)cr;
+    t.g = (int32_t)(g0 + g1);
+    t.b = (int32_t)(1.772 * (double)cb);
+    return t;
+}
+__device__ __forceinline__ int32_t clamp_upb(int32_t v, int32_t upb) { return v < 0 ? 0 : (v > upb ? upb : v); }
+__device__ __forceinline__ Rgb sycc_px(int32_t y, const Rgb& t, int32_t upb) {
+    Rgb o;
+    o.r = clamp_upb(y + t.r, upb);
+    o.g = clamp_upb(y - t.g, upb);
+    o.b = clamp_upb(y + t.b, upb);
+    return o;
+}
+// color_esycc_to_rgb (:1047-1078): left to right in double, + 0.5, truncated, clamped
+__device__ __forceinline__ Rgb esycc_px(int32_t yi, int32_t cbi, int32_t cri, const GkYccArgs& a) {
+#pragma clang fp contract(off)
+    if (a.flip_cb) cbi -= a.offset;
+    if (a.flip_cr) cri -= a.offset;
+    const double y = (double)yi, cb = (double)cbi, cr = (double)cri;
+    double t, m;
+    Rgb o;
+    m = 0.0000368 * cb; t = y - m; m = 1.40199 * cr; t = t + m; t = t + 0.5;
+    o.r = clamp_upb((int32_t)t, a.upb);
+    t = 1.0003 * y; m = 0.344125 * cb; t = t - m; m = 0.7141128 * cr; t = t - m; t = t + 0.5;
+    o.g = clamp_upb((int32_t)t, a.upb);
+    t = 0.999823 * y; m = 1.77204 * cb; t = t + m; m = 0.000008 * cr; t = t - m; t = t + 0.5;
+    o.b = clamp_upb((int32_t)t, a.upb);
+    return o;
+}
+
+template <typename SRC> __device__ __forceinline__ void load_row(const SRC* s, bool whole, uint32_t n, int32_t out[PIX]) {
+    typedef typename Vec<SRC, PIX>::type SV;
+    if (whole) {
+        const SV v = *(const SV*)s;
+#pragma unroll
+        for (int p = 0; p < PIX; ++p) out[p] = (int32_t)v[p];
+    } else {
+#pragma unroll
+        for (int p = 0; p < PIX; ++p) out[p] = p < (int)n ? (int32_t)s[p] : 0;
+    }
+}
+template <typename DST> __device__ __forceinline__ void store_row(DST* d, bool vec, uint32_t n, const int32_t v[PIX]) {
+    typedef typename Vec<DST, PIX>::type DV;
+    if (vec) {
+        DV o;
+#pragma unroll
+        for (int p = 0; p < PIX; ++p) o[p] = (DST)v[p];
+        *(DV*)d = o;
+    } else {
+#pragma unroll
+        for (int p = 0; p < PIX; ++p) if (p < (int)n) d[p] = (DST)v[p];
+    }
+}
+template <typename DST> __device__ __forceinline__ void store_rgb(const GkYccArgs& a, uint32_t y, uint32_t x, bool vec, uint32_t n,
+                                                                  const Rgb px[PIX]) {
+    int32_t v[PIX];
+#pragma unroll
+    for (int p = 0; p < PIX; ++p) v[p] = px[p].r;
+    store_row<DST>((DST*)a.dst[0] + (size_t)y * a.ds[0] + x, vec, n, v);
+#pragma unroll
+    for (int p = 0; p < PIX; ++p) v[p] = px[p].g;
+    store_row<DST>((DST*)a.dst[1] + (size_t)y * a.ds[1] + x, vec, n, v);
+#pragma unroll
+    for (int p = 0; p < PIX; ++p) v[p] = px[p].b;
+    store_row<DST>((DST*)a.dst[2] + (size_t)y * a.ds[2] + x, vec, n, v);
+}
+
+// One row unit per iteration: a row (4:4:4, e-sYCC, 4:2:2) or, in 4:2:0, the rows sharing one
+// chroma row: unit u < ofy is row 0 alone, unit u >= ofy rows ofy + 2 (u - ofy) and the next.
+template <typename SRC, typename DST, int MODE>
+__global__ __launch_bounds__(256) void k_ycc_rgb(GkYccArgs a) {
+    const uint32_t x = (blockIdx.x * 256 + threadIdx.x) * PIX;
+    if (x >= a.w) return;
+    const bool whole = x + PIX <= a.w;
+    const uint32_t n = whole ? PIX : a.w - x;
+    const bool vst = whole && a.vec_store;
+    const uint32_t units = MODE == GK_YCC_420 ? a.ofy + (a.h - a.ofy + 1) / 2 : a.h;
+    const uint32_t u0 = blockIdx.y * a.rows, u1 = min(units, u0 + a.rows);
+    for (uint32_t u = u0; u < u1; ++u) {
+        int32_t ya[PIX];
+        Rgb px[PIX];
+        if (MODE == GK_YCC_444 || MODE == GK_YCC_ESYCC) {
+            int32_t cb[PIX], cr[PIX];
+            load_row<SRC>((const SRC*)a.y + (size_t)u * a.ys + x, whole, n, ya);
+            load_row<SRC>((const SRC*)a.cb + (size_t)u * a.cs + x, whole, n, cb);
+            load_row<SRC>((const SRC*)a.cr + (size_t)u * a.cs + x, whole, n, cr);
+#pragma unroll
+            for (int p = 0; p < PIX; ++p)
+                px[p] = MODE == GK_YCC_444 ? sycc_px(ya[p], sycc_terms(cb[p], cr[p], a.offset), a.upb) : esycc_px(ya[p], cb[p], cr[p], a);
+            store_rgb<DST>(a, u, x, vst, n, px);
+            continue;
+        }
+        // subsampled: rows of the unit, its chroma row, and whether the columns pair from ofx
+        uint32_t y, crow;
+        bool zero_row = false, two = false;
+        if (MODE == GK_YCC_422) { y = u; crow = u; }
+        else if (u < a.ofy) { y = 0; crow = 0; zero_row = true; }
+        else { crow = u - a.ofy; y = a.ofy + 2 * crow; two = y + 1 < a.h; }
+        // 4:2:0 with both parities odd: the unpaired last row pairs its columns from 0
+        const uint32_t ofx = (MODE == GK_YCC_420 && a.ofx && a.ofy && !two && !zero_row) ? 0u : a.ofx;
+        Rgb t[PIX];       // chroma terms per column
+        const Rgb tz = sycc_terms(0, 0, a.offset);
+        if (zero_row) {
+#pragma unroll
+            for (int p = 0; p < PIX; ++p) t[p] = tz;
+        } else {
+            typedef typename Vec<SRC, PIX / 2>::type HV;
+            const SRC* pb = (const SRC*)a.cb + (size_t)crow * a.cs;
+            const SRC* pr = (const SRC*)a.cr + (size_t)crow * a.cs;
+            if (whole && !ofx) {
+                const HV vb = *(const HV*)(pb + x / 2), vr = *(const HV*)(pr + x / 2);
+#pragma unroll
+                for (int q = 0; q < PIX / 2; ++q) t[2 * q] = t[2 * q + 1] = sycc_terms((int32_t)vb[q], (int32_t)vr[q], a.offset);
+            } else {
+#pragma unroll
+                for (int p = 0; p < PIX; ++p) {
+                    const uint32_t xp = x + p;
+                    if (xp >= a.w) t[p] = tz;
+                    else if (xp < ofx) t[p] = tz;
+                    else if (p > 0 && x + p - 1 >= ofx && ((xp - ofx) & 1)) t[p] = t[p - 1];
+                    else { const uint32_t cc = (xp - ofx) >> 1; t[p] = sycc_terms((int32_t)pb[cc], (int32_t)pr[cc], a.offset); }
+                }
+            }
+        }
+        load_row<SRC>((const SRC*)a.y + (size_t)y * a.ys + x, whole, n, ya);
+#pragma unroll
+        for (int p = 0; p < PIX; ++p) px[p] = sycc_px(ya[p], t[p], a.upb);
+        // column 0 of the first row of a pair takes Cb = Cr = 0 when the origin's row is odd (:316-320)
+        if (MODE == GK_YCC_420 && x == 0 && two && a.ofy) px[0] = sycc_px(ya[0], tz, a.upb);
+        store_rgb<DST>(a, y, x, vst, n, px);
+        if (two) {
+            load_row<SRC>((const SRC*)a.y + (size_t)(y + 1) * a.ys + x, whole, n, ya);
+#pragma unroll
+            for (int p = 0; p < PIX; ++p) px[p] = sycc_px(ya[p], t[p], a.upb);
+            // ... and its second row the first chroma sample of the row (:319) when both parities are odd
+            if (x == 0 && a.ofx && a.ofy) {
+                const SRC* pb = (const SRC*)a.cb + (size_t)crow * a.cs;
+                const SRC* pr = (const SRC*)a.cr + (size_t)crow * a.cs;
+                px[0] = sycc_px(ya[0], sycc_terms((int32_t)pb[0], (int32_t)pr[0], a.offset), a.upb);
+            }
+            store_rgb<DST>(a, y + 1, x, vst, n, px);
+        }
+    }
+}
+
+template <typename SRC, typename DST>
+__global__ __launch_bounds__(256) void k_cmyk_rgb(GkCmykArgs a) {
+#pragma clang fp contract(off)
+    const uint32_t x = (blockIdx.x * 256 + threadIdx.x) * PIX;
+    if (x >= a.w) return;
+    const bool whole = x + PIX <= a.w;
+    const uint32_t n = whole ? PIX : a.w - x;
+    const bool vst = whole && a.vec_store;
+    const uint32_t y0 = blockIdx.y * a.rows, y1 = min(a.h, y0 + a.rows);
+    for (uint32_t y = y0; y < y1; ++y) {
+        int32_t in[4][PIX];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) load_row<SRC>((const SRC*)a.src[k] + (size_t)y * a.ss + x, whole, n, in[k]);
+        float K[PIX];
+#pragma unroll
+        for (int p = 0; p < PIX; ++p) { const float k = (float)in[3][p] * a.scale[3]; K[p] = 1.0F - k; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            int32_t v[PIX];
+#pragma unroll
+            for (int p = 0; p < PIX; ++p) {
+                float c = (float)in[k][p] * a.scale[k];
+                c = 1.0F - c;
+                const float m = 255.0F * c;
+                v[p] = (int32_t)(m * K[p]);
+            }
+            store_row<DST>((DST*)a.dst[k] + (size_t)y * a.ds[k] + x, vst, n, v);
+        }
+    }
+}
+
+template <typename SRC, typename DST>
+__global__ __launch_bounds__(256) void k_upsample(GkUpArgs a) {
+    const uint32_t x = (blockIdx.x * 256 + threadIdx.x) * PIX;
+    if (x >= a.w) return;
+    const bool whole = x + PIX <= a.w;
+    const uint32_t n = whole ? PIX : a.w - x;
+    const bool vst = whole && a.vec_store;
+    // source column and phase of the thread's first sample at or after xoff
+    const uint32_t xs = max(x, a.xoff);
+    const uint32_t q0 = (xs - a.xoff) / a.dx, r0 = (xs - a.xoff) % a.dx;
+    const uint32_t y0 = blockIdx.y * a.rows, y1 = min(a.h, y0 + a.rows);
+    for (uint32_t y = y0; y < y1; ++y) {
+        int32_t v[PIX];
+        if (y < a.yoff) {
+#pragma unroll
+            for (int p = 0; p < PIX; ++p) v[p] = 0;
+        } else {
+            const SRC* s = (const SRC*)a.src + (size_t)((y - a.yoff) / a.dy) * a.ss;
+            // whole vectors of the two common grids take one vector load: a copy (dx = 1) and
+            // 2:1 from an even origin; every other case gathers sample by sample
+            if (whole && a.xoff == 0 && a.dx == 1) {
+                load_row<SRC>(s + x, true, n, v);
+                store_row<DST>((DST*)a.dst + (size_t)y * a.ds + x, vst, n, v);
+                continue;
+            }
+            if (whole && a.xoff == 0 && a.dx == 2) {
+                typedef typename Vec<SRC, PIX / 2>::type HV;
+                const HV hv = *(const HV*)(s + x / 2);
+#pragma unroll
+                for (int p = 0; p < PIX; ++p) v[p] = (int32_t)hv[p >> 1];
+                store_row<DST>((DST*)a.dst + (size_t)y * a.ds + x, vst, n, v);
+                continue;
+            }
+            uint32_t q = q0, r = r0;
+            int32_t cur = 0;
+            bool have = false;
+#pragma unroll
+            for (int p = 0; p < PIX; ++p) {
+                if (x + p < a.xoff || p >= (int)n) { v[p] = 0; continue; }
+                if (!have) { cur = (int32_t)s[q]; have = true; }
+                v[p] = cur;
+                if (++r == a.dx) { r = 0; ++q; have = false; }
+            }
+        }
+        store_row<DST>((DST*)a.dst + (size_t)y * a.ds + x, vst, n, v);
+    }
+}
+
+inline uint32_t rows_per_group(uint32_t units) { return std::max(4u, (units + 65534) / 65535); }   // (grid.y limit)
+
+template <typename SRC, typename DST>
+void launch_ycc(hipStream_t st, const GkYccArgs& a, dim3 grid) {
+    switch (a.mode) {
+        case GK_YCC_444: hipLaunchKernelGGL((k_ycc_rgb<SRC, DST, GK_YCC_444>), grid, dim3(256), 0, st, a); break;
+        case GK_YCC_422: hipLaunchKernelGGL((k_ycc_rgb<SRC, DST, GK_YCC_422>), grid, dim3(256), 0, st, a); break;
+        case GK_YCC_420: hipLaunchKernelGGL((k_ycc_rgb<SRC, DST, GK_YCC_420>), grid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((k_ycc_rgb<SRC, DST, GK_YCC_ESYCC>), grid, dim3(256), 0, st, a); break;
+    }
+}
+// T names the destination element type in the body
+#define GK_DISPLAY_DST(t, T, ...)                                 \
+    if ((t) == GK_U8) { typedef uint8_t T; __VA_ARGS__; }         \
+    else if ((t) == GK_U16) { typedef uint16_t T; __VA_ARGS__; }  \
+    else { typedef int32_t T; __VA_ARGS__; }
+}  // namespace
+
+void gk_launch_ycc_rgb(hipStream_t st, int stype, int dtype, const GkYccArgs& args) {
+    GkYccArgs a = args;
+    if (!a.w || !a.h) return;
+    const uint32_t units = a.mode == GK_YCC_420 ? a.ofy + (a.h - a.ofy + 1) / 2 : a.h;
+    a.rows = rows_per_group(units);
+    const dim3 grid((a.w + 256 * PIX - 1) / (256 * PIX), (units + a.rows - 1) / a.rows);
+    GK_DISPLAY_DST(stype, S, GK_DISPLAY_DST(dtype, D, launch_ycc<S, D>(st, a, grid)))
+}
+
+void gk_launch_cmyk_rgb(hipStream_t st, int stype, int dtype, const GkCmykArgs& args) {
+    GkCmykArgs a = args;
+    if (!a.w || !a.h) return;
+    a.rows = rows_per_group(a.h);
+    const dim3 grid((a.w + 256 * PIX - 1) / (256 * PIX), (a.h + a.rows - 1) / a.rows);
+    GK_DISPLAY_DST(stype, S, GK_DISPLAY_DST(dtype, D, hipLaunchKernelGGL((k_cmyk_rgb<S, D>), grid, dim3(256), 0, st, a)))
+}
+
+void gk_launch_upsample(hipStream_t st, int stype, int dtype, const GkUpArgs& args) {
+    GkUpArgs a = args;
+    if (!a.w || !a.h) return;
+    a.rows = rows_per_group(a.h);
+    const dim3 grid((a.w + 256 * PIX - 1) / (256 * PIX), (a.h + a.rows - 1) / a.rows);
+    GK_DISPLAY_DST(stype, S, GK_DISPLAY_DST(dtype, D, hipLaunchKernelGGL((k_upsample<S, D>), grid, dim3(256), 0, st, a)))
 }

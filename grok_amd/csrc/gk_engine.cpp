@@ -2791,6 +2791,132 @@ static ColourOut resolve_colour(const Jp2Colour& C, const Plan& W) {
     return O;
 }
 
+// What the display flags (gk_set_decode_display) make of the output channels: the CLI's
+// GrkDecompress::postProcess (grk_decompress.cpp:1335-1389, 1495) resolved from the header alone.
+struct DisplayOut {
+    enum Stage { NONE, YCC, CMYK, UPSAMPLE } stage = NONE;
+    uint32_t mode = 0;            // YCC: GkYccMode
+    bool converted = false, upsampled = false;
+    uint32_t colour_space = 0;    // of the output (GRK_COLOR_SPACE)
+    uint32_t ofx = 0, ofy = 0;    // oddFirstX / oddFirstY
+    struct Ch { uint32_t dx = 1, dy = 1, prec = 0, sgnd = 0, typ = 0, asoc = 0; };
+    std::vector<Ch> ch;           // output channels
+    bool active() const { return stage != NONE; }
+    uint32_t max_prec() const { uint32_t m = 0; for (const Ch& c : ch) m = std::max(m, c.prec); return m; }
+    uint32_t applied() const { return (converted ? 1u : 0u) | (upsampled ? 2u : 0u); }
+};
+// Plane size of a component sampled every (dx, dy) over the image area or the window (image
+// relative), reduced: every edge ceil(ceil(x / dx) / 2^red).
+static void comp_dims(const Plan& W, uint32_t dx, uint32_t dy, uint32_t red, const uint32_t* win, uint32_t& w, uint32_t& h) {
+    const uint64_t cx0 = (uint64_t)W.x0 + (win ? win[0] : 0), cy0 = (uint64_t)W.y0 + (win ? win[1] : 0);
+    const uint64_t cx1 = (uint64_t)W.x0 + (win ? win[2] : W.w), cy1 = (uint64_t)W.y0 + (win ? win[3] : W.h);
+    auto g = [&](uint64_t v, uint32_t d) { v = (v + d - 1) / d; return (uint32_t)((v + ((1ull << red) - 1)) >> red); };
+    w = g(cx1, dx) - g(cx0, dx);
+    h = g(cy1, dy) - g(cy0, dy);
+}
+static DisplayOut resolve_display(const Jp2Colour& C, const ColourOut& O, const Plan& W, uint32_t flags, uint32_t red,
+                                  const uint32_t* win) {
+    DisplayOut D;
+    const uint32_t n = (uint32_t)O.ch.size();
+    D.ch.resize(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        D.ch[k].dx = W.sx(O.ch[k].src); D.ch[k].dy = W.sy(O.ch[k].src);
+        D.ch[k].prec = O.ch[k].prec; D.ch[k].sgnd = O.ch[k].sgnd; D.ch[k].typ = O.ch[k].typ; D.ch[k].asoc = O.ch[k].asoc;
+    }
+    D.colour_space = C.colour_space(W.nc);
+    if (!flags) return D;
+    if (win && (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h)) throw GkError("bad decode window");
+    // (:1304-1315) the origin's parities, cleared by a window edge that is not the image's
+    D.ofx = (W.x0 & 1) && !(win && win[0] != 0);
+    D.ofy = (W.y0 & 1) && !(win && win[1] != 0);
+    auto sane = [&]() {   // all_components_sanity_check(image, true), common.cpp:333-375
+        if (D.ch[0].prec == 0 || D.ch[0].prec > 16) return false;
+        for (uint32_t k = 1; k < n; ++k)
+            if (D.ch[k].prec != D.ch[0].prec || D.ch[k].sgnd != D.ch[0].sgnd) return false;
+        return true;
+    };
+    auto one_grid = [&](const char* what) {   // (the reference walks every plane with component 0's size)
+        for (uint32_t k = 1; k < n; ++k)
+            if (D.ch[k].dx != D.ch[0].dx || D.ch[k].dy != D.ch[0].dy)
+                throw GkError(std::string("display: ") + what + " components of different sizes (subsampling) cannot be converted");
+    };
+    auto no_boxes = [&](const char* what) {
+        if (O.active())
+            throw GkError(std::string("display: ") + what + " conversion of a file with a palette or a channel definition is not supported");
+    };
+    if (flags & GK_DISPLAY_RGB) {
+        if (D.colour_space != 4 && n == 3 && D.ch[0].dx == D.ch[0].dy && D.ch[1].dx != 1) D.colour_space = 4;
+        else if (n <= 2) D.colour_space = 3;
+        if (D.colour_space == 4) {
+            if (n != 3) throw GkError("display: sYCC: number of components " + std::to_string(n) + " not equal to 3");
+            int mode = -1;
+            const auto& c = D.ch;
+            if (c[0].dx == 1 && c[0].dy == 1 && c[1].dx == c[2].dx && c[1].dy == c[2].dy) {
+                if (c[1].dx == 2 && c[1].dy == 2) mode = GK_YCC_420;
+                else if (c[1].dx == 2 && c[1].dy == 1) mode = GK_YCC_422;
+                else if (c[1].dx == 1 && c[1].dy == 1) mode = GK_YCC_444;
+            }
+            if (mode >= 0) {   // (any other pattern: Grok warns and leaves the planes as they are)
+                no_boxes("sYCC");
+                if (c[0].sgnd || c[1].sgnd || c[2].sgnd)
+                    throw GkError("display: sYCC conversion of a signed component is not supported (the reference assumes unsigned data)");
+                if (c[0].prec == 0 || c[0].prec > 30) throw GkError("display: sYCC conversion needs a precision of 1..30");
+                uint32_t w, h, cw, chh;
+                comp_dims(W, 1, 1, red, win, w, h);
+                comp_dims(W, c[1].dx, c[1].dy, red, win, cw, chh);
+                if (!w || !h) throw GkError("the window is empty at this reduction");
+                if (mode != GK_YCC_444) {
+                    // the subsampled modes index chroma by position: the planes must be what the loops walk
+                    const uint32_t need_w = (w - D.ofx + 1) / 2, need_h = mode == GK_YCC_420 ? (h - D.ofy + 1) / 2 : h;
+                    if (cw != need_w || chh != need_h)
+                        throw GkError("display: sYCC chroma planes of " + std::to_string(cw) + " x " + std::to_string(chh) +
+                                      " do not pair with the " + std::to_string(w) + " x " + std::to_string(h) + " luma plane (need " +
+                                      std::to_string(need_w) + " x " + std::to_string(need_h) +
+                                      "): this window or reduction is not supported (Grok reads out of bounds)");
+                    if (mode == GK_YCC_420 && D.ofx && D.ofy && (w & 1) && ((h - 1) & 1))
+                        throw GkError("display: sYCC 4:2:0 at an odd origin with an odd width and an even height is not supported "
+                                      "(Grok's last-row loop reads one chroma sample out of bounds)");
+                }
+                D.stage = DisplayOut::YCC; D.mode = (uint32_t)mode; D.converted = true; D.colour_space = 2;
+                for (uint32_t k = 1; k < 3; ++k) { D.ch[k].dx = c[0].dx; D.ch[k].dy = c[0].dy; }
+            }
+        } else if (D.colour_space == 5) {
+            if (n != 3) throw GkError("display: e-sYCC: number of components " + std::to_string(n) + " not equal to 3");
+            if (sane()) {
+                no_boxes("e-sYCC");
+                one_grid("e-sYCC");
+                D.stage = DisplayOut::YCC; D.mode = GK_YCC_ESYCC; D.converted = true; D.colour_space = 2;
+            }
+        } else if (D.colour_space == 6) {
+            if (n != 4) throw GkError("display: CMYK: number of components " + std::to_string(n) + " not equal to 4");
+            if (sane()) {
+                no_boxes("CMYK");
+                one_grid("CMYK");
+                if (D.ch[0].sgnd)
+                    throw GkError("display: CMYK conversion of signed components is not supported (the reference assumes unsigned data)");
+                D.stage = DisplayOut::CMYK; D.converted = true; D.colour_space = 2;
+                D.ch.pop_back();
+                for (auto& h : D.ch) h.prec = 8;
+            }
+        }
+    }
+    if (flags & GK_DISPLAY_UPSAMPLE) {
+        if (red) throw GkError("display: upsampling together with a reduced resolution (gk_set_decode_reduce) is not supported");
+        for (auto& h : D.ch) {
+            if (h.dx == 1 && h.dy == 1) continue;
+            if (D.converted)   // (e-sYCC / CMYK whose components are all subsampled alike: two passes)
+                throw GkError("display: upsampling an image that was converted on a subsampled grid is not supported");
+            uint32_t cw, chh;
+            comp_dims(W, h.dx, h.dy, 0, win, cw, chh);
+            if (!cw || !chh) throw GkError("display: a component without samples in this area cannot be upsampled");
+            h.dx = h.dy = 1;
+            D.upsampled = true;
+        }
+        if (D.upsampled && D.stage == DisplayOut::NONE) D.stage = DisplayOut::UPSAMPLE;
+    }
+    return D;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2831,6 +2957,11 @@ struct gk_ctx {
     // the call in progress is the component decode under decode_colour, col_whole: which needs
     // every tile (its palette stage expands the whole image)
     bool dec_colour = true, col_inner = false, col_whole = false;
+    // gk_set_decode_display flags; disp_inner: the call in progress is the component decode under
+    // decode_display (which needs every tile as well)
+    uint32_t dec_display = 0;
+    bool disp_inner = false;
+    DisplayOut hdr_disp;       // what the flags make of the last gk_decode_header's channels
     Jp2Colour hdr_col;         // the last gk_decode_header's colour boxes and output channels
     ColourOut hdr_out;
     uint32_t hdr_ncs = 0;      // its codestream component count
@@ -4616,6 +4747,122 @@ static void decode_colour(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
                                     hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
 }
+// Decode under display flags that apply (gk_set_decode_display; DisplayOut::active): the
+// components are decoded into engine-owned planes of the narrowest sample type, each on its own
+// grid, and one pass of k_ycc_rgb / k_cmyk_rgb / k_upsample (gk_colour.hip) writes the caller's
+// device planes, or a staging that is copied to the host, on the same stream.
+static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
+                           const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
+                           const DisplayOut& D, const Plan& W) {
+    struct Inner {
+        gk_ctx* c;
+        Inner(gk_ctx* c_) : c(c_) { c->col_inner = true; c->col_whole = true; c->disp_inner = true; }
+        ~Inner() { c->col_inner = false; c->col_whole = false; c->disp_inner = false; }
+    };
+    hipStream_t st = ctx->st;
+    const uint32_t red = ctx->dec_reduce, nc = W.nc, nout = (uint32_t)D.ch.size();
+    // output sample type: int32, or the 8 / 16-bit type of the widest output channel
+    bool any_signed = false, all_signed = true;
+    for (uint32_t c = 0; c < nc; ++c) { any_signed = any_signed || W.c_sgnd(c); all_signed = all_signed && W.c_sgnd(c); }
+    const uint32_t oprec = D.max_prec();
+    if (sample_bytes == 1 || sample_bytes == 2) {
+        if (sample_bytes != (oprec + 7) / 8)
+            throw GkError("display: " + std::to_string(sample_bytes) + "-byte output planes for an output precision of " +
+                          std::to_string(oprec) + " bits: use (precision + 7) / 8-byte or int32 planes");
+        if (any_signed && D.converted) throw GkError("display: 8 / 16-bit output of a conversion from signed components: use int32 planes");
+        if (any_signed && !all_signed) throw GkError("8 / 16-bit output needs one sign: use int32 planes");
+    } else if (sample_bytes != 0 && sample_bytes != 4) {
+        throw GkError("sample_bytes must be 4 or (prec + 7) / 8");
+    }
+    // (signed 8 / 16-bit planes take the same bits as unsigned ones: the stage only copies them)
+    const int dtype = sample_bytes == 1 ? GK_U8 : sample_bytes == 2 ? GK_U16 : GK_S32;
+    const uint32_t sb_in = (!any_signed && W.prec <= 16) ? (W.prec + 7) / 8 : 4;
+    const int stype = sb_in == 1 ? GK_U8 : sb_in == 2 ? GK_U16 : GK_S32;
+    const size_t es_in = gk_sample_size(stype), es_out = gk_sample_size(dtype);
+    // component planes, each on its own grid; rows aligned for the kernels' vector loads
+    std::vector<uint32_t> cw(nc), chh(nc), cstr(nc);
+    std::vector<size_t> coff(nc);
+    size_t total = 0;
+    for (uint32_t c = 0; c < nc; ++c) {
+        comp_dims(W, W.sx(c), W.sy(c), red, win, cw[c], chh[c]);
+        if (!cw[c] || !chh[c]) throw GkError("display: a component without samples in this area");
+        cstr[c] = (cw[c] + 15) & ~15u;
+        coff[c] = total;
+        total += (((size_t)cstr[c] * chh[c] * es_in) + 255) & ~(size_t)255;
+    }
+    uint8_t* src = (uint8_t*)ctx->dcol_src.get(total);
+    {
+        std::vector<void*> cp(nc);
+        for (uint32_t c = 0; c < nc; ++c) cp[c] = src + coff[c];
+        Inner in(ctx);
+        decode_impl(ctx, cs, len, cs_on_device, cp.data(), cstr.data(), sb_in == 4 ? 0 : sb_in, 1, win, nullptr);
+    }
+    // output planes: the image grid after an upsampling, component 0's otherwise
+    uint32_t ow = cw[0], oh = chh[0];
+    if (D.stage == DisplayOut::UPSAMPLE) comp_dims(W, 1, 1, 0, win, ow, oh);
+    const uint32_t pstride = (ow + 15) & ~15u;
+    std::vector<uint8_t*> dst(nout);
+    std::vector<uint32_t> dstr(nout);
+    const size_t plane_out = (((size_t)pstride * oh * es_out) + 255) & ~(size_t)255;
+    if (out_on_device) {
+        for (uint32_t k = 0; k < nout; ++k) { dst[k] = (uint8_t*)comps[k]; dstr[k] = strides[k]; }
+    } else {
+        uint8_t* stage = (uint8_t*)ctx->dcol_out.get(plane_out * nout);
+        for (uint32_t k = 0; k < nout; ++k) { dst[k] = stage + plane_out * k; dstr[k] = pstride; }
+    }
+    uint32_t vec = 1;
+    for (uint32_t k = 0; k < nout; ++k)
+        if (((uintptr_t)dst[k] % (GK_PAL_PIX * es_out)) || (dstr[k] % GK_PAL_PIX)) vec = 0;
+    HIPCHK(hipEventRecord(ctx->ev[20], st));
+    if (D.stage == DisplayOut::YCC) {
+        GkYccArgs a{};
+        a.y = src + coff[0]; a.cb = src + coff[1]; a.cr = src + coff[2];
+        a.ys = cstr[0]; a.cs = cstr[1];
+        for (int k = 0; k < 3; ++k) { a.dst[k] = dst[k]; a.ds[k] = dstr[k]; }
+        a.w = ow; a.h = oh; a.mode = D.mode; a.ofx = D.ofx; a.ofy = D.ofy;
+        const uint32_t p0 = W.c_prec(0);
+        a.offset = 1 << (p0 - 1); a.upb = (int32_t)((1u << p0) - 1);
+        a.flip_cb = !W.c_sgnd(1); a.flip_cr = !W.c_sgnd(2);
+        a.vec_store = vec;
+        gk_launch_ycc_rgb(st, stype, dtype, a);
+    } else if (D.stage == DisplayOut::CMYK) {
+        GkCmykArgs a{};
+        for (int k = 0; k < 4; ++k) {
+            a.src[k] = src + coff[k];
+            a.scale[k] = 1.0F / (float)((1 << W.c_prec(k)) - 1);
+        }
+        a.ss = cstr[0];
+        for (int k = 0; k < 3; ++k) { a.dst[k] = dst[k]; a.ds[k] = dstr[k]; }
+        a.w = ow; a.h = oh; a.vec_store = vec;
+        gk_launch_cmyk_rgb(st, stype, dtype, a);
+    } else {
+        const uint64_t cx0 = (uint64_t)W.x0 + (win ? win[0] : 0), cy0 = (uint64_t)W.y0 + (win ? win[1] : 0);
+        for (uint32_t k = 0; k < nout; ++k) {   // (a component at 1 x 1 is copied)
+            const uint32_t dx = W.sx(k), dy = W.sy(k);
+            GkUpArgs a{};
+            a.src = src + coff[k]; a.ss = cstr[k];
+            a.dst = dst[k]; a.ds = dstr[k];
+            a.w = ow; a.h = oh; a.dx = dx; a.dy = dy;
+            a.xoff = (uint32_t)(((cx0 + dx - 1) / dx) * dx - cx0);
+            a.yoff = (uint32_t)(((cy0 + dy - 1) / dy) * dy - cy0);
+            a.vec_store = vec;
+            // the last sample read must lie in the component's plane
+            if (a.xoff >= dx || a.yoff >= dy || (ow > a.xoff && (ow - 1 - a.xoff) / dx >= cw[k]) ||
+                (oh > a.yoff && (oh - 1 - a.yoff) / dy >= chh[k]))
+                throw GkError("internal: upsampling geometry");
+            gk_launch_upsample(st, stype, dtype, a);
+        }
+    }
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[21], st));
+    if (!out_on_device)
+        for (uint32_t k = 0; k < nout; ++k)
+            HIPCHK(hipMemcpy2DAsync(comps[k], (size_t)strides[k] * es_out, dst[k], (size_t)pstride * es_out, (size_t)ow * es_out, oh,
+                                    hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const float ms = ev_ms(ctx, 20, 21);   // the display pass counts as sample stage
+    ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+}
 static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
                         const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win = nullptr,
                         const TilePass* pass = nullptr) {
@@ -4640,7 +4887,7 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     Jp2Colour col;
     {
         size_t joff = 0, jlen = 0;
-        const bool colour = ctx->dec_colour && !ctx->col_inner && !pass;
+        const bool colour = (ctx->dec_colour || ctx->dec_display) && !ctx->col_inner && !pass;
         if (jp2_locate(S, joff, jlen, colour ? &col : nullptr)) {   // JP2 file: decode its codestream box
             cs += joff; len = jlen;
             S = ByteSrc(); S.len = len; S.st = st;
@@ -4649,7 +4896,16 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     }
     Header Hd;
     parse_header(S, Hd);
-    if (col.jp2 && (col.has_pclr || col.has_cdef)) {   // colour boxes that change the channels
+    if (ctx->dec_display && !ctx->col_inner && !pass) {   // display flags: a conversion or an upsampling that applies
+        const Jp2Colour none;
+        const ColourOut co = resolve_colour(ctx->dec_colour ? col : none, Hd.want);
+        const DisplayOut D = resolve_display(col, co, Hd.want, ctx->dec_display, ctx->dec_reduce, win);
+        if (D.active()) {
+            decode_display(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, D, Hd.want);
+            return;
+        }
+    }
+    if (ctx->dec_colour && col.jp2 && (col.has_pclr || col.has_cdef)) {   // colour boxes that change the channels
         const ColourOut co = resolve_colour(col, Hd.want);
         if (co.active()) {
             decode_colour(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, col, co, Hd.want);
@@ -4705,7 +4961,9 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     }
     merge_tile_parts(Hd);
     if (ctx->col_whole && !win && !pass && Hd.parts.size() != P.tiles.size())
-        throw GkError("a palette (pclr / cmap boxes) on a stream that holds only some of its tiles is not supported");
+        throw GkError(ctx->disp_inner ? "display flags (gk_set_decode_display) on a stream that holds only some of its tiles "
+                                        "(sharded / tile-range decode) are not supported"
+                                      : "a palette (pclr / cmap boxes) on a stream that holds only some of its tiles is not supported");
     if (pass) {
         std::vector<TilePart> keep;
         for (auto& TP : Hd.parts)
@@ -5828,16 +6086,33 @@ static bool read_header_colour(ByteSrc& S, const uint8_t* cs, bool on_device, bo
     out = resolve_colour(apply ? col : none, Hd.want);
     return jp2;
 }
-static void fill_image_info(gk_image_info* info, const Header& Hd, const ColourOut& out) {
+static void fill_image_info(gk_image_info* info, const Header& Hd, const ColourOut& out, const DisplayOut* disp = nullptr) {
     info->w = Hd.want.w; info->h = Hd.want.h; info->numcomps = Hd.want.nc; info->prec = Hd.want.prec;
     info->sgnd = Hd.want.sgnd; info->x0 = Hd.want.x0; info->y0 = Hd.want.y0;
     if (out.active()) {   // the output channels: their count, the widest precision, channel 0's sign
         info->numcomps = (uint32_t)out.ch.size(); info->prec = out.max_prec(); info->sgnd = out.ch[0].sgnd;
     }
+    if (disp && disp->applied()) {   // ... after the display stage
+        info->numcomps = (uint32_t)disp->ch.size(); info->prec = disp->max_prec(); info->sgnd = disp->ch[0].sgnd;
+    }
 }
-static void fill_colour_info(gk_colour_info* ci, const Jp2Colour& col, const ColourOut& out, uint32_t ncs) {
+static void fill_colour_info(gk_colour_info* ci, const Jp2Colour& col, const ColourOut& out, uint32_t ncs,
+                             const DisplayOut* disp = nullptr) {
     memset(ci, 0, sizeof(*ci));
     ci->colour_space = col.colour_space(ncs);
+    if (disp) {   // display flags: the colour space, the channels and what was applied describe the output
+        ci->colour_space = disp->colour_space;
+        ci->display_applied = disp->applied();
+        ci->enumcs = col.enumcs; ci->meth = col.meth; ci->icc_len = (uint32_t)col.icc.size();
+        ci->has_palette = out.palette ? 1 : 0;
+        ci->palette_entries = col.ne; ci->palette_columns = col.npc;
+        ci->has_cdef = out.cdef ? 1 : 0;
+        ci->num_comps = ncs; ci->num_channels = (uint32_t)disp->ch.size();
+        for (size_t k = 0; k < disp->ch.size() && k < GK_MAX_CHANNELS; ++k) {
+            ci->typ[k] = (uint16_t)disp->ch[k].typ; ci->asoc[k] = (uint16_t)disp->ch[k].asoc;
+        }
+        return;
+    }
     ci->enumcs = col.enumcs; ci->meth = col.meth; ci->icc_len = (uint32_t)col.icc.size();
     ci->has_palette = out.palette ? 1 : 0;
     ci->palette_entries = col.ne; ci->palette_columns = col.npc;
@@ -5858,15 +6133,18 @@ int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
         Jp2Colour col;
         ColourOut out;
         read_header_colour(S, cs, cs_on_device != 0, ctx->dec_colour, Hd, col, out);
-        fill_image_info(info, Hd, out);
-        const uint32_t n = (uint32_t)out.ch.size();
+        // (display flags: the whole image's output; a refusal that depends on a window is the decode's)
+        DisplayOut disp = resolve_display(col, out, Hd.want, ctx->dec_display, ctx->dec_reduce, nullptr);
+        fill_image_info(info, Hd, out, &disp);
+        const uint32_t n = (uint32_t)disp.ch.size();
         ctx->hdr_dx.assign(n, 1); ctx->hdr_dy.assign(n, 1);
         ctx->hdr_prec.assign(n, 0); ctx->hdr_sgnd.assign(n, 0);
         for (uint32_t k = 0; k < n; ++k) {
-            ctx->hdr_dx[k] = Hd.want.sx(out.ch[k].src); ctx->hdr_dy[k] = Hd.want.sy(out.ch[k].src);
-            ctx->hdr_prec[k] = out.ch[k].prec; ctx->hdr_sgnd[k] = out.ch[k].sgnd;
+            ctx->hdr_dx[k] = disp.ch[k].dx; ctx->hdr_dy[k] = disp.ch[k].dy;
+            ctx->hdr_prec[k] = disp.ch[k].prec; ctx->hdr_sgnd[k] = disp.ch[k].sgnd;
         }
         ctx->hdr_col = std::move(col); ctx->hdr_out = std::move(out); ctx->hdr_ncs = Hd.want.nc;
+        ctx->hdr_disp = std::move(disp);
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;
@@ -5877,7 +6155,7 @@ int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
 int gk_header_colour(gk_ctx* ctx, gk_colour_info* ci) {
     if (!ctx || !ci) return -1;
     if (!ctx->hdr_ncs) { ctx->err = "gk_header_colour: no header has been read"; return -1; }
-    fill_colour_info(ci, ctx->hdr_col, ctx->hdr_out, ctx->hdr_ncs);
+    fill_colour_info(ci, ctx->hdr_col, ctx->hdr_out, ctx->hdr_ncs, ctx->dec_display ? &ctx->hdr_disp : nullptr);
     return 0;
 }
 
@@ -5894,6 +6172,43 @@ int gk_set_decode_colour(gk_ctx* ctx, int apply) {
     if (!ctx) return -1;
     ctx->dec_colour = apply != 0;
     return 0;
+}
+
+int gk_set_decode_display(gk_ctx* ctx, uint32_t flags) {
+    if (!ctx) return -1;
+    if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE)) { ctx->err = "gk_set_decode_display: unknown flags"; return -1; }
+    ctx->dec_display = flags;
+    return 0;
+}
+
+int gk_probe_display(const uint8_t* cs, size_t len, uint32_t flags, uint32_t reduce, gk_image_info* info,
+                     gk_colour_info* colour, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd, uint32_t cap,
+                     char* msg, size_t msg_cap) {
+    if (!cs) return -1;
+    try {
+        if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE)) throw GkError("gk_probe_display: unknown flags");
+        if (reduce >= GK_MAXRLVLS) throw GkError("reduce must be less than the number of resolutions");
+        ByteSrc S; S.len = len; S.host = cs;
+        Header Hd;
+        Jp2Colour col;
+        ColourOut out;
+        read_header_colour(S, cs, false, true, Hd, col, out);
+        for (uint32_t c = 0; c < Hd.want.nc; ++c)
+            if (reduce >= Hd.want.p.c_numres(c)) throw GkError("reduce must be less than the number of resolutions");
+        const DisplayOut disp = resolve_display(col, out, Hd.want, flags, reduce, nullptr);
+        if (info) { fill_image_info(info, Hd, out, &disp); info->sample_bytes = 0; }
+        if (colour) fill_colour_info(colour, col, out, Hd.want.nc, flags ? &disp : nullptr);
+        for (uint32_t c = 0; c < disp.ch.size() && c < cap; ++c) {
+            if (dx) dx[c] = disp.ch[c].dx;
+            if (dy) dy[c] = disp.ch[c].dy;
+            if (prec) prec[c] = disp.ch[c].prec;
+            if (sgnd) sgnd[c] = disp.ch[c].sgnd;
+        }
+        return (int)disp.ch.size();
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
+        return -1;
+    }
 }
 
 int gk_probe_colour(const uint8_t* cs, size_t len, gk_colour_info* ci, char* msg, size_t msg_cap) {

@@ -127,3 +127,43 @@ uint32_t gk_pal_entry_words(uint32_t npc, uint32_t elem_bytes);
 // aligned to GK_PAL_PIX samples.  Returns the table path taken: 0 LDS (one dword per entry),
 // 1 LDS, 2 global gather; < 0: nothing to do.
 int gk_launch_jp2_palette(hipStream_t st, int stype, int dtype, const GkPalArgs& args);
+// Display stage (gk_colour.hip): what Grok's CLI does after the decode (GrkDecompress::postProcess):
+// sYCC / e-sYCC / CMYK to RGB and sample replication of subsampled components.  Source planes are
+// the engine's own (bases and row strides aligned to GK_PAL_PIX samples); stype / dtype: GK_U8,
+// GK_U16 or GK_S32 planes in / out.
+enum GkYccMode { GK_YCC_444 = 0, GK_YCC_422 = 1, GK_YCC_420 = 2, GK_YCC_ESYCC = 3 };
+struct GkYccArgs {
+    const void* y; const void* cb; const void* cr;   // luma w x h; chroma on its own grid (mode)
+    uint32_t ys, cs;           // row strides of luma / chroma in samples
+    void* dst[3];              // R, G, B: w x h each
+    uint32_t ds[3];            // their row strides in samples
+    uint32_t w, h;
+    uint32_t mode;             // GkYccMode
+    uint32_t ofx, ofy;         // 4:2:2 / 4:2:0: the first column / row stands alone (odd image origin)
+    int32_t offset, upb;       // 1 << (prec - 1), (1 << prec) - 1
+    uint32_t flip_cb, flip_cr; // e-sYCC: the component is unsigned (loses `offset`)
+    uint32_t vec_store;        // every dst and its row stride are aligned to GK_PAL_PIX samples
+    uint32_t rows;             // (set by the launcher)
+};
+void gk_launch_ycc_rgb(hipStream_t st, int stype, int dtype, const GkYccArgs& args);
+struct GkCmykArgs {
+    const void* src[4];        // C, M, Y, K: w x h, row stride ss samples
+    uint32_t ss;
+    void* dst[3];
+    uint32_t ds[3];
+    uint32_t w, h;
+    float scale[4];            // 1.0F / (float)((1 << prec) - 1) per source channel
+    uint32_t vec_store;
+    uint32_t rows;
+};
+void gk_launch_cmyk_rgb(hipStream_t st, int stype, int dtype, const GkCmykArgs& args);
+// dst[y][x] = 0 when x < xoff or y < yoff, else src[(y - yoff) / dy][(x - xoff) / dx]
+struct GkUpArgs {
+    const void* src; uint32_t ss;
+    void* dst; uint32_t ds;
+    uint32_t w, h;             // of dst
+    uint32_t dx, dy, xoff, yoff;
+    uint32_t vec_store;
+    uint32_t rows;
+};
+void gk_launch_upsample(hipStream_t st, int stype, int dtype, const GkUpArgs& args);

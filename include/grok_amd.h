@@ -234,6 +234,8 @@ typedef struct gk_colour_info {
     uint16_t typ[GK_MAX_CHANNELS];    /* per output channel: cdef Typ (0 colour, 1 opacity, 2 premultiplied opacity, */
     uint16_t asoc[GK_MAX_CHANNELS];   /* 65535 unspecified) and Asoc (0 whole image, 1..3 colour, 65535 none);
                                          without a cdef Grok's defaults: colour 1..3, then unspecified */
+    uint32_t display_applied;  /* gk_set_decode_display: GK_DISPLAY_RGB set when a conversion to RGB runs,
+                                  GK_DISPLAY_UPSAMPLE when components are upsampled (0 without flags) */
 } gk_colour_info;
 /* Colour description of host codestream / JP2 bytes, no device needed (like gk_probe_header);
  * < 0 with the reason, naming the box, in msg. */
@@ -253,6 +255,40 @@ int gk_header_icc(gk_ctx* ctx, uint8_t* buf, size_t cap, size_t* len);
  * palette and channel definition.  apply = 0: they return the codestream's components untouched
  * (the colour description is still read). */
 int gk_set_decode_colour(gk_ctx* ctx, int apply);
+
+/* What Grok's CLI does to the decoded image before it writes it (GrkDecompress::postProcess,
+ * bin/jp2/grk_decompress.cpp:1300-1506), done on the device by later gk_decode / gk_decode_window
+ * calls.  flags = 0 (default): the components as decoded.
+ * GK_DISPLAY_RGB: sYCC (4:4:4, 4:2:2, 4:2:0), e-sYCC and CMYK images are converted to RGB
+ * (color_sycc_to_rgb, color_esycc_to_rgb, color_cmyk_to_rgb, bin/common/color.cpp) by
+ * postProcess's rule: a 3-component image whose component 0 has dx == dy and component 1 dx != 1
+ * is taken as sYCC whatever its colr box says, otherwise one of <= 2 components as grey; an sYCC
+ * image with another subsampling pattern, or an e-sYCC / CMYK image that fails
+ * all_components_sanity_check (precision 1..16, one precision, one sign), stays unconverted.
+ * GK_DISPLAY_UPSAMPLE: components with dx > 1 or dy > 1 are then replicated to the image grid
+ * (upsample_image_components, bin/common/convert.cpp:209-360; grk_decompress -u), the window's with
+ * a window; refused together with gk_set_decode_reduce > 0.
+ * While flags are set the header calls (gk_decode_header, gk_header_components, gk_header_colour
+ * and gk_probe_display) describe the OUTPUT: channel count, each channel's dx / dy / precision /
+ * sign, the colour space (sRGB after a conversion that ran) and gk_colour_info::display_applied.
+ * Refused, each by name: a channel count other than 3 (sYCC, e-sYCC) or 4 (CMYK); signed
+ * components into the sYCC or CMYK conversion; a window or reduction that leaves the chroma planes
+ * of 4:2:2 / 4:2:0 other than ceil((w - ox) / 2) [x ceil((h - oy) / 2)] for a w x h luma plane
+ * (ox, oy: the origin's parities, cleared by a window edge that is not the image's); e-sYCC / CMYK
+ * components of different sizes; a palette or channel definition on a file that would be
+ * converted; a stream that holds only some of its tiles; 8 / 16-bit planes that are not
+ * (output precision + 7) / 8 bytes. */
+#define GK_DISPLAY_RGB 1u
+#define GK_DISPLAY_UPSAMPLE 2u
+int gk_set_decode_display(gk_ctx* ctx, uint32_t flags);
+/* What a decode of host codestream / JP2 bytes under `flags` and `reduce` returns, no device
+ * needed: the image info and colour description of the output (either may be NULL), dx / dy /
+ * prec / sgnd of the first cap channels (any may be NULL); returns the channel count, or < 0 with
+ * the refusal in msg.  flags = 0, reduce = 0: what gk_probe_header / gk_probe_colour /
+ * gk_probe_components report. */
+int gk_probe_display(const uint8_t* cs, size_t len, uint32_t flags, uint32_t reduce, gk_image_info* info,
+                     gk_colour_info* colour, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd, uint32_t cap,
+                     char* msg, size_t msg_cap);
 
 /* Inverse 5/3 rule of later gk_decode_window calls.  whole_tile = 0 (default): Grok's partial-tile
  * inverse, which a window set through setDecompressWindow selects for every tile
