@@ -5418,8 +5418,11 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
         dcs = d;
     }
     // gather every selected block's segments into a 16-byte aligned slot followed by >= 32
-    // bytes of 0xFF (the T1 decoders read their bytes through aligned windows; the Part-1
-    // decoder takes the padding as the MQ end-of-data bytes)
+    // bytes of padding (the T1 decoders read their bytes through aligned windows).  The plain
+    // Part-1 decoder tests no length per byte and takes the padding as the MQ end-of-data bytes,
+    // so the staging buffer is filled with 0xFF whenever any component of the pass is not HT (a
+    // COC or a tile's coding may put Part-1 blocks under an HT COD); the HT and mode-switch
+    // decoders bound their own reads, and an all-HT pass skips the fill
     // (pos, slot position, length) triples, straight into the pinned upload buffer; a part's
     // chunks are those of its own blocks, so parts fill disjoint ranges
     // (a chunk lands at its block's slot + the block's bytes before it, recorded by the parse, so
@@ -5454,14 +5457,16 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
         nseg = sb.back();
     }
     uint8_t* stg = (uint8_t*)ctx->bytes.get(o + 256);   // decoder window loads read up to 48 B past a block
+    bool pad_ff = false;
+    for (uint32_t c = 0; c < P.nc; ++c) pad_ff = pad_ff || !P.p.c_ht(c);
     if (host_gather) {
         HIPCHK(hipStreamSynchronize(st));   // the pinned staging buffer may still feed an earlier copy
         uint8_t* hst = (uint8_t*)ctx->hstage2.get(o + 256);
-        if (!P.p.ht()) memset(hst, 0xff, o);
+        if (pad_ff) memset(hst, 0xff, o);
         for (size_t k = 0; k < nseg; k += 3) memcpy(hst + seg[k + 1], cs + seg[k], seg[k + 2]);
         HIPCHK(hipMemcpyAsync(stg, hst, o, hipMemcpyHostToDevice, st));
     } else {
-    if (!P.p.ht()) HIPCHK(hipMemsetAsync(stg, 0xff, o, st));
+    if (pad_ff) HIPCHK(hipMemsetAsync(stg, 0xff, o, st));
     if (nseg) {
         uint64_t* ds = (uint64_t*)ctx->dseg.get(nseg * 8 + 8);
         HIPCHK(hipMemcpyAsync(ds, seg, nseg * 8, hipMemcpyHostToDevice, st));

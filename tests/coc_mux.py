@@ -6,8 +6,8 @@ every component), and Pillow exposes no such option, so test streams are assembl
 is encoded alone by the oracle (LRCP, one tile, PLT giving every packet's length), and the packets
 are interleaved in the multi-component LRCP order (layer, resolution, component, precinct;
 A.6.1 / B.12.1.1), a component without resolution r contributing none there.  The main header
-takes component 0's COD (MCT off) and QCD, and a COC / QCC for every other component whose coding /
-quantisation differs (A.6.2, A.6.5).  Each component's packets are unchanged, so a decoder must
+takes component 0's COD (MCT off), its CAP when it is HT, and its QCD, and a COC / QCC for every
+other component whose coding / quantisation differs (A.6.2, A.6.5).  Each component's packets are unchanged, so a decoder must
 reproduce each single-component decode; OpenJPEG 2.5.4 does (tests/test_coc.py)."""
 import os
 import struct
@@ -100,6 +100,9 @@ def mux(planes, prec, comp_kw, nlayers=1):
     cod0[4] = 0   # no MCT
     o = bytearray(b"\xff\x4f")
     o += struct.pack(">HH", 0xFF51, 2 + len(siz)) + siz
+    if 0xFF50 in parts[0][0]:   # an HT component 0 (the COD is HT): its CAP follows SIZ (A.5.2)
+        cap = parts[0][0][0xFF50]
+        o += struct.pack(">HH", 0xFF50, 2 + len(cap)) + cap
     o += struct.pack(">HH", 0xFF52, 2 + len(cod0)) + cod0
     qcd0 = parts[0][0][0xFF5C]
     o += struct.pack(">HH", 0xFF5C, 2 + len(qcd0)) + qcd0

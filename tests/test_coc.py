@@ -23,6 +23,9 @@ CASES = {
     "levels_cblk_97_prc": (70, 90, 8, [dict(numres=4), dict(numres=2, cblk=(16, 16)),
                                        dict(numres=3, irreversible=True, precincts=[(32, 32), (16, 16)])], 1),
     "ht_and_part1": (64, 80, 8, [dict(numres=3), dict(numres=3, cblk_sty=0x40), dict(numres=4, cblk=(32, 32))], 1),
+    # the other direction: an HT COD (component 0) over plain Part-1, 32 x 32 and mode-switch components
+    "part1_under_ht": (64, 80, 8, [dict(numres=3, cblk_sty=0x40), dict(numres=3), dict(numres=4, cblk=(32, 32)),
+                                   dict(numres=3, cblk_sty=0x05)], 1),
     "mode_switches": (60, 72, 8, [dict(numres=3), dict(numres=3, cblk_sty=0x05), dict(numres=2, cblk_sty=0x20)], 1),
     "wide_block": (72, 150, 8, [dict(numres=3), dict(numres=3, cblk=(128, 32))], 1),
     "layers_rate": (96, 96, 8, [dict(numres=4, layer_rate=[20, 5]), dict(numres=3, layer_rate=[30, 8]),

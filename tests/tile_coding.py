@@ -108,6 +108,9 @@ CASES = {
     "prog_layers_sop": (80, 96, dict(numres=3), dict(numres=4, nlayers=3, prog_order="RPCL", sop=True, eph=True),
                         {2}, "cod"),
     "ht_tile": (80, 96, dict(numres=4), dict(numres=4, cblk_sty=0x40), {0, 1}, "cod"),
+    # the other direction: an HT main COD over Part-1 tiles (tile COD) and Part-1 components (tile COCs)
+    "part1_tile_under_ht": (80, 96, dict(numres=4, cblk_sty=0x40), dict(numres=4), {0, 3}, "cod"),
+    "part1_coc_under_ht": (80, 96, dict(numres=3, cblk_sty=0x40), dict(numres=3, cblk=(32, 32)), {1, 2}, "coc"),
     "modes_tile": (80, 96, dict(numres=3, cblk=(32, 32)), dict(numres=3, cblk_sty=0x05), {3}, "cod"),
     "scope_irrev": (80, 96, dict(numres=3), dict(numres=3, irreversible=True), {1, 2}, "scope"),
     "ragged_tiles": (70, 101, dict(numres=3), dict(numres=2, cblk=(16, 16)), {2, 5}, "cod"),
