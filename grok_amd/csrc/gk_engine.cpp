@@ -470,42 +470,127 @@ static void ht_irrev_quant(uint32_t prec, bool sgnd, uint32_t nd, uint32_t r, ui
     expn = e;
 }
 
+// The native QCD of band B (its orient set) at resolution r of nres, component ci: exponent,
+// mantissa, steps and bit-planes.
+static void band_quant(const Plan& P, uint32_t ci, uint32_t nres, uint32_t r, BandG& B) {
+    const uint32_t irrev = P.p.c_irrev(ci);
+    const bool ht = P.p.c_ht(ci);
+    uint32_t level = nres - 1 - r;
+    if (ht && !irrev) {
+        B.mant = 0;
+        B.expn = ht_rev_expn(P.prec, nres - 1, r, B.orient);
+        B.step_enc = B.step_dec = 1.0f;
+        B.numbps = (uint32_t)std::max(0, (int)B.expn + (int)P.p.numgbits - 1) + P.p.roi(ci);
+        return;
+    }
+    uint32_t gain = irrev ? 0 : (B.orient == 0 ? 0 : (B.orient == 3 ? 2 : 1));
+    if (ht) {
+        ht_irrev_quant(P.prec, P.sgnd != 0, nres - 1, r, B.orient, B.expn, B.mant);
+    } else {
+        // Part-1 QCD generation (HTParams.cpp:216-251)
+        double stepsize = 1.0;
+        if (irrev) stepsize = (double)(1u << gain) / band_norm(level, B.orient, false);
+        uint32_t step = (uint32_t)floor(stepsize * 8192.0);
+        int pp = floorlog2(step) - 13, n = 11 - floorlog2(step);
+        B.mant = (n < 0 ? step >> -n : step << n) & 0x7ff;
+        B.expn = (uint32_t)((int)(P.prec + gain) - pp);
+    }
+    // Quantizer::setBandStepSizeAndBps (Quantizer.cpp:26-66)
+    uint32_t lg_enc = B.orient == 0 ? 0 : (B.orient == 3 ? 2 : 1);
+    uint32_t lg_dec = irrev ? 0 : lg_enc;
+    B.step_enc = (float)((1.0 + B.mant / 2048.0) * pow(2.0, (int)(P.prec + lg_enc) - (int)B.expn));
+    B.step_dec = (float)((1.0 + B.mant / 2048.0) * pow(2.0, (int)(P.prec + lg_dec) - (int)B.expn));
+    int v = (int)B.expn + (int)P.p.numgbits - 1;
+    B.numbps = P.p.roi(ci) + (uint32_t)std::max(0, v);   // Quantizer.cpp:47: roishift + ...
+}
+
 static void assign_steps_tile(Plan& P, TileG& T) {
     for (uint32_t ci = 0; ci < (uint32_t)T.comps.size(); ++ci) {
         CompG& C = T.comps[ci];
-        const uint32_t nres = P.p.c_numres(ci), irrev = P.p.c_irrev(ci);
-        const bool ht = P.p.c_ht(ci);
-        for (uint32_t r = 0; r < nres; ++r) {
-            for (auto& B : C.res[r].bands) {
-                uint32_t level = nres - 1 - r;
-                if (ht && !irrev) {
-                    B.mant = 0;
-                    B.expn = ht_rev_expn(P.prec, nres - 1, r, B.orient);
-                    B.step_enc = B.step_dec = 1.0f;
-                    B.numbps = (uint32_t)std::max(0, (int)B.expn + (int)P.p.numgbits - 1) + P.p.roi(ci);
-                    continue;
-                }
-                uint32_t gain = irrev ? 0 : (B.orient == 0 ? 0 : (B.orient == 3 ? 2 : 1));
-                if (ht) {
-                    ht_irrev_quant(P.prec, P.sgnd != 0, nres - 1, r, B.orient, B.expn, B.mant);
-                } else {
-                // Part-1 QCD generation (HTParams.cpp:216-251)
-                double stepsize = 1.0;
-                if (irrev) stepsize = (double)(1u << gain) / band_norm(level, B.orient, false);
-                uint32_t step = (uint32_t)floor(stepsize * 8192.0);
-                int pp = floorlog2(step) - 13, n = 11 - floorlog2(step);
-                B.mant = (n < 0 ? step >> -n : step << n) & 0x7ff;
-                B.expn = (uint32_t)((int)(P.prec + gain) - pp);
-                }
-                // Quantizer::setBandStepSizeAndBps (Quantizer.cpp:26-66)
-                uint32_t lg_enc = B.orient == 0 ? 0 : (B.orient == 3 ? 2 : 1);
-                uint32_t lg_dec = irrev ? 0 : lg_enc;
-                B.step_enc = (float)((1.0 + B.mant / 2048.0) * pow(2.0, (int)(P.prec + lg_enc) - (int)B.expn));
-                B.step_dec = (float)((1.0 + B.mant / 2048.0) * pow(2.0, (int)(P.prec + lg_dec) - (int)B.expn));
-                int v = (int)B.expn + (int)P.p.numgbits - 1;
-                B.numbps = P.p.roi(ci) + (uint32_t)std::max(0, v);   // Quantizer.cpp:47: roishift + ...
-            }
+        const uint32_t nres = P.p.c_numres(ci);
+        for (uint32_t r = 0; r < nres; ++r)
+            for (auto& B : C.res[r].bands) band_quant(P, ci, nres, r, B);
+    }
+}
+
+// Encode refusal by precision: a band whose largest reachable magnitude its coder
+// cannot hold.  That magnitude is the largest input magnitude times the band's BIBO analysis gain:
+// the 5/3 gains of ht_rev_expn, the 9/7 gains below for the lifting scaled as the forward
+// kernels scale it (low band / K, high band * K).  Containers: the Part-1 encoders keep
+// magnitude << 6 in 32 bits, unsigned in the wave-per-block coder (26 bits) and signed in the
+// lane-per-block coder of mode switches and wide blocks (25 bits); the HT decoders place a
+// block's magnitudes under 30 - k_msbs, k_msbs = numbps - 1 <= 29 (30 bit-planes); a QCD exponent has 5 bits; the 9/7
+// path's float32 samples are exact up to 2^24 after the DC shift (25 bits of precision).  The
+// bands judged are those of at least two resolutions, so numres = 1 accepts nothing that a
+// transform would refuse.
+static void check_precision(const Plan& P) {
+    static const double l53[16] = {1.0000, 1.5000, 1.6250, 1.6875, 1.6963, 1.7067, 1.7116, 1.7129,
+                                   1.7141, 1.7145, 1.7151, 1.7152, 1.7155, 1.7155, 1.7156, 1.7156};
+    static const double h53[16] = {2.0000, 2.5000, 2.7500, 2.8047, 2.8198, 2.8410, 2.8558, 2.8601,
+                                   2.8628, 2.8656, 2.8662, 2.8667, 2.8669, 2.8670, 2.8671, 2.8671};
+    static const double l97[5] = {1.0000, 1.3803, 1.3328, 1.3067, 1.3028};   // past [4]: smaller
+    static const double h97[5] = {2.5953, 2.6253, 2.5514, 2.4703, 2.4625};
+    static const char* const oname[4] = {"LL", "HL", "LH", "HH"};
+    const uint32_t prec = P.prec;
+    char msg[256];
+    const double margin = 1.0 + 1.0 / 1024;   // the gain tables' four decimals
+    Plan Q;   // the bands' native steps, ROI shift left out (it has its own refusal)
+    Q.prec = P.prec; Q.sgnd = P.sgnd; Q.nc = P.nc; Q.p = P.p; Q.p.roishift.clear();
+    for (uint32_t c = 0; c < P.nc; ++c) {
+        const bool irrev = P.p.c_irrev(c) != 0, ht = P.p.c_ht(c);
+        if (irrev && prec > 25) {
+            snprintf(msg, sizeof msg, "precision %u: the 9/7 transform's float32 samples are exact up to 25 bits", prec);
+            throw GkError(msg);
         }
+        const uint32_t nres = std::max(P.p.c_numres(c), 2u), nd = nres - 1;
+        // input range after the DC shift: [-2^(p-1), 2^(p-1) - 1]; RCT chroma is a difference of
+        // two samples, +-(2^p - 1); ICT rows have absolute sums <= 1
+        const bool chroma = P.mct3() && !irrev && (c == 1 || c == 2);
+        const double full = chroma ? ldexp(1.0, (int)prec) - 1.0 : ldexp(1.0, (int)prec - 1);
+        // a band without a low-pass step has no DC gain: the range counts from its centre
+        const double centred = chroma ? full : full - 0.5;
+        const int hold = ht ? 30 : (P.p.c_class(c) & 3u) == 1 ? 25 : 26;
+        for (uint32_t r = 0; r < nres; ++r)
+            for (uint32_t orient = r ? 1 : 0; orient < (r ? 4u : 1u); ++orient) {
+                BandG B{};
+                B.orient = orient;
+                band_quant(Q, c, nres, r, B);
+                const uint32_t d = r ? nd - r : nd;
+                double g, in = full, slack;
+                if (!irrev) {
+                    auto L = [&](uint32_t i) { return l53[std::min(i, 15u)]; };
+                    auto H = [&](uint32_t i) { return h53[std::min(i, 15u)]; };
+                    g = r == 0 ? L(nd) * L(nd) : orient == 3 ? H(d) * H(d) : H(d) * L(d + 1);
+                    // the finest HH is two exact integer high-pass steps (gain 2 * 2); every other
+                    // band passes low-pass steps that round, each by less than 1
+                    const bool exact = r == nd && orient == 3;
+                    if (exact) in = centred;
+                    slack = exact ? 0.0 : 16.0 * nres;
+                    if (!exact) g *= margin;
+                } else {
+                    auto L = [&](uint32_t i) { return l97[std::min(i, 4u)]; };
+                    auto H = [&](uint32_t i) { return h97[std::min(i, 4u)]; };
+                    g = (r == 0 ? L(nd) * L(nd) : orient == 3 ? H(d) * H(d) : H(d) * L(d + 1)) * margin / (double)B.step_enc;
+                    slack = 1.0;   // the quantiser's rounding
+                }
+                const double bound = g * in + slack;
+                if (B.expn > 31) {
+                    snprintf(msg, sizeof msg, "precision %u: exponent %u of the %s band (component %u, resolution %u) "
+                             "does not fit the 5-bit QCD field", prec, B.expn, oname[orient], c, r);
+                    throw GkError(msg);
+                }
+                if (ht && B.numbps > 30) {
+                    snprintf(msg, sizeof msg, "precision %u: %u bit-planes in the %s band (component %u, resolution %u), "
+                             "the HT coder holds 30", prec, B.numbps, oname[orient], c, r);
+                    throw GkError(msg);
+                }
+                if (!(bound < ldexp(1.0, hold))) {
+                    snprintf(msg, sizeof msg, "precision %u: the %s band (component %u, resolution %u) can reach %d "
+                             "magnitude bits, the %s coder holds %d", prec, oname[orient], c, r,
+                             (int)floor(log2(bound)) + 1, ht ? "HT" : "Part-1", hold);
+                    throw GkError(msg);
+                }
+            }
     }
 }
 
@@ -3332,6 +3417,7 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     if (want.p.cblk_sty > 0x7f) throw GkError("unknown code-block style bits");
     if (want.nc > 255 || want.nc == 0) throw GkError("bad component count");
     if (want.prec == 0 || want.prec > 31) throw GkError("component precision must be 1..31 bits");
+    check_precision(want);
     if (want.w == 0 || want.h == 0) throw GkError("empty image");
     // grk_compress.cpp:981-988 (and A.6.1's xcb, ycb): 4 <= side <= 1024, at most 4096 samples
     if (want.p.cbw < 2 || want.p.cbh < 2 || want.p.cbw > 10 || want.p.cbh > 10 || want.p.cbw + want.p.cbh > 12)

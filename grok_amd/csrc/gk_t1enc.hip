@@ -127,16 +127,18 @@ __global__ __launch_bounds__(64) void k_t1_cm(const int32_t* __restrict__ coef, 
     uint32_t mx = 0;
 #pragma unroll
     for (int y = 0; y < 64; ++y) {
-        int32_t v = 0;
+        // the magnitude with its 6 fractional bits fills the uint32 (26 bits); the sign is the
+        // coefficient's own (an int's and a float's sign bit alike), read only once it is significant
+        int32_t raw = 0;
+        uint32_t a = 0;
         if (y < (int)h && lane < (int)w) {
-            int32_t raw = coef[B.band_off + (size_t)y * B.stride + lane];
-            if (irrev) v = (int32_t)rintf((__int_as_float(raw) / B.step) * 64.0f);
-            else v = raw * 64;
+            raw = coef[B.band_off + (size_t)y * B.stride + lane];
+            if (irrev) a = (uint32_t)fabsf(rintf((__int_as_float(raw) / B.step) * 64.0f));
+            else a = (uint32_t)(raw < 0 ? -raw : raw) * 64u;
         }
-        uint32_t a = (uint32_t)(v < 0 ? -v : v);
         m[y] = a;
         mx = a > mx ? a : mx;
-        negcol |= (uint64_t)(v < 0) << y;
+        negcol |= (uint64_t)(raw < 0) << y;
     }
     if (const uint32_t rs = B.flags >> 3) {   // ROI maxshift (the component is the region): index integer part up
         mx = 0;

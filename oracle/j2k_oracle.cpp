@@ -2653,6 +2653,93 @@ static std::vector<uint32_t> write_tile_part(std::vector<uint8_t>& o, EncodeStat
     return psots;
 }
 
+// ----------------------------------------------------------------------------
+// Encode refusal by precision: a band whose largest reachable magnitude the coder
+// cannot hold.  The largest magnitude of a band is the largest input magnitude times the band's
+// BIBO analysis gain (the largest sum of absolute weights with which input samples enter one of
+// its coefficients): the 5/3 gains of HTParams.cpp:134-145 above, the 9/7 gains below for the
+// lifting as fwd97_1d scales it (low band / K, high band * K).  Containers:
+//  - Part 1: t1_encode_all keeps magnitude << 6 (T1_NMSEDEC_FRACBITS) in a uint32: 26 bits;
+//  - HT: the decoders place a block's magnitudes under 30 - k_msbs, k_msbs = numbps - 1 <= 29: 30 bit-planes;
+//  - QCD / QCC: a 5-bit exponent;
+//  - 9/7: float32 samples, exact up to 2^24 after the DC shift: 25 bits of precision.
+// The bands judged are those of at least two resolutions, so that numres = 1 accepts nothing
+// that a transform would refuse.  Returns the reason, empty when the encode is accepted.
+// ----------------------------------------------------------------------------
+static const double bibo97_l[5] = {1.0000, 1.3803, 1.3328, 1.3067, 1.3028};   // past [4]: smaller
+static const double bibo97_h[5] = {2.5953, 2.6253, 2.5514, 2.4703, 2.4625};
+static thread_local std::string t_last_error;
+static std::string precision_refusal(const Params& p0, uint32_t nc, uint32_t prec, int sgnd) {
+    char msg[256];
+    if (prec == 0 || prec > 31) {
+        snprintf(msg, sizeof msg, "precision %u: component precision must be 1..31 bits", prec);
+        return msg;
+    }
+    if (p0.irreversible && prec > 25) {
+        snprintf(msg, sizeof msg, "precision %u: the 9/7 transform's float32 samples are exact up to 25 bits", prec);
+        return msg;
+    }
+    Params p = p0;
+    settle_mct(p, nc);
+    p.numres = std::max(p0.numres, 2u);
+    const uint32_t nd = p.numres - 1;
+    const double margin = 1.0 + 1.0 / 1024;   // the gain tables' four decimals
+    static const char* const oname[4] = {"LL", "HL", "LH", "HH"};
+    for (uint32_t c = 0; c < nc; ++c) {
+        Comp C;
+        build_geometry(C, 0, 0, 64, 64, p);
+        assign_steps(C, p, prec, true, nullptr, sgnd, 0, c);
+        // input range after the DC shift: [-2^(p-1), 2^(p-1) - 1]; RCT chroma is a difference of
+        // two samples, +-(2^p - 1); ICT rows have absolute sums <= 1
+        const bool chroma = p.mct && !p.irreversible && (c == 1 || c == 2);
+        const double full = chroma ? ldexp(1.0, (int)prec) - 1.0 : ldexp(1.0, (int)prec - 1);
+        // a band without a low-pass step has no DC gain: the range counts from its centre
+        const double centred = chroma ? full : full - 0.5;
+        for (uint32_t r = 0; r < p.numres; ++r)
+            for (const Band& B : C.res[r].bands) {
+                const uint32_t d = r ? nd - r : nd;
+                double g, in = full, slack;
+                if (!p.irreversible) {
+                    auto L = [](uint32_t i) { return (double)bibo53_l[std::min(i, 15u)]; };
+                    auto H = [](uint32_t i) { return (double)bibo53_h[std::min(i, 15u)]; };
+                    g = r == 0 ? L(nd) * L(nd) : B.orient == 3 ? H(d) * H(d) : H(d) * L(d + 1);
+                    // the finest HH is two exact integer high-pass steps (gain 2 * 2); every other
+                    // band passes low-pass steps that round, each by less than 1
+                    const bool exact = r == nd && B.orient == 3;
+                    if (exact) in = centred;
+                    slack = exact ? 0.0 : 16.0 * p.numres;
+                    if (!exact) g *= margin;
+                } else {
+                    auto L = [](uint32_t i) { return bibo97_l[std::min(i, 4u)]; };
+                    auto H = [](uint32_t i) { return bibo97_h[std::min(i, 4u)]; };
+                    g = (r == 0 ? L(nd) * L(nd) : B.orient == 3 ? H(d) * H(d) : H(d) * L(d + 1)) * margin / (double)B.stepsize;
+                    slack = 1.0;   // the quantiser's rounding
+                }
+                const double bound = g * in + slack;
+                const int need = (int)floor(log2(bound)) + 1;
+                const int hold = p.ht() ? 30 : 26;
+                if (B.expn > 31) {
+                    snprintf(msg, sizeof msg, "precision %u: exponent %u of the %s band (component %u, resolution %u) "
+                             "does not fit the 5-bit QCD field", prec, B.expn, oname[B.orient], c, r);
+                    return msg;
+                }
+                if (p.ht() && B.numbps > 30) {
+                    snprintf(msg, sizeof msg, "precision %u: %u bit-planes in the %s band (component %u, resolution %u), "
+                             "the HT coder holds 30", prec, B.numbps, oname[B.orient], c, r);
+                    return msg;
+                }
+                if (!(bound < ldexp(1.0, hold))) {
+                    snprintf(msg, sizeof msg, "precision %u: the %s band (component %u, resolution %u) can reach %d "
+                             "magnitude bits, the %s coder holds %d", prec, oname[B.orient], c, r, need,
+                             p.ht() ? "HT" : "Part-1", hold);
+                    return msg;
+                }
+            }
+    }
+    return std::string();
+}
+const char* orc_last_error() { return t_last_error.c_str(); }
+
 // Full encode (5/3 or 9/7, Part 1 or HT, any number of layers, one or more tiles).
 // Returns the codestream size, or 0 on failure / insufficient capacity.
 static void jp2_prefix(std::vector<uint8_t>& o, uint32_t w, uint32_t h, uint32_t nc, uint32_t prec, int sgnd,
@@ -2664,6 +2751,8 @@ size_t orc_encode(const int32_t* planes, uint32_t w, uint32_t h, uint32_t nc, ui
     size_t tlm_pos = 0;
     uint32_t nt = 0;
     const Params p0 = to_params(cp);
+    t_last_error = precision_refusal(p0, nc, prec, sgnd);
+    if (!t_last_error.empty()) return 0;
     if (!prc_exps_ok(p0) || !pocs_cover(p0, nc) || num_parts(p0, nc) < 1) return 0;
     // packed packet headers: one tile part per tile, no rate control or PLT (test streams)
     if (p0.ppx && (num_parts(p0, nc) != 1 || needs_rate_control(p0) || p0.plt)) return 0;
@@ -2814,6 +2903,8 @@ size_t orc_main_header(uint32_t w, uint32_t h, uint32_t nc, uint32_t prec, int s
 size_t orc_encode_tile_parts(const int32_t* slab, uint32_t w, uint32_t h, uint32_t nc, uint32_t prec, int sgnd,
                              const orc_cparams* cp, uint32_t row0, uint32_t rows, uint32_t tb, uint32_t te,
                              uint8_t* out, size_t cap, uint32_t* part_lens) {
+    t_last_error = precision_refusal(to_params(cp), nc, prec, sgnd);
+    if (!t_last_error.empty()) return 0;
     if (!prc_exps_ok(to_params(cp)) || to_params(cp).subsampled()) return 0;   // (whole-image planes only)
     std::vector<std::vector<uint8_t>> parts(te - tb);
     par_for(te - tb, [&](size_t q) {

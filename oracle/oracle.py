@@ -63,6 +63,7 @@ def lib():
         _lib.orc_decode.restype = ctypes.c_int
         _lib.orc_decode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p] + [P(ctypes.c_uint32)] * 4
         _lib.orc_set_partial.argtypes = [ctypes.c_int]
+        _lib.orc_last_error.restype = ctypes.c_char_p
         _lib.orc_last_comp_dims.restype = ctypes.c_uint32
         _lib.orc_last_comp_dims.argtypes = [ctypes.c_void_p]
         _lib.orc_last_comp_prec.restype = ctypes.c_uint32
@@ -209,6 +210,12 @@ def comp_shape(w, h, dx, dy, origin=(0, 0)):
     return -(-(y0 + h) // dy) - -(-y0 // dy), -(-(x0 + w) // dx) - -(-x0 // dx)
 
 
+def _why(what):
+    """`what`, with the reason of a refused encode (a precision the coders cannot hold)."""
+    why = lib().orc_last_error().decode()
+    return "%s: %s" % (what, why) if why else what
+
+
 def encode(img, prec, signed=False, size=None, **kw):
     """img: (C, H, W) int32 array; with subsampling=[(dx, dy), ...], a list of per-component 2-D
     planes of comp_shape(W, H, dx, dy, origin) and size=(W, H), the image area."""
@@ -228,7 +235,7 @@ def encode(img, prec, signed=False, size=None, **kw):
     n = lib().orc_encode(a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), w, h, c, prec, int(signed),
                          ctypes.byref(p), out.ctypes.data, cap)
     if n == 0:
-        raise RuntimeError("oracle encode failed")
+        raise RuntimeError(_why("oracle encode failed"))
     return out[:n].tobytes()
 
 
@@ -265,7 +272,7 @@ def encode_tile_parts(slab, row0, image_hw, prec, tile_begin, tile_end, signed=F
     n = lib().orc_encode_tile_parts(a.ctypes.data, W, H, c, prec, int(signed), ctypes.byref(p), row0, rows,
                                     tile_begin, tile_end, out.ctypes.data, cap, lens)
     if n == 0:
-        raise RuntimeError("oracle tile-part encode failed")
+        raise RuntimeError(_why("oracle tile-part encode failed"))
     return out[:n].tobytes(), list(lens)
 
 
