@@ -5776,6 +5776,9 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
             ctx->tm.t1_steps_max = ctx->tm.t1_steps_total = ctx->tm.t1_symbols = 0;
             ctx->tm.t1_solo_decisions = ctx->tm.t1_solo_decisions_max = 0;
             ctx->tm.t1_solo_blocks = nsb;
+            // classes whose split the shared rule chose (zeroed when the call began: a call may decode
+            // several classes); without solo waves (under 8 blocks) no rule is taken
+            ctx->tm.t1_shared += (shared && sp.waves) ? 1 : 0;
             if (getenv("GK_T1_STATS")) {
                 uint64_t sv[5];
                 gk_t1dec_stats(sv);
@@ -6078,6 +6081,7 @@ int gk_encode(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, 
     try {
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
         int rc = 0;
         size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc);
         if (out_len) *out_len = n;
@@ -6096,6 +6100,7 @@ int gk_encode_tiles(gk_ctx* ctx, const gk_image_info* info, const void* const* c
     try {
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
         int rc = 0;
         size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc,
                                tile_begin, tile_end, false, part_lens);
@@ -6115,6 +6120,7 @@ int gk_encode_blocks(gk_ctx* ctx, const gk_image_info* info, const void* const* 
     try {
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
         if (p && p->tile_size_on && (p->t_width < info->w || p->t_height < info->h))
             throw GkError("code-block results are produced for single-tile images only (Grok's plugin tile is one tile)");
         int rc = 0;
@@ -6385,6 +6391,7 @@ int gk_decode(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void
     try {
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
         decode_impl(ctx, cs, len, cs_on_device, comps, strides, sample_bytes, out_on_device);
         return 0;
     } catch (const GkError& e) {
@@ -6486,6 +6493,7 @@ int gk_decode_window(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
     try {
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
         const uint32_t win[4] = {x0, y0, x1, y1};
         decode_impl(ctx, cs, len, cs_on_device, comps, strides, sample_bytes, out_on_device, win);
         return 0;

@@ -1123,12 +1123,12 @@ __global__ __launch_bounds__(64) void k_t1_recon(const GkBlock* __restrict__ blo
 #include "gk_launch.h"
 // Blocks per 64-lane wave (GK_T1DEC_LANES, 1..64).
 uint32_t gk_t1dec_lanes() {
-    static uint32_t lanes = 0;
-    if (!lanes) {
+    // (read once; the language makes a function-local static's initialisation thread-safe)
+    static const uint32_t lanes = [] {
         const char* v = getenv("GK_T1DEC_LANES");
-        int n = v ? atoi(v) : 64;
-        lanes = (uint32_t)(n < 1 ? 1 : (n > 64 ? 64 : n));
-    }
+        const int n = v ? atoi(v) : 64;
+        return (uint32_t)(n < 1 ? 1 : (n > 64 ? 64 : n));
+    }();
     return lanes;
 }
 // max steps per wave, steps, symbols, solo decisions, solo decisions of the busiest solo wave (GK_T1_STATS)
@@ -1140,18 +1140,21 @@ void gk_t1dec_stats(uint64_t out[5]) { for (int i = 0; i < 5; ++i) out[i] = g_la
 // ratio the host packs with (gk_engine.cpp: a lane-parallel wave's cycles per decision of its
 // busiest lane over a solo wave's cycles per decision; C2 measured ~1,675 / 572).
 GkSoloPlan gk_t1dec_solo_plan(uint32_t nblocks, uint32_t lanes) {
-    static int ncu = -1, force = -2;
-    static float ratio = 2.5f;
-    if (ncu < 0) {
+    struct Cfg { int ncu, force; float ratio; };
+    // (finished before it is published: engines on several host threads may make the first call together)
+    static const Cfg cfg = [] {
+        Cfg c{0, -1, 2.5f};
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
             n = 0;
-        ncu = n;
+        c.ncu = n;
         const char* v = getenv("GK_T1DEC_SOLO");
-        force = v ? atoi(v) : -1;
-        if (const char* r = getenv("GK_T1DEC_SOLO_R")) ratio = (float)atof(r);
-    }
-    GkSoloPlan sp{0, -1, ratio};
+        c.force = v ? atoi(v) : -1;
+        if (const char* r = getenv("GK_T1DEC_SOLO_R")) c.ratio = (float)atof(r);
+        return c;
+    }();
+    const int ncu = cfg.ncu, force = cfg.force;
+    GkSoloPlan sp{0, -1, cfg.ratio};
     if (force >= 0) {
         sp.forced = (int)std::min<uint32_t>((uint32_t)force, nblocks);
         sp.waves = ((uint32_t)sp.forced + 11) / 12 * 12;
@@ -1166,23 +1169,32 @@ GkSoloPlan gk_t1dec_solo_plan(uint32_t nblocks, uint32_t lanes) {
 void gk_launch_t1_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* order,
                       uint64_t* scratch, const uint64_t* wave_off, uint32_t nblocks, uint32_t nsolo) {
     if (!nblocks) return;
-    static unsigned long long* stats = nullptr;
     const char* sv = getenv("GK_T1_STATS");
     const bool want = sv != nullptr, timing = sv && atoi(sv) == 2;
-    if (want && !stats) { (void)hipMalloc(&stats, 256); }
-    if (want) (void)hipMemsetAsync(stats, 0, 256, st);
-    static int kpark = -1;
-    if (kpark < 0) {
+    unsigned long long* stats = nullptr;
+    if (want) {   // (allocated once, by whichever thread asks first)
+        static unsigned long long* const buf = [] {
+            unsigned long long* p = nullptr;
+            (void)hipMalloc(&p, 256);
+            return p;
+        }();
+        stats = buf;
+        (void)hipMemsetAsync(stats, 0, 256, st);
+    }
+    // computed completely before it is published (engines on several host threads may make the
+    // first call together)
+    static const int kpark = [] {
         const char* kp = getenv("GK_T1DEC_PARK");   // parked lanes that trigger a stripe boundary
-        kpark = kp ? atoi(kp) : 16;
+        int k = kp ? atoi(kp) : 16;
         // GK_T1DEC_CRIT=0: no event for the lane with the most work left alone (bit 8 of kpark)
         const char* kc = getenv("GK_T1DEC_CRIT");
-        if (!kc || atoi(kc)) kpark |= 0x100;
-        if (kc && atoi(kc) >= 2) kpark |= (atoi(kc) - 1) << 10;
+        if (!kc || atoi(kc)) k |= 0x100;
+        if (kc && atoi(kc) >= 2) k |= (atoi(kc) - 1) << 10;
         // GK_T1DEC_MID=0: no half-group exit when that lane has parked (bit 9)
         const char* km = getenv("GK_T1DEC_MID");
-        if (!km || atoi(km)) kpark |= 0x200;
-    }
+        if (!km || atoi(km)) k |= 0x200;
+        return k;
+    }();
     const uint32_t nwaves = (nblocks + 63) / 64;
     auto launch = [&](auto kern, uint32_t W, unsigned long long* stp) {
         const uint32_t ngroups = (nwaves + W - 1) / W;

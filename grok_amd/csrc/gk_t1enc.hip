@@ -899,12 +899,11 @@ void gk_launch_t1_mq(hipStream_t st, const uint8_t* sym, const uint64_t* sym_off
     if (count == 0xffffffffu) count = nblocks;
     if (!count) return;
     nsolo = std::min((nsolo + 3) / 4 * 4, (count + 3) / 4 * 4);   // whole workgroups of solo waves
-    static uint32_t nl = 0;
-    if (!nl) {   // blocks per 64-lane wave (GK_T1ENC_LANES, 1..64)
+    static const uint32_t nl = [] {   // blocks per 64-lane wave (GK_T1ENC_LANES, 1..64), read once
         const char* v = getenv("GK_T1ENC_LANES");
         const int n = v ? atoi(v) : 64;
-        nl = (uint32_t)(n < 1 ? 1 : (n > 64 ? 64 : n));
-    }
+        return (uint32_t)(n < 1 ? 1 : (n > 64 ? 64 : n));
+    }();
     // dynamic LDS: the four waves' pass ends, padded so one workgroup fills the CU's 160 KiB
     const size_t pe = (size_t)(GK_MAX_PASSES + 1) * nl * 4 * 4;
     const size_t lds = std::max(pe, (size_t)163840 - 4 * sizeof(MqLds));

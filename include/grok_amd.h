@@ -110,6 +110,9 @@ typedef struct gk_timings {
     /* Part-1 decode: code-blocks given to solo waves (one wave per block on the SIMDs the
        lane-parallel waves leave); with GK_T1_STATS, their decisions and the largest per wave */
     uint64_t t1_solo_blocks, t1_solo_decisions, t1_solo_decisions_max;
+    /* Part-1 decode: decoder classes of the last call whose solo / lane-parallel split was chosen
+       by the rule for a device shared with another engine's call in progress (0 on encode) */
+    uint64_t t1_shared;
 } gk_timings;
 
 typedef struct gk_ctx gk_ctx;
