@@ -26,9 +26,51 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_last_error", "gk_version", "gk_set_decode_layers", "gk_set_decode_reduce",
            "gk_set_window_rule", "gk_set_subsampling", "gk_probe_components", "gk_header_components",
            "gk_probe_colour", "gk_header_colour", "gk_header_icc", "gk_set_decode_colour", "gk_probe_icc",
-           "gk_probe_stream_components", "gk_set_decode_display", "gk_probe_display")
+           "gk_probe_stream_components", "gk_set_decode_display", "gk_probe_display", "gk_set_decode_precision",
+           "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels")
 GK_MAX_CHANNELS = 256
-GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE = 1, 2   # gk_set_decode_display flags
+GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB = 1, 2, 4   # gk_set_decode_display flags
+GK_PREC_CLIP, GK_PREC_SCALE = 0, 1   # gk_precision::mode (grk_precision_mode)
+
+
+class Precision(ctypes.Structure):
+    """gk_precision (include/grok_amd.h): one entry of a forced-precision list."""
+    _fields_ = [("prec", ctypes.c_uint8), ("mode", ctypes.c_uint8)]
+
+
+def parse_precision(spec):
+    """A forced-precision list as [(prec, "C" | "S")]: `spec` is None / [] (no list), such a list, or
+    grk_decompress's -p string (parsePrecision, grk_decompress.cpp:212-330): comma-separated
+    entries of a precision 1..32 and an optional mode letter C (clip, the default) or S (scale).
+    (0 keeps a channel's precision and is accepted in a list given as tuples, and here.)"""
+    if spec is None:
+        return []
+    if isinstance(spec, str):
+        out = []
+        for item in spec.split(","):
+            item = item.strip()
+            mode = "C"
+            if item and item[-1] in "CS":
+                item, mode = item[:-1], item[-1]
+            if not item.isdigit() or int(item) > 32:
+                raise ValueError("precision %r: expected {prec}[C|S] with a precision of 1..32" % item)
+            out.append((int(item), mode))
+        return out
+    out = []
+    for prec, mode in spec:
+        mode = {GK_PREC_CLIP: "C", GK_PREC_SCALE: "S"}.get(mode, mode)
+        if mode not in ("C", "S") or not 0 <= int(prec) <= 255:
+            raise ValueError("precision entry (%r, %r): expected (prec, 'C' | 'S')" % (prec, mode))
+        out.append((int(prec), mode))
+    return out
+
+
+def _precision_array(spec):
+    lst = parse_precision(spec)
+    arr = (Precision * max(len(lst), 1))()
+    for i, (prec, mode) in enumerate(lst):
+        arr[i] = Precision(prec, GK_PREC_SCALE if mode == "S" else GK_PREC_CLIP)
+    return arr, len(lst)
 
 
 class Poc(ctypes.Structure):
@@ -159,6 +201,18 @@ def load_library(build_if_missing=True):
     lib.gk_probe_display.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, P(ImageInfo),
                                      P(ColourInfo)] + [P(ctypes.c_uint32)] * 4 + [ctypes.c_uint32, ctypes.c_char_p,
                                                                                   ctypes.c_size_t]
+    lib.gk_set_decode_precision.restype = ctypes.c_int
+    lib.gk_set_decode_precision.argtypes = [ctypes.c_void_p, P(Precision), ctypes.c_uint32]
+    lib.gk_probe_output.restype = ctypes.c_int
+    lib.gk_probe_output.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, P(Precision),
+                                    ctypes.c_uint32, P(ImageInfo), P(ColourInfo)] + [P(ctypes.c_uint32)] * 4 + \
+        [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]
+    lib.gk_decode_pixels.restype = ctypes.c_int
+    lib.gk_decode_pixels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                     ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int]
+    lib.gk_decode_window_pixels.restype = ctypes.c_int
+    lib.gk_decode_window_pixels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] + \
+        [ctypes.c_uint32] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -286,6 +340,7 @@ class DisplayInfo:
         self.colour_space = colour.colour_space
         self.converted = bool(colour.display_applied & GK_DISPLAY_RGB)
         self.upsampled = bool(colour.display_applied & GK_DISPLAY_UPSAMPLE)
+        self.replicated = bool(colour.display_applied & GK_DISPLAY_FORCE_RGB)   # grey to RGB
 
 
 def probe_display(cs, rgb=False, upsample=False, reduce=0):
@@ -301,6 +356,25 @@ def probe_display(cs, rgb=False, upsample=False, reduce=0):
     flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0)
     n = lib.gk_probe_display(b.ctypes.data, len(b), flags, int(reduce), ctypes.byref(info), ctypes.byref(colour),
                              dx, dy, pr, sg, 16384, msg, 512)
+    if n < 0:
+        raise ValueError(msg.value.decode())
+    return DisplayInfo(info, colour, [(dx[c], dy[c], pr[c], sg[c]) for c in range(n)], int(reduce))
+
+
+def probe_output(cs, rgb=False, upsample=False, force_rgb=False, precision=None, reduce=0):
+    """gk_probe_output: probe_display with the grey-to-RGB flag and a forced-precision list
+    (parse_precision): what Engine.decode / decode_pixels return under set_decode_display(rgb,
+    upsample, force_rgb) and set_decode_precision(precision), no engine or GPU needed."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    info, colour = ImageInfo(), ColourInfo()
+    dx, dy, pr, sg = [(ctypes.c_uint32 * 16384)() for _ in range(4)]
+    msg = ctypes.create_string_buffer(512)
+    flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0) | \
+        (GK_DISPLAY_FORCE_RGB if force_rgb else 0)
+    arr, n = _precision_array(precision)
+    n = lib.gk_probe_output(b.ctypes.data, len(b), flags, int(reduce), arr, n, ctypes.byref(info), ctypes.byref(colour),
+                            dx, dy, pr, sg, 16384, msg, 512)
     if n < 0:
         raise ValueError(msg.value.decode())
     return DisplayInfo(info, colour, [(dx[c], dy[c], pr[c], sg[c]) for c in range(n)], int(reduce))
@@ -629,14 +703,74 @@ class Engine:
         if self.lib.gk_set_decode_colour(self.ctx, int(bool(apply))) != 0:
             self._err("gk_set_decode_colour")
 
-    def set_decode_display(self, rgb=False, upsample=False):
+    def set_decode_display(self, rgb=False, upsample=False, force_rgb=False):
         """gk_set_decode_display: what grk_decompress does to the decoded image, on the GPU.  rgb:
         sYCC (4:4:4, 4:2:2, 4:2:0), e-sYCC and CMYK images decode to RGB planes; upsample: subsampled
-        components are replicated to the image grid (grk_decompress -u).  Sticky; read_header,
-        subsampling and colour_info then describe the output, so decode returns one (C, H, W) array."""
-        flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0)
+        components are replicated to the image grid (grk_decompress -u); force_rgb: a grey image's
+        channel becomes R, G and B (grk_decompress -f; other channels follow, grey + alpha is RGBA).
+        Sticky; read_header, subsampling and colour_info then describe the output, so decode returns
+        one (C, H, W) array."""
+        flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0) | \
+            (GK_DISPLAY_FORCE_RGB if force_rgb else 0)
         if self.lib.gk_set_decode_display(self.ctx, flags) != 0:
             self._err("gk_set_decode_display")
+
+    def set_decode_precision(self, spec):
+        """gk_set_decode_precision: force the output channels' precision (grk_decompress -p).
+        spec: a list of (prec, "C" | "S") or a -p string such as "8S" or "8S,12C,0S"
+        (parse_precision); None or [] clears it.  Channel k takes entry min(k, n - 1); prec 0 keeps
+        the channel's precision; S scales as Grok does, C clamps to the forced range.  Sticky;
+        read_header reports the forced precisions, and 8 / 16-bit output is sized by them."""
+        arr, n = _precision_array(spec)
+        if self.lib.gk_set_decode_precision(self.ctx, arr, n) != 0:
+            self._err("gk_set_decode_precision")
+
+    def precisions(self):
+        """[(prec, signed)] per output channel of the stream the last read_header / decode read."""
+        pr, sg = (ctypes.c_uint32 * 16384)(), (ctypes.c_uint32 * 16384)()
+        n = self.lib.gk_header_components(self.ctx, None, None, pr, sg, 16384)
+        return [(pr[c], bool(sg[c])) for c in range(max(n, 0))]
+
+    def decode_pixels(self, cs, length=None, out=None, sample_bytes=0, window=None):
+        """gk_decode_pixels / gk_decode_window_pixels: the decoded image as packed pixels.  Returns
+        an (H, W, C) numpy array (int32, or 8 / 16-bit with sample_bytes 1 / 2), or fills ``out``: a
+        torch cuda tensor of that shape with stride(2) == 1, stride(1) == C and any row stride (its
+        element size selects the sample type).  C, H and W are what read_header reports under the
+        sticky settings (display flags, precision list, reduce); window = (x0, y0, x1, y1) decodes
+        that rectangle only.  Channels of different sizes (subsampled components) need
+        set_decode_display(upsample=True)."""
+        info = self.read_header(cs, length)
+        c = info.numcomps
+        red = getattr(self, "_reduce", 0)
+        sub = self.subsampling()
+        dx, dy = sub[0] if sub else (1, 1)
+        cd = lambda a, b: -(-a // b)
+        x0, y0, x1, y1 = window if window is not None else (0, 0, info.w, info.h)
+        gx = lambda v: cd(cd(v + info.x0, dx), 1 << red)
+        gy = lambda v: cd(cd(v + info.y0, dy), 1 << red)
+        h, w = gy(y1) - gy(y0), gx(x1) - gx(x0)
+        if out is not None:
+            assert tuple(out.shape) == (h, w, c) and out.stride(2) == 1 and (w == 1 or out.stride(1) == c)
+            sample_bytes = _sample_bytes(out)
+            es = sample_bytes or 4
+            dst, row_bytes, res, out_dev = ctypes.c_void_p(out.data_ptr()), (out.stride(0) if h > 1 else w * c) * es, out, 1
+        else:
+            es = sample_bytes or 4
+            res = np.empty((h, w, c), _np_sample_dtype(sample_bytes, info))
+            dst, row_bytes, out_dev = ctypes.c_void_p(res.ctypes.data), w * c * es, 0
+        if _is_torch_cuda(cs):
+            src, n, on_dev = ctypes.c_void_p(cs.data_ptr()), length, 1
+        else:
+            b = np.frombuffer(cs, np.uint8)
+            src, n, on_dev = ctypes.c_void_p(b.ctypes.data), len(cs), 0
+        if window is None:
+            rc = self.lib.gk_decode_pixels(self.ctx, src, n, on_dev, dst, row_bytes, sample_bytes, out_dev)
+        else:
+            rc = self.lib.gk_decode_window_pixels(self.ctx, src, n, on_dev, x0, y0, x1, y1, dst, row_bytes, sample_bytes,
+                                                  out_dev)
+        if rc != 0:
+            self._err("gk_decode_pixels")
+        return res
 
     def decode_window(self, cs, window, length=None, out=None, sample_bytes=0):
         """gk_decode_window: window = (x0, y0, x1, y1).  Returns a (C, y1-y0, x1-x0) numpy

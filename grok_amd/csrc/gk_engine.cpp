@@ -2884,11 +2884,24 @@ struct DisplayOut {
     bool converted = false, upsampled = false;
     uint32_t colour_space = 0;    // of the output (GRK_COLOR_SPACE)
     uint32_t ofx = 0, ofy = 0;    // oddFirstX / oddFirstY
-    struct Ch { uint32_t dx = 1, dy = 1, prec = 0, sgnd = 0, typ = 0, asoc = 0; };
+    struct Ch {
+        uint32_t dx = 1, dy = 1, prec = 0, sgnd = 0, typ = 0, asoc = 0;
+        // the output stage (k_pixels): the channel of the stage before it (conversion and
+        // upsampling done, grey not yet replicated) that it reads, that channel's precision, and
+        // what a forced precision does to its samples (GkPixOp)
+        uint32_t from = 0, prec0 = 0;
+        uint32_t op = GK_PIX_NONE, shift = 0;
+        int32_t lo = 0, hi = 0;
+        float scale = 1.0F;
+    };
     std::vector<Ch> ch;           // output channels
+    uint32_t nstage = 0;          // channels before grey to RGB
+    bool replicated = false;      // GK_DISPLAY_FORCE_RGB made three channels of a grey one
+    bool forced = false;          // a precision entry changes a channel
     bool active() const { return stage != NONE; }
+    bool out_active() const { return replicated || forced; }   // needs the output stage
     uint32_t max_prec() const { uint32_t m = 0; for (const Ch& c : ch) m = std::max(m, c.prec); return m; }
-    uint32_t applied() const { return (converted ? 1u : 0u) | (upsampled ? 2u : 0u); }
+    uint32_t applied() const { return (converted ? 1u : 0u) | (upsampled ? 2u : 0u) | (replicated ? 4u : 0u); }
 };
 // Plane size of a component sampled every (dx, dy) over the image area or the window (image
 // relative), reduced: every edge ceil(ceil(x / dx) / 2^red).
@@ -2899,8 +2912,8 @@ static void comp_dims(const Plan& W, uint32_t dx, uint32_t dy, uint32_t red, con
     w = g(cx1, dx) - g(cx0, dx);
     h = g(cy1, dy) - g(cy0, dy);
 }
-static DisplayOut resolve_display(const Jp2Colour& C, const ColourOut& O, const Plan& W, uint32_t flags, uint32_t red,
-                                  const uint32_t* win) {
+static DisplayOut resolve_display_flags(const Jp2Colour& C, const ColourOut& O, const Plan& W, uint32_t flags, uint32_t red,
+                                        const uint32_t* win) {
     DisplayOut D;
     const uint32_t n = (uint32_t)O.ch.size();
     D.ch.resize(n);
@@ -2929,9 +2942,11 @@ static DisplayOut resolve_display(const Jp2Colour& C, const ColourOut& O, const 
         if (O.active())
             throw GkError(std::string("display: ") + what + " conversion of a file with a palette or a channel definition is not supported");
     };
-    if (flags & GK_DISPLAY_RGB) {
+    if (flags & (GK_DISPLAY_RGB | GK_DISPLAY_FORCE_RGB)) {   // (:1335-1341)
         if (D.colour_space != 4 && n == 3 && D.ch[0].dx == D.ch[0].dy && D.ch[1].dx != 1) D.colour_space = 4;
         else if (n <= 2) D.colour_space = 3;
+    }
+    if (flags & GK_DISPLAY_RGB) {
         if (D.colour_space == 4) {
             if (n != 3) throw GkError("display: sYCC: number of components " + std::to_string(n) + " not equal to 3");
             int mode = -1;
@@ -3001,6 +3016,81 @@ static DisplayOut resolve_display(const Jp2Colour& C, const ColourOut& O, const 
     }
     return D;
 }
+static const char* colour_space_name(uint32_t cs) {   // GRK_COLOR_SPACE
+    switch (cs) {
+        case 0: return "unknown";
+        case 2: return "sRGB";
+        case 3: return "grey";
+        case 4: return "sYCC";
+        case 5: return "e-sYCC";
+        case 6: return "CMYK";
+        case 7: return "default CIELab";
+        case 8: return "custom CIELab";
+        case 9: return "ICC";
+        default: return "unspecified";
+    }
+}
+// The whole of what a decode returns: the display flags, then GK_DISPLAY_FORCE_RGB's grey to RGB
+// (postProcess :1444-1468, convert_gray_to_rgb) and the precision list (:1469-1494), both done
+// by the output stage.  Every refusal is made here, from the header alone.
+static DisplayOut resolve_display(const Jp2Colour& C, const ColourOut& O, const Plan& W, uint32_t flags, uint32_t red,
+                                  const uint32_t* win, const std::vector<gk_precision>* list = nullptr) {
+    DisplayOut D = resolve_display_flags(C, O, W, flags, red, win);
+    D.nstage = (uint32_t)D.ch.size();
+    for (uint32_t k = 0; k < D.nstage; ++k) { D.ch[k].from = k; D.ch[k].prec0 = D.ch[k].prec; }
+    if (flags & GK_DISPLAY_FORCE_RGB) {
+        if (D.colour_space == 3) {
+            const DisplayOut::Ch g = D.ch[0];
+            D.ch.insert(D.ch.begin(), 2, g);   // R, G, B from channel 0, then the others
+            for (uint32_t k = 0; k < 3; ++k)
+                if (g.typ == 0) D.ch[k].asoc = k + 1;
+            D.replicated = true;
+            D.colour_space = 2;
+        } else if (D.colour_space == 4 && !(flags & GK_DISPLAY_RGB)) {
+            throw GkError("display: GK_DISPLAY_FORCE_RGB on an sYCC image: add GK_DISPLAY_RGB to convert it first");
+        } else if (D.colour_space != 2) {
+            throw GkError(std::string("display: GK_DISPLAY_FORCE_RGB: don't know how to convert a colour space of ") +
+                          colour_space_name(D.colour_space) + " to RGB" +
+                          ((D.colour_space == 4 || D.colour_space == 6) ? " (it was left unconverted)" : ""));
+        }
+    }
+    if (list && !list->empty()) {
+        const uint32_t n = (uint32_t)list->size();
+        for (uint32_t i = 0; i < n; ++i) {
+            if ((*list)[i].prec > 16)
+                throw GkError("precision entry " + std::to_string(i) + ": " + std::to_string((*list)[i].prec) +
+                              " bits (the output stage holds 0..16)");
+            if ((*list)[i].mode > GK_PREC_SCALE) throw GkError("precision entry " + std::to_string(i) + ": unknown mode");
+        }
+        for (uint32_t k = 0; k < D.ch.size(); ++k) {
+            const gk_precision e = (*list)[std::min(k, n - 1)];
+            DisplayOut::Ch& h = D.ch[k];
+            if (!e.prec) continue;
+            if (h.prec0 > 16 || !h.prec0)
+                throw GkError("forced precision on channel " + std::to_string(k) + " of " + std::to_string(h.prec0) +
+                              " bits: a channel must have 1..16 bits");
+            const uint32_t p = e.prec, q = h.prec0;
+            h.prec = p;
+            if (p != q) D.forced = true;
+            if (e.mode == GK_PREC_CLIP) {
+                if (p < q) {
+                    h.op = GK_PIX_CLAMP;
+                    h.lo = h.sgnd ? -(int32_t)(1u << (p - 1)) : 0;
+                    h.hi = h.sgnd ? (int32_t)(1u << (p - 1)) - 1 : (int32_t)((1u << p) - 1);
+                }
+            } else if (p > q) {   // scale_component: one float32 quotient, taken here
+                const uint32_t new_max = h.sgnd ? 1u << (p - 1) : (1u << p) - 1;
+                const uint32_t old_max = h.sgnd ? 1u << (q - 1) : (1u << q) - 1;
+                h.op = GK_PIX_SCALE;
+                h.scale = (float)new_max / (float)old_max;
+            } else if (p < q) {
+                h.op = GK_PIX_SHIFT;
+                h.shift = q - p;
+            }
+        }
+    }
+    return D;
+}
 
 }  // namespace
 
@@ -3046,6 +3136,13 @@ struct gk_ctx {
     // decode_display (which needs every tile as well)
     uint32_t dec_display = 0;
     bool disp_inner = false;
+    // gk_set_decode_precision's list; out_inner: the call in progress is the planar decode under
+    // decode_output (display flags and colour boxes still apply to it, GK_DISPLAY_FORCE_RGB and
+    // the list do not); pix: the call in progress is a pixel call and this is its destination
+    std::vector<gk_precision> dec_prec;
+    bool out_inner = false;
+    struct PixDst { void* pixels; size_t row_bytes; };
+    const PixDst* pix = nullptr;
     DisplayOut hdr_disp;       // what the flags make of the last gk_decode_header's channels
     Jp2Colour hdr_col;         // the last gk_decode_header's colour boxes and output channels
     ColourOut hdr_out;
@@ -3083,6 +3180,7 @@ struct gk_ctx {
     HostBuf hinfo, hseg, hhdr, hpasses, hord, hweight, hord_enc;
     DevBuf dstage1, dstage2;   // decode: batched tile-part / packet header fetches (device input)
     DevBuf dcol_src, dcol_out, dcol_tab;   // palette stage: index / component planes, host-bound output, tables
+    DevBuf dpix_src, dpix_out;             // output stage: its planar input, host-bound output
     HostBuf hstage1, hstage2;
     int16_t* nmse_tab = nullptr;   // device copy of the nmsedec tables (4 x 128)
     hipEvent_t ev[32];
@@ -4949,6 +5047,137 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
     const float ms = ev_ms(ctx, 20, 21);   // the display pass counts as sample stage
     ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
 }
+// The output stage (DisplayOut::out_active, and every pixel call): the image is decoded as the
+// display flags and colour boxes make it (GK_DISPLAY_FORCE_RGB and the precision list set aside)
+// into engine-owned planes of the narrowest sample type, and k_pixels (gk_pixels.hip) reads them
+// once: forced precision, grey to RGB, and either packed pixels or, one launch per channel, the
+// caller's planes.  An image that needs no conversion, upsampling or palette is decoded straight
+// into those planes (one pass after the decode); the others go through their kernel first (two).
+static void decode_output(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
+                          const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
+                          const DisplayOut& D, const Plan& W) {
+    struct Inner {
+        gk_ctx* c; const gk_ctx::PixDst* pix;
+        Inner(gk_ctx* c_) : c(c_), pix(c_->pix) { c->out_inner = true; c->pix = nullptr; }
+        ~Inner() { c->out_inner = false; c->pix = pix; }
+    };
+    hipStream_t st = ctx->st;
+    const gk_ctx::PixDst* pix = ctx->pix;
+    const uint32_t nout = (uint32_t)D.ch.size(), nst = D.nstage;
+    const uint32_t red = D.upsampled ? 0 : ctx->dec_reduce;
+    // every refusal first: nothing is allocated or launched before the call is known to be sound
+    if (win && (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h)) throw GkError("bad decode window");
+    bool any_signed = false, all_signed = true;
+    for (const auto& h : D.ch) { any_signed = any_signed || h.sgnd; all_signed = all_signed && h.sgnd; }
+    const uint32_t oprec = D.max_prec();
+    if (sample_bytes == 1 || sample_bytes == 2) {
+        if (sample_bytes != (oprec + 7) / 8)
+            throw GkError("output: sample_bytes " + std::to_string(sample_bytes) + " for an output precision of " + std::to_string(oprec) +
+                          " bits: use (precision + 7) / 8-byte or int32 samples");
+        if (any_signed && !all_signed) throw GkError("output: 8 / 16-bit samples need one sign (sample_bytes): use int32 samples");
+    } else if (sample_bytes != 0 && sample_bytes != 4) {
+        throw GkError("output: sample_bytes must be 4 or (prec + 7) / 8");
+    }
+    const int dtype = sample_bytes == 1 ? GK_U8 : sample_bytes == 2 ? GK_U16 : GK_S32;
+    const size_t es_out = gk_sample_size(dtype);
+    // the stage's channels (those the inner decode writes) and their planes
+    std::vector<uint32_t> sw(nst), sh(nst), sstr(nst), sprec(nst, 0);
+    bool st_signed = false;
+    for (const auto& h : D.ch) {
+        comp_dims(W, h.dx, h.dy, red, win, sw[h.from], sh[h.from]);
+        sprec[h.from] = h.prec0;
+        st_signed = st_signed || h.sgnd;
+    }
+    for (uint32_t j = 0; j < nst; ++j)
+        if (!sw[j] || !sh[j]) throw GkError(win ? "the window is empty at this reduction" : "output: a channel without samples in this area");
+    if (pix) {
+        if (nout > GK_PIX_MAX_CH)
+            throw GkError("pixels: " + std::to_string(nout) + " output channels (at most " + std::to_string(GK_PIX_MAX_CH) +
+                          "): use the planar calls gk_decode / gk_decode_window");
+        for (uint32_t j = 1; j < nst; ++j)
+            if (sw[j] != sw[0] || sh[j] != sh[0])
+                throw GkError("pixels: output channels of different sizes (subsampled components): set GK_DISPLAY_UPSAMPLE");
+        const size_t need = (size_t)sw[0] * nout * es_out;
+        if (pix->row_bytes < need)
+            throw GkError("pixels: row_bytes " + std::to_string(pix->row_bytes) + " is below w * C * es = " + std::to_string(need));
+        if (pix->row_bytes % es_out) throw GkError("pixels: row_bytes must be a multiple of the sample size");
+        if (out_on_device && ((uintptr_t)pix->pixels % es_out)) throw GkError("pixels: the buffer is not aligned to its sample size");
+    }
+    uint32_t smax = 0;
+    for (uint32_t j = 0; j < nst; ++j) smax = std::max(smax, sprec[j]);
+    const uint32_t sb_in = (!st_signed && smax <= 16) ? (smax + 7) / 8 : 4;
+    const int stype = sb_in == 1 ? GK_U8 : sb_in == 2 ? GK_U16 : GK_S32;
+    const size_t es_in = gk_sample_size(stype);
+    std::vector<size_t> soff(nst);
+    size_t total = 0;
+    for (uint32_t j = 0; j < nst; ++j) {
+        sstr[j] = (sw[j] + 15) & ~15u;   // rows aligned for the kernel's vector loads
+        soff[j] = total;
+        total += (((size_t)sstr[j] * sh[j] * es_in) + 255) & ~(size_t)255;
+    }
+    uint8_t* src = (uint8_t*)ctx->dpix_src.get(total);
+    {
+        std::vector<void*> cp(nst);
+        for (uint32_t j = 0; j < nst; ++j) cp[j] = src + soff[j];
+        Inner in(ctx);
+        decode_impl(ctx, cs, len, cs_on_device, cp.data(), sstr.data(), sb_in == 4 ? 0 : sb_in, 1, win, nullptr);
+    }
+    auto chan = [&](uint32_t k) {
+        const DisplayOut::Ch& h = D.ch[k];
+        GkPixChan c{};
+        c.src = src + soff[h.from]; c.ss = sstr[h.from];
+        c.op = h.op; c.lo = h.lo; c.hi = h.hi; c.scale = h.scale; c.shift = h.shift;
+        return c;
+    };
+    HIPCHK(hipEventRecord(ctx->ev[22], st));
+    if (pix) {
+        const uint32_t ow = sw[0], oh = sh[0];
+        const size_t tight = (size_t)ow * nout * es_out, pitch = (tight + 15) & ~(size_t)15;
+        GkPixArgs a{};
+        for (uint32_t k = 0; k < nout; ++k) {
+            a.ch[k] = chan(k);
+            a.ch[k].same_prev = k > 0 && D.ch[k].from == D.ch[k - 1].from;
+        }
+        a.w = ow; a.h = oh; a.nch = nout;
+        if (out_on_device) { a.dst = pix->pixels; a.row_bytes = pix->row_bytes; }
+        else { a.dst = ctx->dpix_out.get(pitch * oh); a.row_bytes = pitch; }
+        gk_launch_pixels(st, stype, dtype, a);
+        launch_check(__LINE__);
+        HIPCHK(hipEventRecord(ctx->ev[23], st));
+        if (!out_on_device)
+            HIPCHK(hipMemcpy2DAsync(pix->pixels, pix->row_bytes, a.dst, pitch, tight, oh, hipMemcpyDeviceToHost, st));
+    } else {   // planar: the one-channel case, launched per channel
+        std::vector<uint8_t*> dst(nout);
+        std::vector<size_t> pitch(nout);
+        if (!out_on_device) {
+            size_t tot = 0;
+            for (uint32_t k = 0; k < nout; ++k) {
+                pitch[k] = ((size_t)sw[D.ch[k].from] * es_out + 15) & ~(size_t)15;
+                tot += pitch[k] * sh[D.ch[k].from];
+            }
+            uint8_t* stage = (uint8_t*)ctx->dpix_out.get(tot);
+            for (uint32_t k = 0; k < nout; ++k) { dst[k] = stage; stage += pitch[k] * sh[D.ch[k].from]; }
+        } else {
+            for (uint32_t k = 0; k < nout; ++k) { dst[k] = (uint8_t*)comps[k]; pitch[k] = (size_t)strides[k] * es_out; }
+        }
+        for (uint32_t k = 0; k < nout; ++k) {
+            GkPixArgs a{};
+            a.ch[0] = chan(k);
+            a.w = sw[D.ch[k].from]; a.h = sh[D.ch[k].from]; a.nch = 1;
+            a.dst = dst[k]; a.row_bytes = pitch[k];
+            gk_launch_pixels(st, stype, dtype, a);
+        }
+        launch_check(__LINE__);
+        HIPCHK(hipEventRecord(ctx->ev[23], st));
+        if (!out_on_device)
+            for (uint32_t k = 0; k < nout; ++k)
+                HIPCHK(hipMemcpy2DAsync(comps[k], (size_t)strides[k] * es_out, dst[k], pitch[k], (size_t)sw[D.ch[k].from] * es_out,
+                                        sh[D.ch[k].from], hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    const float ms = ev_ms(ctx, 22, 23);   // the output pass counts as sample stage, as the display pass does
+    ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+}
 static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
                         const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win = nullptr,
                         const TilePass* pass = nullptr) {
@@ -4973,7 +5202,7 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     Jp2Colour col;
     {
         size_t joff = 0, jlen = 0;
-        const bool colour = (ctx->dec_colour || ctx->dec_display) && !ctx->col_inner && !pass;
+        const bool colour = (ctx->dec_colour || ctx->dec_display || !ctx->dec_prec.empty() || ctx->pix) && !ctx->col_inner && !pass;
         if (jp2_locate(S, joff, jlen, colour ? &col : nullptr)) {   // JP2 file: decode its codestream box
             cs += joff; len = jlen;
             S = ByteSrc(); S.len = len; S.st = st;
@@ -4982,11 +5211,18 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     }
     Header Hd;
     parse_header(S, Hd);
-    if (ctx->dec_display && !ctx->col_inner && !pass) {   // display flags: a conversion or an upsampling that applies
+    // (under decode_output the flags that belong to the output stage are set aside)
+    const uint32_t dflags = ctx->out_inner ? ctx->dec_display & ~GK_DISPLAY_FORCE_RGB : ctx->dec_display;
+    const bool out_stage = !ctx->out_inner && (ctx->pix || !ctx->dec_prec.empty());
+    if ((dflags || out_stage) && !ctx->col_inner && !pass) {   // display flags, a precision list, a pixel call
         const Jp2Colour none;
         const ColourOut co = resolve_colour(ctx->dec_colour ? col : none, Hd.want);
-        const DisplayOut D = resolve_display(col, co, Hd.want, ctx->dec_display, ctx->dec_reduce, win);
-        if (D.active()) {
+        const DisplayOut D = resolve_display(col, co, Hd.want, dflags, ctx->dec_reduce, win, out_stage ? &ctx->dec_prec : nullptr);
+        if (ctx->pix || D.out_active()) {   // forced precision, grey to RGB, packed pixels
+            decode_output(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, D, Hd.want);
+            return;
+        }
+        if (D.active()) {   // a conversion or an upsampling that applies
             decode_display(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, D, Hd.want);
             return;
         }
@@ -5046,8 +5282,10 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
         }
     }
     merge_tile_parts(Hd);
-    if (ctx->col_whole && !win && !pass && Hd.parts.size() != P.tiles.size())
-        throw GkError(ctx->disp_inner ? "display flags (gk_set_decode_display) on a stream that holds only some of its tiles "
+    if ((ctx->col_whole || ctx->out_inner) && !win && !pass && Hd.parts.size() != P.tiles.size())
+        throw GkError(!ctx->col_whole ? "the output stage (pixel calls, forced precision, grey to RGB) on a stream that holds only some of "
+                                        "its tiles (sharded / tile-range decode) is not supported"
+                      : ctx->disp_inner ?"display flags (gk_set_decode_display) on a stream that holds only some of its tiles "
                                         "(sharded / tile-range decode) are not supported"
                                       : "a palette (pclr / cmap boxes) on a stream that holds only some of its tiles is not supported");
     if (pass) {
@@ -6189,7 +6427,7 @@ static void fill_image_info(gk_image_info* info, const Header& Hd, const ColourO
     if (out.active()) {   // the output channels: their count, the widest precision, channel 0's sign
         info->numcomps = (uint32_t)out.ch.size(); info->prec = out.max_prec(); info->sgnd = out.ch[0].sgnd;
     }
-    if (disp && disp->applied()) {   // ... after the display stage
+    if (disp && (disp->applied() || disp->forced)) {   // ... after the display and output stages
         info->numcomps = (uint32_t)disp->ch.size(); info->prec = disp->max_prec(); info->sgnd = disp->ch[0].sgnd;
     }
 }
@@ -6231,7 +6469,7 @@ int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
         ColourOut out;
         read_header_colour(S, cs, cs_on_device != 0, ctx->dec_colour, Hd, col, out);
         // (display flags: the whole image's output; a refusal that depends on a window is the decode's)
-        DisplayOut disp = resolve_display(col, out, Hd.want, ctx->dec_display, ctx->dec_reduce, nullptr);
+        DisplayOut disp = resolve_display(col, out, Hd.want, ctx->dec_display, ctx->dec_reduce, nullptr, &ctx->dec_prec);
         fill_image_info(info, Hd, out, &disp);
         const uint32_t n = (uint32_t)disp.ch.size();
         ctx->hdr_dx.assign(n, 1); ctx->hdr_dy.assign(n, 1);
@@ -6252,7 +6490,7 @@ int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
 int gk_header_colour(gk_ctx* ctx, gk_colour_info* ci) {
     if (!ctx || !ci) return -1;
     if (!ctx->hdr_ncs) { ctx->err = "gk_header_colour: no header has been read"; return -1; }
-    fill_colour_info(ci, ctx->hdr_col, ctx->hdr_out, ctx->hdr_ncs, ctx->dec_display ? &ctx->hdr_disp : nullptr);
+    fill_colour_info(ci, ctx->hdr_col, ctx->hdr_out, ctx->hdr_ncs, ctx->dec_display ? &ctx->hdr_disp : nullptr);   // (a list changes nothing here)
     return 0;
 }
 
@@ -6273,17 +6511,32 @@ int gk_set_decode_colour(gk_ctx* ctx, int apply) {
 
 int gk_set_decode_display(gk_ctx* ctx, uint32_t flags) {
     if (!ctx) return -1;
-    if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE)) { ctx->err = "gk_set_decode_display: unknown flags"; return -1; }
+    if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB)) { ctx->err = "gk_set_decode_display: unknown flags"; return -1; }
     ctx->dec_display = flags;
+    return 0;
+}
+
+int gk_set_decode_precision(gk_ctx* ctx, const gk_precision* list, uint32_t n) {
+    if (!ctx) return -1;
+    if (n && !list) { ctx->err = "gk_set_decode_precision: no list"; return -1; }
+    ctx->dec_prec.assign(list, list + n);
     return 0;
 }
 
 int gk_probe_display(const uint8_t* cs, size_t len, uint32_t flags, uint32_t reduce, gk_image_info* info,
                      gk_colour_info* colour, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd, uint32_t cap,
                      char* msg, size_t msg_cap) {
+    return gk_probe_output(cs, len, flags, reduce, nullptr, 0, info, colour, dx, dy, prec, sgnd, cap, msg, msg_cap);
+}
+
+int gk_probe_output(const uint8_t* cs, size_t len, uint32_t flags, uint32_t reduce, const gk_precision* list, uint32_t n,
+                    gk_image_info* info, gk_colour_info* colour, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd,
+                    uint32_t cap, char* msg, size_t msg_cap) {
     if (!cs) return -1;
     try {
-        if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE)) throw GkError("gk_probe_display: unknown flags");
+        if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB)) throw GkError("gk_probe_display: unknown flags");
+        if (n && !list) throw GkError("gk_probe_output: no list");
+        const std::vector<gk_precision> plist(list, list + n);
         if (reduce >= GK_MAXRLVLS) throw GkError("reduce must be less than the number of resolutions");
         ByteSrc S; S.len = len; S.host = cs;
         Header Hd;
@@ -6292,7 +6545,7 @@ int gk_probe_display(const uint8_t* cs, size_t len, uint32_t flags, uint32_t red
         read_header_colour(S, cs, false, true, Hd, col, out);
         for (uint32_t c = 0; c < Hd.want.nc; ++c)
             if (reduce >= Hd.want.p.c_numres(c)) throw GkError("reduce must be less than the number of resolutions");
-        const DisplayOut disp = resolve_display(col, out, Hd.want, flags, reduce, nullptr);
+        const DisplayOut disp = resolve_display(col, out, Hd.want, flags, reduce, nullptr, &plist);
         if (info) { fill_image_info(info, Hd, out, &disp); info->sample_bytes = 0; }
         if (colour) fill_colour_info(colour, col, out, Hd.want.nc, flags ? &disp : nullptr);
         for (uint32_t c = 0; c < disp.ch.size() && c < cap; ++c) {
@@ -6501,6 +6754,35 @@ int gk_decode_window(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
         ctx->err = e.msg;
         return -1;
     }
+}
+
+static int decode_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const uint32_t* win, void* pixels,
+                         size_t row_bytes, uint32_t sample_bytes, int out_on_device) {
+    if (!ctx || !cs || !pixels) return -1;
+    const gk_ctx::PixDst dst{pixels, row_bytes};
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
+        ctx->pix = &dst;
+        decode_impl(ctx, cs, len, cs_on_device, nullptr, nullptr, sample_bytes, out_on_device, win);
+        ctx->pix = nullptr;
+        return 0;
+    } catch (const GkError& e) {
+        ctx->pix = nullptr;
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+int gk_decode_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* pixels, size_t row_bytes,
+                     uint32_t sample_bytes, int out_on_device) {
+    return decode_pixels(ctx, cs, len, cs_on_device, nullptr, pixels, row_bytes, sample_bytes, out_on_device);
+}
+int gk_decode_window_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, uint32_t x0, uint32_t y0,
+                            uint32_t x1, uint32_t y1, void* pixels, size_t row_bytes, uint32_t sample_bytes,
+                            int out_on_device) {
+    const uint32_t win[4] = {x0, y0, x1, y1};
+    return decode_pixels(ctx, cs, len, cs_on_device, win, pixels, row_bytes, sample_bytes, out_on_device);
 }
 
 int gk_get_timings(gk_ctx* ctx, gk_timings* t) {

@@ -167,3 +167,28 @@ struct GkUpArgs {
     uint32_t rows;
 };
 void gk_launch_upsample(hipStream_t st, int stype, int dtype, const GkUpArgs& args);
+// Output stage (gk_pixels.hip): forced precision, grey to RGB and packed pixels in one pass.
+// Sample k of pixel (x, y) is written at dst + y * row_bytes + (x * nch + k) * es; a planar
+// plane is the nch = 1 case.  Source planes are the engine's own (bases and row strides aligned
+// to GK_PAL_PIX samples); dst needs its element's alignment only.
+enum GkPixOp { GK_PIX_NONE = 0, GK_PIX_CLAMP = 1, GK_PIX_SCALE = 2, GK_PIX_SHIFT = 3 };
+#define GK_PIX_MAX_CH 16
+struct GkPixChan {
+    const void* src;           // the channel's plane, row stride ss samples
+    uint32_t ss;
+    uint32_t op;               // GkPixOp
+    int32_t lo, hi;            // CLAMP
+    float scale;               // SCALE: rint((float)v * scale), one float32 product
+    uint32_t shift;            // SHIFT: v / 2^shift, truncating toward zero
+    uint32_t same_prev;        // src is the plane of the channel before this one: loaded once
+    uint32_t pad_;
+};
+struct GkPixArgs {
+    GkPixChan ch[GK_PIX_MAX_CH];
+    void* dst;
+    uint64_t row_bytes;
+    uint32_t w, h, nch;
+    uint32_t rows;             // (set by the launcher)
+};
+// stype / dtype: GK_U8, GK_U16 or GK_S32 planes in / pixels out
+void gk_launch_pixels(hipStream_t st, int stype, int dtype, const GkPixArgs& args);

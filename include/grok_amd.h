@@ -238,7 +238,8 @@ typedef struct gk_colour_info {
     uint16_t asoc[GK_MAX_CHANNELS];   /* 65535 unspecified) and Asoc (0 whole image, 1..3 colour, 65535 none);
                                          without a cdef Grok's defaults: colour 1..3, then unspecified */
     uint32_t display_applied;  /* gk_set_decode_display: GK_DISPLAY_RGB set when a conversion to RGB runs,
-                                  GK_DISPLAY_UPSAMPLE when components are upsampled (0 without flags) */
+                                  GK_DISPLAY_UPSAMPLE when components are upsampled, GK_DISPLAY_FORCE_RGB when
+                                  a grey channel is replicated (0 without flags) */
 } gk_colour_info;
 /* Colour description of host codestream / JP2 bytes, no device needed (like gk_probe_header);
  * < 0 with the reason, naming the box, in msg. */
@@ -283,6 +284,17 @@ int gk_set_decode_colour(gk_ctx* ctx, int apply);
  * (output precision + 7) / 8 bytes. */
 #define GK_DISPLAY_RGB 1u
 #define GK_DISPLAY_UPSAMPLE 2u
+/* GK_DISPLAY_FORCE_RGB (grk_decompress -f; postProcess :1444-1468, convert_gray_to_rgb,
+ * bin/common/convert.cpp:148-207), evaluated after the GK_DISPLAY_RGB conversion.  The colour-space
+ * rule of :1335-1341 (a 3-component image with subsampled chroma counts as sYCC, one of <= 2
+ * components as grey) is applied when GK_DISPLAY_RGB or GK_DISPLAY_FORCE_RGB is set.  An sRGB image
+ * is left alone.  A grey image's channel 0 becomes three channels with its dx / dy / precision /
+ * sign / typ, the remaining channels follow with their own (grey + alpha: R, G, B, A), the colour
+ * space becomes sRGB and display_applied gains this bit; the grey plane is read once by the
+ * output stage, not copied.  Every other colour space is refused by name (Grok: "don't know how to
+ * convert image to RGB colorspace"): unknown (a raw codestream of >= 3 components), sYCC or CMYK
+ * left unconverted (add GK_DISPLAY_RGB), e-sYCC, ICC, CIELab. */
+#define GK_DISPLAY_FORCE_RGB 4u
 int gk_set_decode_display(gk_ctx* ctx, uint32_t flags);
 /* What a decode of host codestream / JP2 bytes under `flags` and `reduce` returns, no device
  * needed: the image info and colour description of the output (either may be NULL), dx / dy /
@@ -292,6 +304,53 @@ int gk_set_decode_display(gk_ctx* ctx, uint32_t flags);
 int gk_probe_display(const uint8_t* cs, size_t len, uint32_t flags, uint32_t reduce, gk_image_info* info,
                      gk_colour_info* colour, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd, uint32_t cap,
                      char* msg, size_t msg_cap);
+
+/* Forced output precision (grk_decompress -p; postProcess :1469-1494, grk_precision /
+ * grk_precision_mode).  Sticky; n = 0 clears the list.  Output channel k (counted after the colour
+ * boxes, the conversion and grey to RGB) takes entry min(k, n - 1); prec = 0 keeps the channel's
+ * precision; the channel's reported precision becomes the forced one.
+ * GK_PREC_SCALE is scale_component (bin/common/convert.cpp:96-146): equal precisions untouched;
+ * up: lrintf((float)v * scale), scale = (float)newMax / (float)oldMax a float32 quotient taken on
+ * the host, max = 2^p - 1 unsigned, 2^(p - 1) signed; down: C division by 2^(old - new), truncating
+ * toward zero.
+ * GK_PREC_CLIP clamps to the forced precision's range with the channel's sign, [0, 2^p - 1] or
+ * [-2^(p - 1), 2^(p - 1) - 1] (Grok's clip<T>, :1476-1486, clamps to the limits of the 32-bit type
+ * and so changes no sample: DESIGN.md R-BUG-11).
+ * Entries are 0..16 and a channel that gets a forced precision must itself be <= 16 bits (the
+ * CLI's limit :1249-1258); otherwise the header and decode calls refuse, naming the channel,
+ * before anything is allocated or launched.  The list applies to gk_decode / gk_decode_window
+ * (planar) and to the pixel calls; the header calls describe the output, and the plane-size rule
+ * (8 / 16-bit planes of (widest output precision + 7) / 8 bytes) follows the forced precision. */
+#define GK_PREC_CLIP 0u    /* GRK_PREC_MODE_CLIP */
+#define GK_PREC_SCALE 1u   /* GRK_PREC_MODE_SCALE */
+typedef struct gk_precision {
+    uint8_t prec;
+    uint8_t mode;
+} gk_precision;
+int gk_set_decode_precision(gk_ctx* ctx, const gk_precision* list, uint32_t n);
+
+/* gk_probe_display with a precision list: what a decode under `flags`, `reduce` and the list
+ * returns, no device needed.  n = 0: what gk_probe_display reports. */
+int gk_probe_output(const uint8_t* cs, size_t len, uint32_t flags, uint32_t reduce, const gk_precision* list,
+                    uint32_t n, gk_image_info* info, gk_colour_info* colour, uint32_t* dx, uint32_t* dy, uint32_t* prec,
+                    uint32_t* sgnd, uint32_t cap, char* msg, size_t msg_cap);
+
+/* Decode to packed pixels: the image Grok's image writers are handed after postProcess
+ * (interleaving as in bin/image_format, e.g. PNGFormat / TIFFFormat's planar-to-interleaved
+ * pass), written by the device.  Sample k of pixel (x, y) lies at
+ * pixels + y * row_bytes + (x * C + k) * es; C is the output channel count the header calls report,
+ * es = sample_bytes (0 or 4: int32; 1 / 2: (widest output precision + 7) / 8, one sign).  Row bytes
+ * past w * C * es are never written.  Every sticky setting is honoured (layers, reduce, colour
+ * boxes, display flags, precision list, window rule).  Refused, each by name: output channels of
+ * different sizes (subsampled components without GK_DISPLAY_UPSAMPLE); a sample_bytes that breaks
+ * the rule or mixes signs in 8 / 16 bits; row_bytes below w * C * es or no multiple of es; more
+ * than 16 output channels (use the planar calls); a stream that holds only some of its tiles. */
+int gk_decode_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* pixels, size_t row_bytes,
+                     uint32_t sample_bytes, int out_on_device);
+/* The same for the window [x0, x1) x [y0, y1) (gk_decode_window): pixels addresses sample (x0, y0). */
+int gk_decode_window_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, uint32_t x0, uint32_t y0,
+                            uint32_t x1, uint32_t y1, void* pixels, size_t row_bytes, uint32_t sample_bytes,
+                            int out_on_device);
 
 /* Inverse 5/3 rule of later gk_decode_window calls.  whole_tile = 0 (default): Grok's partial-tile
  * inverse, which a window set through setDecompressWindow selects for every tile
