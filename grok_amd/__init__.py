@@ -27,7 +27,8 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_set_window_rule", "gk_set_subsampling", "gk_probe_components", "gk_header_components",
            "gk_probe_colour", "gk_header_colour", "gk_header_icc", "gk_set_decode_colour", "gk_probe_icc",
            "gk_probe_stream_components", "gk_set_decode_display", "gk_probe_display", "gk_set_decode_precision",
-           "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels")
+           "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels", "gk_encode_pixels",
+           "gk_set_encode_colour", "gk_jp2_boxes")
 GK_MAX_CHANNELS = 256
 GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB = 1, 2, 4   # gk_set_decode_display flags
 GK_PREC_CLIP, GK_PREC_SCALE = 0, 1   # gk_precision::mode (grk_precision_mode)
@@ -135,6 +136,92 @@ class ColourInfo(ctypes.Structure):
 _lib = None
 
 
+class CmapEntry(ctypes.Structure):
+    """gk_cmap_entry"""
+    _fields_ = [("component", ctypes.c_uint16), ("mapping_type", ctypes.c_uint8), ("palette_column", ctypes.c_uint8)]
+
+
+class EncodeColour(ctypes.Structure):
+    """gk_encode_colour"""
+    _fields_ = [("colour_space", ctypes.c_uint32), ("icc", ctypes.c_void_p), ("icc_len", ctypes.c_uint32),
+                ("num_channels", ctypes.c_uint32), ("typ", ctypes.POINTER(ctypes.c_uint16)),
+                ("asoc", ctypes.POINTER(ctypes.c_uint16)), ("palette_entries", ctypes.c_uint32),
+                ("palette_columns", ctypes.c_uint32), ("channel_prec", ctypes.POINTER(ctypes.c_uint8)),
+                ("lut", ctypes.POINTER(ctypes.c_int32)), ("cmap", ctypes.POINTER(CmapEntry))]
+
+
+# GRK_COLOR_SPACE by name (gk_encode_colour::colour_space)
+COLOUR_SPACES = {"srgb": 2, "grey": 3, "gray": 3, "sycc": 4, "esycc": 5, "eycc": 5, "cmyk": 6, "cie": 7, "icc": 9}
+
+
+def _encode_colour(space=None, icc=None, channels=None, palette=None):
+    """gk_encode_colour of the Python arguments (set_encode_colour / jp2_boxes), or None when all are
+    None.  space: a GRK_COLOR_SPACE value or a name of COLOUR_SPACES (default: "icc" with a profile);
+    channels: [(typ, asoc)] per component; palette: (lut (NE, NPC), column precisions,
+    [(component, mapping type, palette column)])."""
+    if space is None and icc is None and channels is None and palette is None:
+        return None
+    e = EncodeColour()
+    if space is None:
+        space = "icc" if icc is not None else 0
+    if isinstance(space, str):
+        if space.lower() not in COLOUR_SPACES:
+            raise ValueError("colour_space: unknown colour space name %r" % space)
+        space = COLOUR_SPACES[space.lower()]
+    e.colour_space = int(space)
+    keep = []
+    if icc is not None:
+        b = (ctypes.c_uint8 * max(len(icc), 1)).from_buffer_copy(bytes(icc) or b"\0")
+        keep.append(b)
+        e.icc, e.icc_len = ctypes.cast(b, ctypes.c_void_p), len(icc)
+    if channels is not None:
+        n = len(channels)
+        t = (ctypes.c_uint16 * max(n, 1))(*[int(c[0]) for c in channels])
+        a = (ctypes.c_uint16 * max(n, 1))(*[int(c[1]) for c in channels])
+        keep += [t, a]
+        e.num_channels, e.typ, e.asoc = n, t, a
+    if palette is not None:
+        lut, precs, cm = palette
+        lut = np.asarray(lut)
+        if lut.ndim != 2 or lut.shape[1] != len(precs) or len(cm) != len(precs):
+            raise ValueError("pclr / cmap: the LUT is (NE, NPC), with NPC column precisions and NPC cmap entries")
+        if lut.size and (lut.min() < -(1 << 31) or lut.max() >= (1 << 31)):
+            raise ValueError("pclr box: a LUT value does not fit 32 bits")
+        if any(not 0 <= int(p) <= 255 for p in precs) or any(not (0 <= c <= 65535 and 0 <= m <= 255 and 0 <= k <= 255) for c, m, k in cm):
+            raise ValueError("pclr / cmap: column precisions, MTYP and PCOL are bytes, CMP 16 bits")
+        l32 = np.ascontiguousarray(lut, dtype=np.int32)
+        pr = (ctypes.c_uint8 * max(len(precs), 1))(*[int(x) for x in precs])
+        ce = (CmapEntry * max(len(cm), 1))(*[CmapEntry(int(c), int(m), int(k)) for c, m, k in cm])
+        keep += [l32, pr, ce]
+        e.palette_entries, e.palette_columns = lut.shape
+        e.channel_prec, e.lut, e.cmap = pr, l32.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ce
+    e._keep = keep
+    return e
+
+
+def jp2_boxes(shape, prec, cs_len, signed=False, space=None, icc=None, channels=None, palette=None):
+    """gk_jp2_boxes: the JP2 boxes in front of a codestream of cs_len bytes for an image of
+    shape = (C, H, W), no device needed; file = these bytes + the codestream.  The colour
+    arguments are Engine.set_encode_colour's; without them ihdr and the default colr
+    (Engine.jp2_header's bytes).  A refusal raises ValueError with the engine's message."""
+    lib = load_library()
+    c, h, w = shape
+    info = ImageInfo(w, h, c, prec, int(signed), 0)
+    e = _encode_colour(space, icc, channels, palette)
+    msg = ctypes.create_string_buffer(512)
+    n = ctypes.c_size_t()
+    buf = np.empty(4096, np.uint8)
+    for _ in range(2):
+        rc = lib.gk_jp2_boxes(ctypes.byref(info), ctypes.byref(e) if e is not None else None, cs_len, buf.ctypes.data, buf.size,
+                              ctypes.byref(n), msg, len(msg))
+        if rc != -2:
+            break
+        buf = np.empty(n.value, np.uint8)
+    if rc != 0:
+        raise ValueError("gk_jp2_boxes: " + msg.value.decode())
+    return buf[:n.value].tobytes()
+
+
 def load_library(build_if_missing=True):
     """Load the in-tree HIP extension (built by grok_amd.build / __graft_entry__.build)."""
     global _lib
@@ -213,6 +300,14 @@ def load_library(build_if_missing=True):
     lib.gk_decode_window_pixels.restype = ctypes.c_int
     lib.gk_decode_window_pixels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] + \
         [ctypes.c_uint32] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int]
+    lib.gk_encode_pixels.restype = ctypes.c_int
+    lib.gk_encode_pixels.argtypes = [ctypes.c_void_p, P(ImageInfo), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                                     P(CParameters), ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), ctypes.c_int]
+    lib.gk_set_encode_colour.restype = ctypes.c_int
+    lib.gk_set_encode_colour.argtypes = [ctypes.c_void_p, P(EncodeColour)]
+    lib.gk_jp2_boxes.restype = ctypes.c_int
+    lib.gk_jp2_boxes.argtypes = [P(ImageInfo), P(EncodeColour), ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t,
+                                 P(ctypes.c_size_t), ctypes.c_char_p, ctypes.c_size_t]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -516,6 +611,77 @@ class Engine:
             self._err("gk_encode")
         return buf[:n.value].tobytes()
 
+    def set_encode_colour(self, space=None, icc=None, channels=None, palette=None):
+        """gk_set_encode_colour (sticky): the colour description later JP2 encodes and jp2_header write
+        (colr, cdef, pclr + cmap), as _encode_colour reads the arguments; no argument clears it.  sYCC
+        and e-sYCC also clear the MCT of later encodes, raw codestreams included.  A refusal raises
+        ValueError and leaves the engine with no description."""
+        e = _encode_colour(space, icc, channels, palette)
+        if self.lib.gk_set_encode_colour(self.ctx, ctypes.byref(e) if e is not None else None) != 0:
+            raise ValueError("gk_set_encode_colour: " + self.lib.gk_last_error(self.ctx).decode())
+
+    def encode_pixels(self, pixels, prec, signed=False, params=None, out=None, origin=None):
+        """gk_encode_pixels: encode packed pixels.  pixels: an (H, W, C) or (H, W) numpy array (host)
+        or torch cuda tensor (device) with stride(2) == 1, stride(1) == C and any row stride; its
+        element size selects the sample type (4 bytes: int32; 1 / 2 bytes must be (prec + 7) // 8; a
+        host array of another type is converted to int32 by value, as ``encode`` converts planes; a
+        device tensor of a non-integer type is refused).  The result is the codestream
+        ``encode`` writes for the same samples in (C, H, W) planes; params, out and origin as there."""
+        if params is None:
+            params = default_params()
+        on_dev = _is_torch_cuda(pixels)
+        if on_dev:   # (a device tensor is read as it lies: its bits must be integer samples)
+            if pixels.dtype.is_floating_point or pixels.dtype.is_complex or str(pixels.dtype) == "torch.bool" or \
+                    pixels.element_size() not in (1, 2, 4):
+                raise ValueError("encode_pixels needs a device tensor of 8-, 16- or 32-bit integers, not %s" % pixels.dtype)
+        else:
+            pixels = np.asarray(pixels)
+            if not (pixels.dtype.kind in "ui" and pixels.dtype.itemsize in (1, 2, 4)) or \
+                    (pixels.dtype.itemsize < 4 and pixels.dtype.itemsize != (prec + 7) // 8):
+                pixels = np.ascontiguousarray(pixels, dtype=np.int32)
+        if pixels.ndim == 2:
+            pixels = pixels[:, :, None]
+        h, w, c = pixels.shape
+        es = pixels.element_size() if on_dev else pixels.dtype.itemsize
+        if on_dev:
+            st = [pixels.stride(i) for i in range(3)]
+            base = pixels.data_ptr()
+        else:
+            if any(s % es for s in pixels.strides):
+                pixels = np.ascontiguousarray(pixels)
+            st = [s // es for s in pixels.strides]
+            base = pixels.ctypes.data
+        if (c > 1 and st[2] != 1) or (w > 1 and st[1] != c) or (h > 1 and st[0] < w * c):
+            if on_dev:
+                raise ValueError("encode_pixels needs stride(2) == 1, stride(1) == C and a row stride of at least W * C")
+            pixels = np.ascontiguousarray(pixels)
+            st, base = [w * c, c, 1], pixels.ctypes.data
+        row_bytes = (st[0] if h > 1 else w * c) * es
+        info = ImageInfo(w, h, c, prec, int(signed), 0 if es == 4 else es)
+        if origin is not None:
+            info.x0, info.y0 = int(origin[0]), int(origin[1])
+        else:
+            info.x0, info.y0 = params.tx0, params.ty0
+        n = ctypes.c_size_t()
+        src = ctypes.c_void_p(base)
+        if out is not None:
+            rc = self.lib.gk_encode_pixels(self.ctx, ctypes.byref(info), src, row_bytes, int(on_dev), ctypes.byref(params),
+                                           ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(n), 1)
+            if rc != 0:
+                self._err("gk_encode_pixels")
+            return n.value
+        cap = c * h * w * 4 + (1 << 20)
+        buf = np.empty(cap, np.uint8)
+        rc = self.lib.gk_encode_pixels(self.ctx, ctypes.byref(info), src, row_bytes, int(on_dev), ctypes.byref(params),
+                                       buf.ctypes.data, cap, ctypes.byref(n), 0)
+        if rc == -2:
+            buf = np.empty(n.value, np.uint8)
+            rc = self.lib.gk_encode_pixels(self.ctx, ctypes.byref(info), src, row_bytes, int(on_dev), ctypes.byref(params),
+                                           buf.ctypes.data, n.value, ctypes.byref(n), 0)
+        if rc != 0:
+            self._err("gk_encode_pixels")
+        return buf[:n.value].tobytes()
+
     def _encode_subsampled(self, planes, prec, signed, params, out, origin, subsampling, size):
         c = len(planes)
         w, h = size
@@ -648,7 +814,11 @@ class Engine:
         info = ImageInfo(w, h, c, prec, int(signed), 0)
         buf = np.empty(256, np.uint8)
         n = ctypes.c_size_t()
-        if self.lib.gk_jp2_header(self.ctx, ctypes.byref(info), cs_len, buf.ctypes.data, buf.size, ctypes.byref(n)) != 0:
+        rc = self.lib.gk_jp2_header(self.ctx, ctypes.byref(info), cs_len, buf.ctypes.data, buf.size, ctypes.byref(n))
+        if rc == -2:   # (a colour description set by set_encode_colour: an ICC profile, a palette)
+            buf = np.empty(n.value, np.uint8)
+            rc = self.lib.gk_jp2_header(self.ctx, ctypes.byref(info), cs_len, buf.ctypes.data, buf.size, ctypes.byref(n))
+        if rc != 0:
             self._err("gk_jp2_header")
         return buf[:n.value].tobytes()
 

@@ -2574,17 +2574,126 @@ static const uint32_t BOX_JP = 0x6a502020, BOX_FTYP = 0x66747970, BOX_JP2H = 0x6
 static bool jp2_needs_xl(const Plan& P) {
     return (uint64_t)P.nc * P.w * P.h * ((P.prec + 7) / 8) > (1ull << 30);
 }
-static size_t jp2_prefix_size(const Plan& P) { return 12 + 20 + 45 + (jp2_needs_xl(P) ? 16 : 8); }
-// signature, file type, JP2 header (ihdr + colr) and the jp2c box header for a codestream of cs_len bytes
-static void write_jp2_prefix(std::vector<uint8_t>& o, const Plan& P, uint64_t cs_len) {
-    put32(o, 12); put32(o, BOX_JP); put32(o, 0x0d0a870a);
-    put32(o, 20); put32(o, BOX_FTYP); put32(o, BRAND_JP2); put32(o, 0); put32(o, BRAND_JP2);
-    put32(o, 8 + 22 + 15); put32(o, BOX_JP2H);
+static const uint32_t BOX_BPCC = 0x62706363, BOX_PCLR = 0x70636c72, BOX_CMAP = 0x636d6170, BOX_CDEF = 0x63646566;
+// gk_set_encode_colour's description, copied in: what FileFormatCompress::initCompress (:694-909)
+// takes from the grk_image (colour space, ICC profile, component types / associations, palette)
+struct EncColour {
+    bool set = false;
+    uint32_t space = 0;
+    std::vector<uint8_t> icc;
+    std::vector<uint16_t> typ, asoc;   // per component (empty: every component is colour)
+    bool palette = false;
+    uint32_t ne = 0, npc = 0;
+    std::vector<uint8_t> pprec;
+    std::vector<int32_t> lut;          // ne rows of npc columns
+    struct Map { uint16_t cmp; uint8_t mtyp, pcol; };
+    std::vector<Map> cmap;
+    bool clears_mct() const { return set && (space == 4 || space == 5); }   // sYCC / e-sYCC (CodeStreamCompress.cpp:494-500)
+};
+static void enc_colour_validate(const std::vector<uint8_t>& jp2h, const Plan& P);
+// What no image can make valid (gk_set_encode_colour refuses it at once).  Returns the colr EnumCS
+// (0: METH 2) and sets initCompress's color_channels (:823-839).
+static uint32_t enc_colour_check(const EncColour& E, uint32_t& colour_channels) {
+    uint32_t enumcs = 0;
+    colour_channels = 0;
+    switch (E.space) {
+        case 2: enumcs = 16; colour_channels = 3; break;   // sRGB
+        case 3: enumcs = 17; colour_channels = 1; break;   // grey
+        case 4: enumcs = 18; colour_channels = 3; break;   // sYCC
+        case 5: enumcs = 24; colour_channels = 3; break;   // e-sYCC
+        case 6: enumcs = 12; colour_channels = 4; break;   // CMYK
+        case 9: break;                                     // ICC: METH 2
+        case 7: throw GkError("colour_space: GRK_CLRSPC_DEFAULT_CIE (colr EnumCS 14, CIELab) is not supported");
+        default: throw GkError("colour_space: unsupported colour space enumeration " + std::to_string(E.space));
+    }
+    if (E.space == 9 && E.icc.empty()) throw GkError("icc: GRK_CLRSPC_ICC needs a profile");
+    // (every LBox is 32 bits: the profile leaves room for the largest palette and the other boxes)
+    if (E.icc.size() > 0xff000000u) throw GkError("icc: a profile of " + std::to_string(E.icc.size()) + " bytes does not fit a JP2 box");
+    if (E.space != 9 && !E.icc.empty()) throw GkError("icc: a profile is written only with GRK_CLRSPC_ICC (colr METH 2)");
+    if (E.palette) {
+        if (E.ne == 0 || E.ne > 1024) throw GkError("pclr box: " + std::to_string(E.ne) + " palette entries (NE must be 1..1024)");
+        if (E.npc == 0) throw GkError("pclr box: no palette columns (NPC 0)");
+        if (E.npc > 255) throw GkError("pclr box: " + std::to_string(E.npc) + " palette columns (NPC is one byte)");
+        for (uint32_t i = 0; i < E.npc; ++i)
+            if (E.pprec[i] == 0 || E.pprec[i] > 16)
+                throw GkError("pclr box: column precision " + std::to_string(E.pprec[i]) + " must be 1..16 bits (Grok's limit)");
+        for (uint32_t j = 0; j < E.ne; ++j)
+            for (uint32_t i = 0; i < E.npc; ++i) {
+                const int32_t v = E.lut[(size_t)j * E.npc + i];
+                if (v < 0 || v >= (1 << E.pprec[i]))
+                    throw GkError("pclr box: LUT value " + std::to_string(v) + " of entry " + std::to_string(j) + " is outside its " +
+                                  std::to_string(E.pprec[i]) + "-bit column " + std::to_string(i));
+            }
+        for (uint32_t i = 0; i < E.npc; ++i)
+            if (E.cmap[i].mtyp > 1)
+                throw GkError("cmap box: mapping type " + std::to_string(E.cmap[i].mtyp) + " of channel " + std::to_string(i) + " (MTYP must be 0 or 1)");
+    }
+    return enumcs;
+}
+// The contents of the jp2h box in write_jp2h's order (:176-264): ihdr, colr, [cdef], [pclr, cmap].
+// Without a description: ihdr and the greyscale / sRGB colr.  What Grok would refuse, write past
+// its arrays for, or the engine's own reader would refuse, is refused by name.
+static std::vector<uint8_t> jp2h_content(const Plan& P, const EncColour* ec) {
+    std::vector<uint8_t> o;
     put32(o, 22); put32(o, BOX_IHDR); put32(o, P.h); put32(o, P.w); put16(o, P.nc);
     o.push_back((uint8_t)((P.prec - 1) | (P.sgnd ? 0x80 : 0)));   // BPC (one precision for all components)
     o.push_back(7); o.push_back(0); o.push_back(0);                 // C = 7, UnkC = 0, IPR = 0
-    put32(o, 15); put32(o, BOX_COLR); o.push_back(1); o.push_back(0); o.push_back(0);   // METH 1, PREC, APPROX
-    put32(o, P.nc < 3 ? 17 : 16);                                   // EnumCS: greyscale / sRGB
+    if (!ec || !ec->set) {
+        put32(o, 15); put32(o, BOX_COLR); o.push_back(1); o.push_back(0); o.push_back(0);   // METH 1, PREC, APPROX
+        put32(o, P.nc < 3 ? 17 : 16);                               // EnumCS: greyscale / sRGB
+        return o;
+    }
+    uint32_t colour_channels = 0;
+    const uint32_t enumcs = enc_colour_check(*ec, colour_channels);
+    if (ec->space == 9) {
+        put32(o, 11 + (uint32_t)ec->icc.size()); put32(o, BOX_COLR); o.push_back(2); o.push_back(0); o.push_back(0);
+        o.insert(o.end(), ec->icc.begin(), ec->icc.end());
+    } else {
+        put32(o, 15); put32(o, BOX_COLR); o.push_back(1); o.push_back(0); o.push_back(0);
+        put32(o, enumcs);
+    }
+    if (!ec->typ.empty() && ec->typ.size() != P.nc)
+        throw GkError("typ / asoc: " + std::to_string(ec->typ.size()) + " channel entries for " + std::to_string(P.nc) + " components");
+    bool alpha = false;
+    for (uint16_t t : ec->typ) alpha = alpha || t != 0;
+    if (alpha) {   // (:840-865, the forced leading entries included)
+        if (colour_channels > P.nc)
+            throw GkError("cdef box: the colour space has " + std::to_string(colour_channels) + " colour channels, the image " +
+                          std::to_string(P.nc) + " components");
+        put32(o, 10 + 6 * P.nc); put32(o, BOX_CDEF); put16(o, P.nc);
+        for (uint32_t i = 0; i < P.nc; ++i) {
+            put16(o, i);
+            put16(o, i < colour_channels ? 0 : ec->typ[i]);
+            put16(o, i < colour_channels ? i + 1 : ec->asoc[i]);
+        }
+    }
+    if (ec->palette) {
+        uint32_t per = 0;
+        for (uint32_t i = 0; i < ec->npc; ++i) per += (ec->pprec[i] + 7u) / 8u;
+        put32(o, 8 + 3 + ec->npc + per * ec->ne); put32(o, BOX_PCLR); put16(o, ec->ne); o.push_back((uint8_t)ec->npc);
+        for (uint32_t i = 0; i < ec->npc; ++i) o.push_back((uint8_t)(ec->pprec[i] - 1));
+        for (uint32_t j = 0; j < ec->ne; ++j)
+            for (uint32_t i = 0; i < ec->npc; ++i) {
+                const int32_t v = ec->lut[(size_t)j * ec->npc + i];
+                if (ec->pprec[i] > 8) o.push_back((uint8_t)(v >> 8));
+                o.push_back((uint8_t)v);
+            }
+        put32(o, 8 + 4 * ec->npc); put32(o, BOX_CMAP);
+        for (uint32_t i = 0; i < ec->npc; ++i) { put16(o, ec->cmap[i].cmp); o.push_back(ec->cmap[i].mtyp); o.push_back(ec->cmap[i].pcol); }
+    }
+    enc_colour_validate(o, P);   // whatever the reader refuses in these boxes, under its own message
+    return o;
+}
+static size_t jp2_prefix_size(const Plan& P, const std::vector<uint8_t>& hd) {
+    return 12 + 20 + 8 + hd.size() + (jp2_needs_xl(P) ? 16 : 8);
+}
+// signature, file type, JP2 header (hd: jp2h_content) and the jp2c box header for a codestream of
+// cs_len bytes
+static void write_jp2_prefix(std::vector<uint8_t>& o, const Plan& P, uint64_t cs_len, const std::vector<uint8_t>& hd) {
+    put32(o, 12); put32(o, BOX_JP); put32(o, 0x0d0a870a);
+    put32(o, 20); put32(o, BOX_FTYP); put32(o, BRAND_JP2); put32(o, 0); put32(o, BRAND_JP2);
+    put32(o, 8 + (uint32_t)hd.size()); put32(o, BOX_JP2H);
+    o.insert(o.end(), hd.begin(), hd.end());
     if (jp2_needs_xl(P)) {
         put32(o, 1); put32(o, BOX_JP2C); put32(o, (uint32_t)((cs_len + 16) >> 32)); put32(o, (uint32_t)(cs_len + 16));
     } else {
@@ -2628,7 +2737,6 @@ struct Jp2Colour {
         }
     }
 };
-static const uint32_t BOX_BPCC = 0x62706363, BOX_PCLR = 0x70636c72, BOX_CMAP = 0x636d6170, BOX_CDEF = 0x63646566;
 static void jp2_read_colr(ByteSrc& S, size_t p, size_t n, Jp2Colour& C) {
     if (n < 3) throw GkError("colr box: bad size");
     if (C.has_colr) return;   // I.5.3.3: every colour specification box after the first is ignored
@@ -2874,6 +2982,42 @@ static ColourOut resolve_colour(const Jp2Colour& C, const Plan& W) {
         }
     }
     return O;
+}
+
+// The jp2h contents an encode is about to write, read back as a decode would read them: the
+// reader's refusals (jp2_read_* and resolve_colour) are the writer's.
+static void enc_colour_validate(const std::vector<uint8_t>& jp2h, const Plan& P) {
+    ByteSrc S; S.len = jp2h.size(); S.host = jp2h.data();
+    Jp2Colour C;
+    jp2_read_jp2h(S, 0, jp2h.size(), C);
+    C.jp2 = true;
+    Plan W;
+    W.w = P.w; W.h = P.h; W.nc = P.nc; W.prec = P.prec; W.sgnd = P.sgnd;
+    (void)resolve_colour(C, W);
+}
+static void set_enc_colour(EncColour& E, const gk_encode_colour* s) {
+    E = EncColour();
+    if (!s) return;
+    EncColour N;
+    N.set = true; N.space = s->colour_space;
+    if (s->icc_len && !s->icc) throw GkError("icc: a length without a buffer");
+    if (s->icc_len) N.icc.assign(s->icc, s->icc + s->icc_len);
+    if (s->num_channels) {
+        if (!s->typ || !s->asoc) throw GkError("typ / asoc: a channel count without both arrays");
+        if (s->num_channels > 16384) throw GkError("typ / asoc: more than 16384 channels");
+        N.typ.assign(s->typ, s->typ + s->num_channels); N.asoc.assign(s->asoc, s->asoc + s->num_channels);
+    }
+    if (s->palette_entries || s->palette_columns) {
+        N.palette = true; N.ne = s->palette_entries; N.npc = s->palette_columns;
+        if (N.ne > 65535 || N.npc > 255) throw GkError("pclr box: NE must be 1..1024 and NPC 1..255");
+        if (N.npc && (!s->channel_prec || !s->cmap || (N.ne && !s->lut))) throw GkError("pclr box: a palette without its column precisions, LUT or cmap entries");
+        N.pprec.assign(s->channel_prec, s->channel_prec + N.npc);
+        N.lut.assign(s->lut, s->lut + (size_t)N.ne * N.npc);
+        for (uint32_t i = 0; i < N.npc; ++i) N.cmap.push_back({s->cmap[i].component, s->cmap[i].mapping_type, s->cmap[i].palette_column});
+    }
+    uint32_t cc;
+    (void)enc_colour_check(N, cc);
+    E = N;
 }
 
 // What the display flags (gk_set_decode_display) make of the output channels: the CLI's
@@ -3181,12 +3325,15 @@ struct gk_ctx {
     DevBuf dstage1, dstage2;   // decode: batched tile-part / packet header fetches (device input)
     DevBuf dcol_src, dcol_out, dcol_tab;   // palette stage: index / component planes, host-bound output, tables
     DevBuf dpix_src, dpix_out;             // output stage: its planar input, host-bound output
+    DevBuf dpix_in;                        // encode from pixels: the host's packed rows
     HostBuf hstage1, hstage2;
     int16_t* nmse_tab = nullptr;   // device copy of the nmsedec tables (4 x 128)
     hipEvent_t ev[32];
     bool blocks_uploaded = false;
     uint32_t enc_b0 = 0, enc_b1 = 0;   // block range of the uploaded encode table
     std::vector<uint8_t> enc_dx, enc_dy;   // gk_set_subsampling: the next encodes' component subsampling
+    EncColour enc_col;                     // gk_set_encode_colour: the next encodes' colour description
+    std::vector<uint8_t> enc_jp2h;         // the jp2h contents of the JP2 encode in progress (setup_plan)
     std::vector<uint32_t> hdr_dx, hdr_dy, hdr_prec, hdr_sgnd;   // the last gk_decode_header's components
     bool enc_rc = false;                // its rate-control flag (GkBlock::flags bit 1)
     // band quantisation held by the cached plan's bands: the plan's own (encoder, native_qcd)
@@ -3507,6 +3654,7 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     if (want.p.tw && ((uint64_t)want.gx0 + want.p.tw <= want.x0 || (uint64_t)want.gy0 + want.p.th <= want.y0))
         throw GkError("the first tile must overlap the image area");
     if (want.nc < 3) want.p.mct = 0;
+    if (ctx->enc_col.clears_mct()) want.p.mct = 0;   // sYCC / e-sYCC (CodeStreamCompress.cpp:494-500)
     // CodeStreamCompress.cpp:501-512: no MCT unless the first three components share a grid
     if (want.p.mct && !want.mct3()) want.p.mct = 0;
     check_poc_coverage(want.p, want.nc);
@@ -3517,6 +3665,8 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     if (want.prec == 0 || want.prec > 31) throw GkError("component precision must be 1..31 bits");
     check_precision(want);
     if (want.w == 0 || want.h == 0) throw GkError("empty image");
+    // the jp2h contents of this call, built (and a colour description refused) once, here
+    if (want.p.jp2) ctx->enc_jp2h = jp2h_content(want, &ctx->enc_col);
     // grk_compress.cpp:981-988 (and A.6.1's xcb, ycb): 4 <= side <= 1024, at most 4096 samples
     if (want.p.cbw < 2 || want.p.cbh < 2 || want.p.cbw > 10 || want.p.cbh > 10 || want.p.cbw + want.p.cbh > 12)
         throw GkError("code-block size must be 4..1024 per side with at most 4096 samples");
@@ -3597,10 +3747,15 @@ static void dump_blocks(gk_ctx* ctx, const uint32_t* hinfo, const GkPass* dps, u
     }
 }
 
+// Packed pixels handed to gk_encode_pixels: sample k of pixel (x, y) at pixels + y * row_bytes +
+// (x * nc + k) * es.  encode_impl unpacks them into planes of the same sample type (k_unpixels)
+// where it would stage host planes, and goes on as if the caller had passed those device planes.
+struct PixSrc { const void* pixels; size_t row_bytes; int on_device; };
+
 static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
                           int comps_on_device, const gk_cparameters* cp, uint8_t* out, size_t cap, int out_on_device,
                           int* rc, uint32_t tb = 0, uint32_t te = 0, bool with_header = true,
-                          uint32_t* part_lens = nullptr, bool blocks_only = false) {
+                          uint32_t* part_lens = nullptr, bool blocks_only = false, const PixSrc* pix = nullptr) {
     setup_plan(ctx, info, cp);
     Plan& P = ctx->plan;
     const uint32_t ntiles = (uint32_t)P.tiles.size();
@@ -3629,7 +3784,25 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     // group's grid: every row of the image width); host planes are staged back to back
     std::vector<Region> RGg;
     for (const SGroup& G : P.groups) RGg.push_back(group_region(P, RG, G));
-    {
+    if (pix) {
+        // packed pixels (one grid): the touched rows, staged at their tight width when they are the
+        // host's, are separated into nc planes whose rows start on GK_UNPIX_ALIGN bytes
+        const size_t tight = (size_t)RG.w * P.nc * es;
+        const uint8_t* first = (const uint8_t*)pix->pixels + (size_t)RG.y0 * pix->row_bytes;
+        GkUnpixArgs ua{};
+        ua.ds = align_up(RG.w, GK_UNPIX_ALIGN);
+        ua.plane = (uint64_t)ua.ds * RG.h;
+        ua.w = RG.w; ua.h = RG.h; ua.nch = P.nc;
+        ua.dst = ctx->dplanes.get(ua.plane * P.nc * es);
+        ua.src = first; ua.row_bytes = pix->row_bytes;
+        if (!pix->on_device) {
+            void* dp = ctx->dpix_in.get(tight * RG.h);
+            HIPCHK(hipMemcpy2DAsync(dp, tight, first, pix->row_bytes, tight, RG.h, hipMemcpyHostToDevice, st));
+            ua.src = dp; ua.row_bytes = tight;
+        }
+        gk_launch_unpixels(st, (int)es, ua);
+        for (uint32_t c = 0; c < P.nc; ++c) { src[c] = (const uint8_t*)ua.dst + (size_t)c * ua.plane * es; sstr[c] = ua.ds; }
+    } else {
         size_t tot = 0;
         for (uint32_t c = 0; c < P.nc; ++c) tot += (size_t)RGg[P.group_of[c]].w * RGg[P.group_of[c]].h;
         uint8_t* dp = comps_on_device ? nullptr : (uint8_t*)ctx->dplanes.get(tot * es + 16);
@@ -3846,7 +4019,7 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     write_main_header(H, P, &tlm_pos);
     // updateRates' header bytes: the stream position after the main header (JP2 boxes and the
     // jp2c box header come first in a .jp2), CodeStreamCompress.cpp:963
-    const size_t rc_header_size = H.size() + (P.p.jp2 ? jp2_prefix_size(P) : 0);
+    const size_t rc_header_size = H.size() + (P.p.jp2 ? jp2_prefix_size(P, ctx->enc_jp2h) : 0);
     if (!with_header) H.clear();
     const auto te1 = eclk::now();
     if (const char* ds = getenv("GK_DUMP_SYMS"); ds && dsym && !P.p.t1_generic()) {
@@ -3906,7 +4079,7 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     // JP2 boxes before the codestream; the jp2c length is written once the size is known
     std::vector<uint8_t> J;
     const bool jp2 = P.p.jp2 && with_header;
-    if (jp2) write_jp2_prefix(J, P, 0);
+    if (jp2) write_jp2_prefix(J, P, 0, ctx->enc_jp2h);
     add_host(J.data(), J.size());
     const size_t main_at = J.size();   // the main header's position in hdrs
     add_host(H.data(), H.size());
@@ -4188,8 +4361,9 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     if (with_header) add_host(eoc, 2);
     const size_t total = pos;
     if (jp2) {
+        const size_t prefix = J.size();
         J.clear();
-        write_jp2_prefix(J, P, total - jp2_prefix_size(P));
+        write_jp2_prefix(J, P, total - prefix, ctx->enc_jp2h);
         memcpy(hdrs.data(), J.data(), J.size());
     }
     launch_check(__LINE__);
@@ -6331,6 +6505,35 @@ int gk_encode(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, 
     }
 }
 
+int gk_encode_pixels(gk_ctx* ctx, const gk_image_info* info, const void* pixels, size_t row_bytes, int pixels_on_device,
+                     const gk_cparameters* p, uint8_t* out, size_t cap, size_t* out_len, int out_on_device) {
+    if (!ctx || !info || !pixels || !out) return -1;
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
+        // what packed pixels cannot express; whatever gk_encode refuses follows in encode_impl
+        // (setup_plan), which allocates nothing before it
+        for (size_t c = 0; c < ctx->enc_dx.size(); ++c)
+            if (ctx->enc_dx[c] != 1 || ctx->enc_dy[c] != 1)
+                throw GkError("pixels: gk_set_subsampling is active (packed pixels have one grid; use the planar call)");
+        if (info->numcomps > GK_PIX_MAX_CH) throw GkError("pixels: more than 16 channels (use the planar call)");
+        const size_t es = gk_sample_size(sample_type(info->sample_bytes, info->prec, info->sgnd != 0));
+        if (row_bytes < (size_t)info->w * info->numcomps * es) throw GkError("pixels: row_bytes is below w * C * es");
+        if (row_bytes % es) throw GkError("pixels: row_bytes must be a multiple of the sample size");
+        if ((uintptr_t)pixels % es) throw GkError("pixels: the buffer is not aligned to its sample size");
+        const PixSrc px{pixels, row_bytes, pixels_on_device};
+        int rc = 0;
+        size_t n = encode_impl(ctx, info, nullptr, nullptr, 1, p, out, cap, out_on_device, &rc, 0, 0, true, nullptr, false, &px);
+        if (out_len) *out_len = n;
+        if (rc == -2) ctx->err = "output capacity too small";
+        return rc;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
 int gk_encode_tiles(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
                     int comps_on_device, const gk_cparameters* p, uint32_t tile_begin, uint32_t tile_end,
                     uint8_t* out, size_t cap, size_t* out_len, uint32_t* part_lens, int out_on_device) {
@@ -6584,13 +6787,48 @@ int gk_jp2_header(gk_ctx* ctx, const gk_image_info* info, uint64_t cs_len, uint8
         P.w = info->w; P.h = info->h; P.nc = info->numcomps; P.prec = info->prec; P.sgnd = info->sgnd;
         if (!P.w || !P.h || !P.nc || P.nc > 255 || !P.prec || P.prec > 31) throw GkError("bad image info");
         std::vector<uint8_t> J;
-        write_jp2_prefix(J, P, cs_len);
+        write_jp2_prefix(J, P, cs_len, jp2h_content(P, &ctx->enc_col));
         if (out_len) *out_len = J.size();
         if (J.size() > cap) { ctx->err = "output capacity too small"; return -2; }
         memcpy(out, J.data(), J.size());
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_set_encode_colour(gk_ctx* ctx, const gk_encode_colour* spec) {
+    if (!ctx) return -1;
+    try {
+        set_enc_colour(ctx->enc_col, spec);   // (cleared first: a refused description leaves none)
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_jp2_boxes(const gk_image_info* info, const gk_encode_colour* spec, uint64_t cs_len, uint8_t* out, size_t cap,
+                 size_t* out_len, char* msg, size_t msg_cap) {
+    if (!info || !out) return -1;
+    try {
+        Plan P;
+        P.w = info->w; P.h = info->h; P.nc = info->numcomps; P.prec = info->prec; P.sgnd = info->sgnd;
+        if (!P.w || !P.h || !P.nc || P.nc > 255 || !P.prec || P.prec > 31) throw GkError("bad image info");
+        EncColour E;
+        set_enc_colour(E, spec);
+        std::vector<uint8_t> J;
+        write_jp2_prefix(J, P, cs_len, jp2h_content(P, &E));
+        if (out_len) *out_len = J.size();
+        if (J.size() > cap) {
+            if (msg && msg_cap) snprintf(msg, msg_cap, "output capacity too small");
+            return -2;
+        }
+        memcpy(out, J.data(), J.size());
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
         return -1;
     }
 }

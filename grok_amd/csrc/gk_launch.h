@@ -192,3 +192,20 @@ struct GkPixArgs {
 };
 // stype / dtype: GK_U8, GK_U16 or GK_S32 planes in / pixels out
 void gk_launch_pixels(hipStream_t st, int stype, int dtype, const GkPixArgs& args);
+// Input stage of an encode from packed pixels (gk_unpixels.hip): sample k of pixel (x, y) is read
+// at src + y * row_bytes + (x * nch + k) * es and written to plane k, dst + k * plane samples on,
+// row stride ds samples, in the same sample type.  The planes are the engine's own: dst, ds and
+// plane aligned to 32 bytes; src needs its element's alignment only, and no byte outside the w *
+// nch * es bytes of a row is read.
+#define GK_UNPIX_ALIGN 32u
+struct GkUnpixArgs {
+    const void* src;
+    uint64_t row_bytes;
+    void* dst;
+    uint64_t plane;            // samples between the planes of consecutive channels
+    uint32_t ds;
+    uint32_t w, h, nch;
+    uint32_t rows;             // (set by the launcher)
+};
+// es: bytes per sample (1, 2 or 4)
+void gk_launch_unpixels(hipStream_t st, int es, const GkUnpixArgs& args);

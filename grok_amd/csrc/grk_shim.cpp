@@ -273,20 +273,60 @@ bool run_encode(CodecObj* C, const void* const* planes, const uint32_t* strides,
     gk_image_info info;
     if (!image_geometry(C->image, info)) return false;
     info.sample_bytes = sample_bytes;
-    if (C->fmt == GRK_CODEC_JP2 && C->image->color_space != GRK_CLRSPC_UNKNOWN &&
-        C->image->color_space != (info.numcomps < 3 ? GRK_CLRSPC_GRAY : GRK_CLRSPC_SRGB)) {
-        error("JP2 output supports sRGB (3+ components) or greyscale colour spaces on this path");
-        return false;
+    // the image's colour description.  A raw codestream carries none: only what reaches it goes to
+    // the engine (sYCC / e-sYCC clear the MCT, CodeStreamCompress.cpp:494-500), and nothing else
+    // about the image's colour can refuse the encode.  For a JP2 file (FileFormatCompress::
+    // initCompress :749-871) colour space, ICC profile, component types / associations and palette
+    // go to the engine when any of them differs from what it writes by default;
+    // GRK_CLRSPC_UNKNOWN keeps that default's colour space
+    const grk_image* im = C->image;
+    gk_encode_colour spec{};
+    bool described = false;
+    std::vector<uint16_t> typ(info.numcomps), asoc(info.numcomps);
+    std::vector<gk_cmap_entry> cm;
+    if (C->fmt != GRK_CODEC_JP2) {
+        spec.colour_space = im->color_space;
+        described = im->color_space == GRK_CLRSPC_SYCC || im->color_space == GRK_CLRSPC_EYCC;
+    } else {
+        const GRK_COLOR_SPACE dflt = info.numcomps < 3 ? GRK_CLRSPC_GRAY : GRK_CLRSPC_SRGB;
+        const grk_color* col = im->meta ? &im->meta->color : nullptr;
+        const grk_palette_data* pal = col ? col->palette : nullptr;
+        spec.colour_space = im->color_space == GRK_CLRSPC_UNKNOWN ? dflt : im->color_space;
+        described = spec.colour_space != (uint32_t)dflt;
+        for (uint32_t c = 0; c < info.numcomps; ++c) {
+            typ[c] = (uint16_t)im->comps[c].type; asoc[c] = (uint16_t)im->comps[c].association;
+            described = described || im->comps[c].type != GRK_COMPONENT_TYPE_COLOUR;
+        }
+        spec.num_channels = info.numcomps; spec.typ = typ.data(); spec.asoc = asoc.data();
+        if (col && col->icc_profile_buf && col->icc_profile_len) {
+            spec.icc = col->icc_profile_buf; spec.icc_len = col->icc_profile_len;
+            described = true;
+        }
+        if (pal) {
+            spec.palette_entries = pal->num_entries; spec.palette_columns = pal->num_channels;
+            spec.channel_prec = pal->channel_prec; spec.lut = pal->lut;
+            for (uint32_t i = 0; i < pal->num_channels && pal->component_mapping; ++i)
+                cm.push_back({pal->component_mapping[i].component_index, pal->component_mapping[i].mapping_type,
+                              pal->component_mapping[i].palette_column});
+            if (cm.size() != pal->num_channels || !pal->channel_prec || !pal->lut) { error("palette without its mapping, precisions or LUT"); return false; }
+            spec.cmap = cm.data();
+            described = true;
+        }
     }
     std::lock_guard<std::mutex> lk(g_eng_m);
     gk_ctx* e = engine();
     if (!e) return false;
+    if (gk_set_encode_colour(e, described ? &spec : nullptr) != 0) {
+        error("%s", gk_last_error(e));
+        return false;
+    }
     std::vector<uint32_t> dx(info.numcomps), dy(info.numcomps);
     for (uint32_t c = 0; c < info.numcomps; ++c) {
         dx[c] = C->image->comps[c].dx ? C->image->comps[c].dx : 1; dy[c] = C->image->comps[c].dy ? C->image->comps[c].dy : 1;
     }
     if (gk_set_subsampling(e, subsampled(C->image) ? info.numcomps : 0, dx.data(), dy.data()) != 0) {
         error("%s", gk_last_error(e));
+        gk_set_encode_colour(e, nullptr);
         return false;
     }
     std::vector<uint8_t> out((size_t)info.w * info.h * info.numcomps * 4 + (1 << 20));
@@ -297,6 +337,7 @@ bool run_encode(CodecObj* C, const void* const* planes, const uint32_t* strides,
         rc = gk_encode(e, &info, planes, strides, 0, &p, out.data(), out.size(), &n, 0);
     }
     gk_set_subsampling(e, 0, nullptr, nullptr);
+    gk_set_encode_colour(e, nullptr);
     if (rc != 0) { error("%s", gk_last_error(e)); return false; }
     StreamObj* s = stream_of(C->stream);
     if (!s || !s->write_all(out.data(), n)) return false;

@@ -134,6 +134,21 @@ int gk_encode(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, 
               int comps_on_device, const gk_cparameters* p, uint8_t* out, size_t cap, size_t* out_len,
               int out_on_device);
 
+/* gk_encode from packed pixels, the mirror of gk_decode_pixels: what Grok's image readers hold
+ * before they split it into planes (bin/image_format, e.g. PNGFormat / TIFFFormat's
+ * interleaved-to-planar pass), read by the device.  Sample k of pixel (x, y) lies at
+ * pixels + y * row_bytes + (x * C + k) * es; C = info->numcomps, es follows info->sample_bytes
+ * (0 or 4: int32; 1 / 2: (prec + 7) / 8; signed samples are the same bits).  No byte outside the
+ * w * C * es bytes of a row is read.  info->x0 / y0 and every coding parameter are honoured and the
+ * codestream is the one gk_encode writes for the same samples in planes.  Refused, each by name,
+ * before anything is allocated: an active gk_set_subsampling (packed pixels have one grid); a
+ * sample_bytes that breaks the rule; row_bytes below w * C * es, or row_bytes / pixels no multiple
+ * of es; more than 16 channels (use the planar call); whatever gk_encode refuses.  Returns as
+ * gk_encode (-2: capacity too small, *out_len = needed). */
+int gk_encode_pixels(gk_ctx* ctx, const gk_image_info* info, const void* pixels, size_t row_bytes,
+                     int pixels_on_device, const gk_cparameters* p, uint8_t* out, size_t cap, size_t* out_len,
+                     int out_on_device);
+
 /* Tile sharding: encode only tiles [tile_begin, tile_end) of the
  * image described by info / p — grk_compress_tile (grok.h:1082-1657) per tile, without
  * the main header.  comps[c] addresses the image origin; only the sample rows of the
@@ -157,6 +172,56 @@ int gk_main_header(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters*
  * FileFormatCompress.cpp:666-693, 59-102): JP2 file = these bytes + the codestream.  Used to
  * assemble sharded tile parts into a .jp2.  Returns 0, -2 if cap is too small (*out_len = needed). */
 int gk_jp2_header(gk_ctx* ctx, const gk_image_info* info, uint64_t cs_len, uint8_t* out, size_t cap, size_t* out_len);
+
+/* Colour description of later encodes: what FileFormatCompress::initCompress (FileFormatCompress.cpp
+ * :694-909) reads from the grk_image, written into the jp2h box as write_jp2h does (:176-264), in
+ * its order: ihdr, colr, cdef, pclr, cmap.
+ * colr: METH 1 with EnumCS 16 (GRK_CLRSPC_SRGB), 17 (GRAY), 18 (SYCC), 24 (EYCC) or 12 (CMYK), or
+ * METH 2 carrying the profile for GRK_CLRSPC_ICC (EnumCS 0); PREC = APPROX = 0.
+ * cdef: written when any typ[] is not colour (0); numcomps entries, the first color_channels of
+ * them forced to (i, 0, i + 1) (4 for CMYK, 3 for sRGB / sYCC / e-sYCC, 1 for grey, 0 for ICC), the
+ * rest (i, typ[i], asoc[i]) (:811-865).
+ * pclr + cmap: written when a palette is given; Bi = channel_prec - 1, every LUT value big-endian in
+ * (prec + 7) / 8 bytes, one cmap entry per palette column.
+ * One effect reaches the codestream, raw or wrapped: sYCC and e-sYCC clear the MCT
+ * (CodeStreamCompress.cpp:494-500).
+ * Refused, each by name: GRK_CLRSPC_UNKNOWN and values Grok errors on; GRK_CLRSPC_DEFAULT_CIE (EnumCS
+ * 14, which the decoder refuses); GRK_CLRSPC_ICC without a profile; a profile with another colour
+ * space (Grok drops it silently); typ / asoc for another component count; a cdef whose
+ * color_channels exceed the component count; and every box the engine's own reader refuses
+ * (gk_probe_colour's messages: NE outside 1..1024, NPC 0, a column above 16 bits, a LUT value
+ * outside its column, MTYP above 1, a column mapped twice or out of range, a direct mapping with a
+ * column, a component index out of range, a signed mapped component, a mapped component of more bits
+ * than the palette has entries, an incomplete or contradictory cdef). */
+typedef struct gk_cmap_entry {
+    uint16_t component;        /* grk_component_mapping_comp::component_index (CMP) */
+    uint8_t mapping_type;      /* MTYP: 0 direct, 1 palette */
+    uint8_t palette_column;    /* PCOL */
+} gk_cmap_entry;
+typedef struct gk_encode_colour {
+    uint32_t colour_space;     /* GRK_COLOR_SPACE, as gk_colour_info::colour_space */
+    const uint8_t* icc;        /* grk_color::icc_profile_buf / icc_profile_len */
+    uint32_t icc_len;
+    uint32_t num_channels;     /* entries of typ / asoc: 0 (every component is colour) or the component count */
+    const uint16_t* typ;       /* grk_image_comp::type */
+    const uint16_t* asoc;      /* grk_image_comp::association */
+    uint32_t palette_entries;  /* grk_palette_data::num_entries (NE); 0 with palette_columns 0: no palette */
+    uint32_t palette_columns;  /* num_channels (NPC) */
+    const uint8_t* channel_prec;   /* NPC column precisions */
+    const int32_t* lut;        /* NE rows of NPC values */
+    const gk_cmap_entry* cmap; /* NPC entries */
+} gk_encode_colour;
+/* Sticky: later gk_encode / gk_encode_pixels calls with cod_format 2, and gk_jp2_header, write the
+ * boxes above instead of ihdr + a default colr; everything is copied.  spec = NULL clears it (the
+ * state of a new engine: every byte as before).  What depends on the image (component count,
+ * precision, sign) is checked by the call that writes the boxes, before anything is allocated.  A
+ * refused spec leaves the engine with none. */
+int gk_set_encode_colour(gk_ctx* ctx, const gk_encode_colour* spec);
+/* gk_jp2_header without an engine (no device needed): the JP2 boxes in front of a codestream of
+ * cs_len bytes for the image `info` under `spec` (NULL: ihdr + the default colr).  Returns 0, -2 if
+ * cap is too small (*out_len = needed), -1 with the refusal in msg. */
+int gk_jp2_boxes(const gk_image_info* info, const gk_encode_colour* spec, uint64_t cs_len, uint8_t* out, size_t cap,
+                 size_t* out_len, char* msg, size_t msg_cap);
 
 /* grk_decompress_read_header (grok.cpp:287-297, CodeStreamDecompress::readHeader) of a raw
  * codestream or a JP2 file (its jp2c box; FileFormatDecompress::read_box_hdr :632-672). */
