@@ -28,9 +28,9 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_probe_colour", "gk_header_colour", "gk_header_icc", "gk_set_decode_colour", "gk_probe_icc",
            "gk_probe_stream_components", "gk_set_decode_display", "gk_probe_display", "gk_set_decode_precision",
            "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels", "gk_encode_pixels",
-           "gk_set_encode_colour", "gk_jp2_boxes")
+           "gk_set_encode_colour", "gk_jp2_boxes", "gk_header_cielab", "gk_probe_cielab")
 GK_MAX_CHANNELS = 256
-GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB = 1, 2, 4   # gk_set_decode_display flags
+GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB, GK_DISPLAY_ICC = 1, 2, 4, 8   # gk_set_decode_display flags
 GK_PREC_CLIP, GK_PREC_SCALE = 0, 1   # gk_precision::mode (grk_precision_mode)
 
 
@@ -280,6 +280,10 @@ def load_library(build_if_missing=True):
     lib.gk_header_colour.argtypes = [ctypes.c_void_p, P(ColourInfo)]
     lib.gk_header_icc.restype = ctypes.c_int
     lib.gk_header_icc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]
+    lib.gk_header_cielab.restype = ctypes.c_int
+    lib.gk_header_cielab.argtypes = [ctypes.c_void_p, P(ctypes.c_uint32), P(ctypes.c_uint32)]
+    lib.gk_probe_cielab.restype = ctypes.c_int
+    lib.gk_probe_cielab.argtypes = [ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_uint32), P(ctypes.c_uint32)]
     lib.gk_set_decode_colour.restype = ctypes.c_int
     lib.gk_set_decode_colour.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.gk_set_decode_display.restype = ctypes.c_int
@@ -423,6 +427,18 @@ def probe_icc(cs):
     return buf[:n.value].tobytes()
 
 
+def probe_cielab(cs):
+    """gk_probe_cielab: the CIELab words of host JP2 bytes (colr EnumCS 14) as Grok keeps them: [14,
+    default / custom tag] or [14, 0, rl, ol, ra, oa, rb, ob, il]; [] for any other file."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    words, n = (ctypes.c_uint32 * 9)(), ctypes.c_uint32()
+    if lib.gk_probe_cielab(b.ctypes.data, len(b), words, ctypes.byref(n)) != 0:
+        probe_colour(cs)   # (raises with the reason)
+        raise ValueError("gk_probe_cielab failed")
+    return [int(words[i]) for i in range(n.value)]
+
+
 class DisplayInfo:
     """What probe_display reports: the output of a decode under the display flags."""
 
@@ -436,11 +452,12 @@ class DisplayInfo:
         self.converted = bool(colour.display_applied & GK_DISPLAY_RGB)
         self.upsampled = bool(colour.display_applied & GK_DISPLAY_UPSAMPLE)
         self.replicated = bool(colour.display_applied & GK_DISPLAY_FORCE_RGB)   # grey to RGB
+        self.managed = bool(colour.display_applied & GK_DISPLAY_ICC)   # ICC profile / CIELab to sRGB
 
 
-def probe_display(cs, rgb=False, upsample=False, reduce=0):
+def probe_display(cs, rgb=False, upsample=False, reduce=0, icc=False):
     """gk_probe_display: what a decode of host codestream / JP2 bytes returns under
-    Engine.set_decode_display(rgb, upsample) and set_decode_reduce(reduce), no engine or GPU
+    Engine.set_decode_display(rgb, upsample, icc=icc) and set_decode_reduce(reduce), no engine or GPU
     needed: a DisplayInfo with the channel shapes (rows, cols), precisions, signs, colour space
     (GRK_COLOR_SPACE) and the converted / upsampled flags.  Raises ValueError with the refusal."""
     lib = load_library()
@@ -448,7 +465,7 @@ def probe_display(cs, rgb=False, upsample=False, reduce=0):
     info, colour = ImageInfo(), ColourInfo()
     dx, dy, pr, sg = [(ctypes.c_uint32 * 16384)() for _ in range(4)]
     msg = ctypes.create_string_buffer(512)
-    flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0)
+    flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0) | (GK_DISPLAY_ICC if icc else 0)
     n = lib.gk_probe_display(b.ctypes.data, len(b), flags, int(reduce), ctypes.byref(info), ctypes.byref(colour),
                              dx, dy, pr, sg, 16384, msg, 512)
     if n < 0:
@@ -456,17 +473,17 @@ def probe_display(cs, rgb=False, upsample=False, reduce=0):
     return DisplayInfo(info, colour, [(dx[c], dy[c], pr[c], sg[c]) for c in range(n)], int(reduce))
 
 
-def probe_output(cs, rgb=False, upsample=False, force_rgb=False, precision=None, reduce=0):
+def probe_output(cs, rgb=False, upsample=False, force_rgb=False, precision=None, reduce=0, icc=False):
     """gk_probe_output: probe_display with the grey-to-RGB flag and a forced-precision list
     (parse_precision): what Engine.decode / decode_pixels return under set_decode_display(rgb,
-    upsample, force_rgb) and set_decode_precision(precision), no engine or GPU needed."""
+    upsample, force_rgb, icc) and set_decode_precision(precision), no engine or GPU needed."""
     lib = load_library()
     b = np.frombuffer(bytes(cs), np.uint8)
     info, colour = ImageInfo(), ColourInfo()
     dx, dy, pr, sg = [(ctypes.c_uint32 * 16384)() for _ in range(4)]
     msg = ctypes.create_string_buffer(512)
     flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0) | \
-        (GK_DISPLAY_FORCE_RGB if force_rgb else 0)
+        (GK_DISPLAY_FORCE_RGB if force_rgb else 0) | (GK_DISPLAY_ICC if icc else 0)
     arr, n = _precision_array(precision)
     n = lib.gk_probe_output(b.ctypes.data, len(b), flags, int(reduce), arr, n, ctypes.byref(info), ctypes.byref(colour),
                             dx, dy, pr, sg, 16384, msg, 512)
@@ -867,21 +884,31 @@ class Engine:
             self._err("gk_header_icc")
         return buf.tobytes()
 
+    def cielab(self):
+        """gk_header_cielab: the CIELab words (colr EnumCS 14) of that stream as Grok keeps them,
+        [14, tag] or [14, 0, rl, ol, ra, oa, rb, ob, il]; [] for any other stream."""
+        words, n = (ctypes.c_uint32 * 9)(), ctypes.c_uint32()
+        if self.lib.gk_header_cielab(self.ctx, words, ctypes.byref(n)) != 0:
+            self._err("gk_header_cielab")
+        return [int(words[i]) for i in range(n.value)]
+
     def set_decode_colour(self, apply):
         """gk_set_decode_colour: apply a JP2 file's palette and channel definition on decode (True,
         the default: planes are the output channels) or return the codestream's components (False)."""
         if self.lib.gk_set_decode_colour(self.ctx, int(bool(apply))) != 0:
             self._err("gk_set_decode_colour")
 
-    def set_decode_display(self, rgb=False, upsample=False, force_rgb=False):
+    def set_decode_display(self, rgb=False, upsample=False, force_rgb=False, icc=False):
         """gk_set_decode_display: what grk_decompress does to the decoded image, on the GPU.  rgb:
         sYCC (4:4:4, 4:2:2, 4:2:0), e-sYCC and CMYK images decode to RGB planes; upsample: subsampled
         components are replicated to the image grid (grk_decompress -u); force_rgb: a grey image's
-        channel becomes R, G and B (grk_decompress -f; other channels follow, grey + alpha is RGBA).
+        channel becomes R, G and B (grk_decompress -f; other channels follow, grey + alpha is RGBA);
+        icc: a file's ICC profile (colr METH 2, matrix / tone-curve classes) or CIELab space (EnumCS
+        14) is converted to sRGB, as the CLI does for an output that cannot embed a profile.
         Sticky; read_header, subsampling and colour_info then describe the output, so decode returns
         one (C, H, W) array."""
         flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0) | \
-            (GK_DISPLAY_FORCE_RGB if force_rgb else 0)
+            (GK_DISPLAY_FORCE_RGB if force_rgb else 0) | (GK_DISPLAY_ICC if icc else 0)
         if self.lib.gk_set_decode_display(self.ctx, flags) != 0:
             self._err("gk_set_decode_display")
 

@@ -39,6 +39,7 @@
 #include "gk_common.h"
 #include "gk_bitio.h"
 #include "gk_launch.h"
+#include "gk_icc.h"
 
 namespace {
 
@@ -2704,6 +2705,8 @@ static void write_jp2_prefix(std::vector<uint8_t>& o, const Plan& P, uint64_t cs
 // The colour boxes of a JP2 header box (jp2h), as FileFormatDecompress reads them: colr
 // (read_colr :1028-1149), pclr (read_palette_clr :1483-1548), cmap (read_component_mapping
 // :1437-1482) and cdef (read_channel_definition :931-1027); ihdr / bpcc are kept as read.
+#define GK_CIELAB_CUSTOM 0x0u          // GRK_CUSTOM_CIELAB_SPACE
+#define GK_CIELAB_DEFAULT 0x44454600u  // GRK_DEFAULT_CIELAB_SPACE ('DEF')
 struct Jp2Colour {
     bool jp2 = false;
     bool has_ihdr = false;
@@ -2712,6 +2715,9 @@ struct Jp2Colour {
     bool has_colr = false;          // a colr box was accepted (the first one wins)
     uint32_t meth = 0, enumcs = 0;
     std::vector<uint8_t> icc;
+    // EnumCS 14: the words Grok keeps in icc_profile_buf (read_colr :1076-1123): 14, the default /
+    // custom tag, then rl, ol, ra, oa, rb, ob, il of the 35-byte box
+    std::vector<uint32_t> lab;
     bool has_pclr = false;
     uint32_t ne = 0, npc = 0;
     std::vector<uint8_t> pprec;     // palette column precisions
@@ -2729,6 +2735,7 @@ struct Jp2Colour {
         if (meth == 2 && !icc.empty()) return 9;   // GRK_CLRSPC_ICC
         switch (enumcs) {
             case 12: return 6;   // CMYK
+            case 14: return (lab.size() > 1 && lab[1] == GK_CIELAB_DEFAULT) ? 7 : 8;   // default / custom CIELab
             case 16: return 2;   // sRGB
             case 17: return 3;   // grey
             case 18: return 4;   // sYCC
@@ -2745,7 +2752,14 @@ static void jp2_read_colr(ByteSrc& S, size_t p, size_t n, Jp2Colour& C) {
         if (n < 7) throw GkError("colr box: bad size");
         const uint32_t cs = S.be32(p + 3);
         if (cs != 0 && cs != 12 && cs != 14 && cs != 16 && cs != 17 && cs != 18 && cs != 24) return;   // box ignored
-        if (cs == 14) throw GkError("colr box: the CIELab enumerated colour space (EnumCS 14) and its parameters are not supported");
+        if (cs == 14) {   // (:1076-1123: the 35-byte box carries ranges, offsets and the illuminant; any
+                          //  other size is the default space, as the warning path leaves it)
+            C.lab.assign({14u, GK_CIELAB_DEFAULT});
+            if (n == 35) {
+                C.lab[1] = GK_CIELAB_CUSTOM;
+                for (uint32_t i = 0; i < 7; ++i) C.lab.push_back(S.be32(p + 7 + 4 * i));
+            }
+        }
         C.meth = 1; C.enumcs = cs; C.has_colr = true;
     } else if (meth == 2) {
         if (n == 3) throw GkError("colr box: ICC profile of length zero");
@@ -3023,13 +3037,18 @@ static void set_enc_colour(EncColour& E, const gk_encode_colour* s) {
 // What the display flags (gk_set_decode_display) make of the output channels: the CLI's
 // GrkDecompress::postProcess (grk_decompress.cpp:1335-1389, 1495) resolved from the header alone.
 struct DisplayOut {
-    enum Stage { NONE, YCC, CMYK, UPSAMPLE } stage = NONE;
+    enum Stage { NONE, YCC, CMYK, UPSAMPLE, ICC, LAB } stage = NONE;
     uint32_t mode = 0;            // YCC: GkYccMode
     bool converted = false, upsampled = false;
+    bool managed = false;         // GK_DISPLAY_ICC: the profile or the CIELab space is converted to sRGB
+    GkIccTransform icc;           // ICC: the profile as read
+    uint32_t src_prec = 0;        // ICC / LAB: the precision of the converted channels as decoded
+    double lab_lo[3] = {}, lab_range[3] = {};   // LAB: value = lo + v * range / (2^prec - 1)
     uint32_t colour_space = 0;    // of the output (GRK_COLOR_SPACE)
     uint32_t ofx = 0, ofy = 0;    // oddFirstX / oddFirstY
     struct Ch {
         uint32_t dx = 1, dy = 1, prec = 0, sgnd = 0, typ = 0, asoc = 0;
+        uint32_t src = 0;         // the codestream component behind the channel (ICC / LAB: a cdef may reorder them)
         // the output stage (k_pixels): the channel of the stage before it (conversion and
         // upsampling done, grey not yet replicated) that it reads, that channel's precision, and
         // what a forced precision does to its samples (GkPixOp)
@@ -3045,7 +3064,7 @@ struct DisplayOut {
     bool active() const { return stage != NONE; }
     bool out_active() const { return replicated || forced; }   // needs the output stage
     uint32_t max_prec() const { uint32_t m = 0; for (const Ch& c : ch) m = std::max(m, c.prec); return m; }
-    uint32_t applied() const { return (converted ? 1u : 0u) | (upsampled ? 2u : 0u) | (replicated ? 4u : 0u); }
+    uint32_t applied() const { return (converted ? 1u : 0u) | (upsampled ? 2u : 0u) | (replicated ? 4u : 0u) | (managed ? 8u : 0u); }
 };
 // Plane size of a component sampled every (dx, dy) over the image area or the window (image
 // relative), reduced: every edge ceil(ceil(x / dx) / 2^red).
@@ -3064,6 +3083,7 @@ static DisplayOut resolve_display_flags(const Jp2Colour& C, const ColourOut& O, 
     for (uint32_t k = 0; k < n; ++k) {
         D.ch[k].dx = W.sx(O.ch[k].src); D.ch[k].dy = W.sy(O.ch[k].src);
         D.ch[k].prec = O.ch[k].prec; D.ch[k].sgnd = O.ch[k].sgnd; D.ch[k].typ = O.ch[k].typ; D.ch[k].asoc = O.ch[k].asoc;
+        D.ch[k].src = O.ch[k].src;
     }
     D.colour_space = C.colour_space(W.nc);
     if (!flags) return D;
@@ -3141,6 +3161,59 @@ static DisplayOut resolve_display_flags(const Jp2Colour& C, const ColourOut& O, 
                 D.stage = DisplayOut::CMYK; D.converted = true; D.colour_space = 2;
                 D.ch.pop_back();
                 for (auto& h : D.ch) h.prec = 8;
+            }
+        }
+    }
+    // GK_DISPLAY_ICC (:1390-1443): a METH 2 profile (color_apply_icc_profile) or the CIELab space
+    // (color_cielab_to_rgb) to sRGB, after the conversions above
+    const bool lab = C.jp2 && C.meth == 1 && C.enumcs == 14 && C.lab.size() >= 2;
+    const bool prof = C.jp2 && C.meth == 2 && !C.icc.empty();
+    if ((flags & GK_DISPLAY_ICC) && (lab || prof)) {
+        const char* what = lab ? "CIELab" : "ICC";
+        if (prof) {
+            const std::string why = gk_icc_read(C.icc.data(), C.icc.size(), D.icc);
+            if (!why.empty()) throw GkError("display: ICC: " + why);
+        }
+        const uint32_t ncv = lab ? 3u : D.icc.grey ? 1u : 3u;   // channels the conversion replaces
+        if (prof && !D.icc.grey && n < 3)
+            throw GkError("display: ICC: an RGB profile on an image of " + std::to_string(n) + " channels (it needs at least 3)");
+        if (prof && D.icc.grey && n > 2)
+            throw GkError("display: ICC: a grey profile on an image of " + std::to_string(n) + " channels (it takes 1 or 2)");
+        if (lab && n < 3) throw GkError("display: CIELab: an image of " + std::to_string(n) + " channels (it needs at least 3)");
+        // (color.cpp:469-485: the first four channels of an RGB image must be alike, else the image
+        //  is left as it is; all_components_sanity_check :436, :782 asks one precision and sign of all)
+        bool alike = true;
+        if (prof && !D.icc.grey)
+            for (uint32_t k = 1; k < std::min(n, 4u); ++k)
+                alike = alike && D.ch[k].dx == D.ch[0].dx && D.ch[k].dy == D.ch[0].dy && D.ch[k].prec == D.ch[0].prec &&
+                        D.ch[k].sgnd == D.ch[0].sgnd;
+        if (alike) {
+            if (D.converted) throw GkError(std::string("display: ") + what + ": subsampled components (an image taken as sYCC) cannot be colour-managed");
+            for (uint32_t k = 0; k < n; ++k)
+                if (D.ch[k].dx != 1 || D.ch[k].dy != 1)
+                    throw GkError(std::string("display: ") + what + ": subsampled components cannot be colour-managed");
+            for (uint32_t k = 0; k < ncv; ++k)
+                if (D.ch[k].sgnd) throw GkError(std::string("display: ") + what + ": conversion of a signed channel is not supported");
+            if (D.ch[0].prec > 16)
+                throw GkError(std::string("display: ") + what + ": a precision of " + std::to_string(D.ch[0].prec) + " bits (the conversion holds 1..16)");
+        }
+        if (alike && sane()) {
+            if (O.palette) throw GkError(std::string("display: ") + what + " conversion of a file with a palette is not supported");
+            D.stage = lab ? DisplayOut::LAB : DisplayOut::ICC;
+            D.managed = true;
+            D.src_prec = D.ch[0].prec;
+            D.colour_space = (prof && D.icc.grey) ? 3 : 2;
+            if (lab) {   // (:833-851, :920-927)
+                const double p = (double)D.src_prec, vmax = std::pow(2.0, p) - 1.0;
+                double r[3] = {100, 170, 200}, o[3] = {0, std::pow(2.0, p - 1), 3 * std::pow(2.0, p - 3)};
+                if (C.lab[1] != GK_CIELAB_DEFAULT && C.lab.size() >= 9)
+                    for (int k = 0; k < 3; ++k) { r[k] = (double)C.lab[2 + 2 * k]; o[k] = (double)C.lab[3 + 2 * k]; }
+                for (int k = 0; k < 3; ++k) {
+                    D.lab_lo[k] = -(r[k] * o[k]) / vmax;
+                    const double hi = D.lab_lo[k] + r[k];
+                    D.lab_range[k] = hi - D.lab_lo[k];
+                }
+                for (uint32_t k = 0; k < 3; ++k) D.ch[k].prec = 16;
             }
         }
     }
@@ -3325,6 +3398,8 @@ struct gk_ctx {
     DevBuf dstage1, dstage2;   // decode: batched tile-part / packet header fetches (device input)
     DevBuf dcol_src, dcol_out, dcol_tab;   // palette stage: index / component planes, host-bound output, tables
     DevBuf dpix_src, dpix_out;             // output stage: its planar input, host-bound output
+    DevBuf dicc_tab;                       // ICC stage: the launch's curve tables (icc_blob as uploaded)
+    std::vector<uint8_t> icc_blob;
     DevBuf dpix_in;                        // encode from pixels: the host's packed rows
     HostBuf hstage1, hstage2;
     int16_t* nmse_tab = nullptr;   // device copy of the nmsedec tables (4 x 128)
@@ -5193,6 +5268,65 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
         for (int k = 0; k < 3; ++k) { a.dst[k] = dst[k]; a.ds[k] = dstr[k]; }
         a.w = ow; a.h = oh; a.vec_store = vec;
         gk_launch_cmyk_rgb(st, stype, dtype, a);
+    } else if (D.stage == DisplayOut::ICC || D.stage == DisplayOut::LAB) {
+        const uint32_t p = D.src_prec;
+        uint32_t ncv = 3;
+        if (D.stage == DisplayOut::LAB) {
+            GkLabArgs a{};
+            for (int k = 0; k < 3; ++k) {
+                a.src[k] = src + coff[D.ch[k].src]; a.ss[k] = cstr[D.ch[k].src];
+                a.dst[k] = dst[k]; a.ds[k] = dstr[k];
+                a.lo[k] = D.lab_lo[k]; a.range[k] = D.lab_range[k];
+            }
+            a.w = ow; a.h = oh; a.vmax = (double)((1u << p) - 1); a.vec_store = vec;
+            gk_inv3(GK_SRGB_COLORANTS, a.m);
+            gk_launch_lab_rgb(st, stype, dtype, a);
+        } else {
+            const GkIccTransform& T = D.icc;
+            ncv = T.grey ? 1 : 3;
+            GkIccArgs a{};
+            for (uint32_t k = 0; k < ncv; ++k) {
+                a.src[k] = src + coff[D.ch[k].src]; a.ss[k] = cstr[D.ch[k].src];
+                a.dst[k] = dst[k]; a.ds[k] = dstr[k];
+            }
+            a.w = ow; a.h = oh; a.nch = ncv; a.prec = p; a.vec_store = vec;
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) a.m[i][j] = T.m[i][j];
+            // the launch's table: a linearisation table per channel up to 8 bits, the `curv` tables above
+            const bool dbl = p > GK_ICC_FLOAT_PREC;
+            std::vector<double> tab;
+            for (uint32_t k = 0; k < ncv; ++k) {
+                const GkIccCurve& cv = T.curve[k];
+                GkIccChan& h = a.ch[k];
+                h.off = (uint32_t)tab.size();
+                if (p <= 8) {
+                    h.kind = GK_ICC_LUT; h.n = 1u << p;
+                    for (uint32_t v = 0; v < h.n; ++v) tab.push_back(cv.eval(v, h.n - 1));
+                } else if (cv.kind == GkIccCurve::TABLE) {
+                    h.kind = GK_ICC_TABLE; h.n = (uint32_t)cv.table.size();
+                    for (uint16_t e : cv.table) tab.push_back((double)e);   // (the 16-bit entries as they are)
+                } else {
+                    h.kind = cv.kind == GkIccCurve::PARA ? GK_ICC_PARA : GK_ICC_IDENTITY;
+                    h.g = cv.g; h.a = cv.a; h.b = cv.b; h.c = cv.c; h.d = cv.d; h.e = cv.e; h.f = cv.f;
+                }
+            }
+            a.table_elems = (uint32_t)tab.size();
+            if (!tab.empty()) {
+                ctx->icc_blob.resize(tab.size() * (dbl ? 8 : 4));
+                if (dbl) memcpy(ctx->icc_blob.data(), tab.data(), tab.size() * 8);
+                else for (size_t i = 0; i < tab.size(); ++i) { const float f = (float)tab[i]; memcpy(ctx->icc_blob.data() + 4 * i, &f, 4); }
+                void* dt = ctx->dicc_tab.get(ctx->icc_blob.size());
+                HIPCHK(hipMemcpyAsync(dt, ctx->icc_blob.data(), ctx->icc_blob.size(), hipMemcpyHostToDevice, st));
+                a.table = dt;
+            }
+            gk_launch_icc_rgb(st, stype, dtype, a);
+        }
+        for (uint32_t k = ncv; k < nout; ++k) {   // the channels beside the colours (opacity): copied
+            GkUpArgs a{};
+            a.src = src + coff[D.ch[k].src]; a.ss = cstr[D.ch[k].src];
+            a.dst = dst[k]; a.ds = dstr[k];
+            a.w = ow; a.h = oh; a.dx = 1; a.dy = 1; a.vec_store = vec;
+            gk_launch_upsample(st, stype, dtype, a);
+        }
     } else {
         const uint64_t cx0 = (uint64_t)W.x0 + (win ? win[0] : 0), cy0 = (uint64_t)W.y0 + (win ? win[1] : 0);
         for (uint32_t k = 0; k < nout; ++k) {   // (a component at 1 x 1 is copied)
@@ -6714,7 +6848,7 @@ int gk_set_decode_colour(gk_ctx* ctx, int apply) {
 
 int gk_set_decode_display(gk_ctx* ctx, uint32_t flags) {
     if (!ctx) return -1;
-    if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB)) { ctx->err = "gk_set_decode_display: unknown flags"; return -1; }
+    if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB | GK_DISPLAY_ICC)) { ctx->err = "gk_set_decode_display: unknown flags"; return -1; }
     ctx->dec_display = flags;
     return 0;
 }
@@ -6737,7 +6871,7 @@ int gk_probe_output(const uint8_t* cs, size_t len, uint32_t flags, uint32_t redu
                     uint32_t cap, char* msg, size_t msg_cap) {
     if (!cs) return -1;
     try {
-        if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB)) throw GkError("gk_probe_display: unknown flags");
+        if (flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB | GK_DISPLAY_ICC)) throw GkError("gk_probe_display: unknown flags");
         if (n && !list) throw GkError("gk_probe_output: no list");
         const std::vector<gk_precision> plist(list, list + n);
         if (reduce >= GK_MAXRLVLS) throw GkError("reduce must be less than the number of resolutions");
@@ -6946,6 +7080,27 @@ int gk_probe_icc(const uint8_t* cs, size_t len, uint8_t* buf, size_t cap, size_t
     } catch (const GkError&) {
         return -1;
     }
+}
+int gk_probe_cielab(const uint8_t* cs, size_t len, uint32_t words[9], uint32_t* n) {
+    if (!cs) return -1;
+    try {
+        ByteSrc S; S.len = len; S.host = cs;
+        size_t joff = 0, jlen = 0;
+        Jp2Colour col;
+        jp2_locate(S, joff, jlen, &col);
+        if (n) *n = (uint32_t)col.lab.size();
+        if (words) std::copy(col.lab.begin(), col.lab.end(), words);
+        return 0;
+    } catch (const GkError&) {
+        return -1;
+    }
+}
+int gk_header_cielab(gk_ctx* ctx, uint32_t words[9], uint32_t* n) {
+    if (!ctx) return -1;
+    const std::vector<uint32_t>& lab = ctx->hdr_col.lab;
+    if (n) *n = (uint32_t)lab.size();
+    if (words) std::copy(lab.begin(), lab.end(), words);
+    return 0;
 }
 
 int gk_header_components(gk_ctx* ctx, uint32_t* dx, uint32_t* dy, uint32_t* prec, uint32_t* sgnd, uint32_t cap) {

@@ -209,3 +209,45 @@ struct GkUnpixArgs {
 };
 // es: bytes per sample (1, 2 or 4)
 void gk_launch_unpixels(hipStream_t st, int es, const GkUnpixArgs& args);
+// Colour management of the display stage (gk_icc.hip): a JP2 file's ICC profile (colr METH 2,
+// matrix / tone-curve classes; gk_icc.h reads it) and the CIELab enumerated space (EnumCS 14)
+// to sRGB, as color_apply_icc_profile / color_cielab_to_rgb (bin/common/color.cpp:423-964) on
+// v / (2^prec - 1).  Source planes are the engine's own (aligned to GK_PAL_PIX samples).
+enum GkIccKind { GK_ICC_IDENTITY = 0, GK_ICC_PARA = 1, GK_ICC_TABLE = 2, GK_ICC_LUT = 3 };
+struct GkIccChan {
+    uint32_t kind;             // GkIccKind
+    uint32_t off, n;           // TABLE (n >= 2 16-bit entries over [0, 1], interpolated) / LUT (the value of sample v at v):
+                               // n elements of the launch's table from element off on
+    uint32_t pad_;
+    double g, a, b, c, d, e, f;   // PARA: x >= d ? pow(a * x + b, g) + e : c * x + f
+};
+struct GkIccArgs {
+    const void* src[3];        // R, G, B (nch = 3) or the grey channel (nch = 1): w x h
+    uint32_t ss[3];
+    void* dst[3];
+    uint32_t ds[3];
+    uint32_t w, h, nch, prec;
+    GkIccChan ch[3];
+    double m[3][3];            // curve output -> linear sRGB (unused when nch = 1)
+    const void* table;         // device memory: table_elems floats (prec <= GK_ICC_FLOAT_PREC) or doubles
+    uint32_t table_elems;
+    uint32_t vec_store;
+    uint32_t rows;             // (set by the launcher)
+};
+#define GK_ICC_FLOAT_PREC 12u      // samples of up to this many bits are evaluated in float32, wider ones in double
+#define GK_ICC_LDS_BYTES 32768u    // curve tables up to this size are staged in LDS, larger ones read from global memory
+// Returns 1 when the table was staged in LDS, 0 when it is read from global memory (or there is none).
+int gk_launch_icc_rgb(hipStream_t st, int stype, int dtype, const GkIccArgs& args);
+struct GkLabArgs {
+    const void* src[3];        // L*, a*, b*: w x h, row stride ss samples
+    uint32_t ss[3];
+    void* dst[3];              // R, G, B at 16 bits
+    uint32_t ds[3];
+    uint32_t w, h;
+    double lo[3], range[3];    // value = lo + v * range / vmax
+    double vmax;               // 2^prec - 1
+    double m[3][3];            // XYZ -> linear sRGB: the inverse of the sRGB colorants (gk_icc.h)
+    uint32_t vec_store;
+    uint32_t rows;
+};
+void gk_launch_lab_rgb(hipStream_t st, int stype, int dtype, const GkLabArgs& args);

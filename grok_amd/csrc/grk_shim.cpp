@@ -733,6 +733,23 @@ bool grk_decompress_read_header(grk_codec* codec, grk_header_info* hi) {
             }
             m->color.icc_profile_len = (uint32_t)n;
             C->out->img.meta = m;
+        } else if (C->colour.colour_space == GRK_CLRSPC_DEFAULT_CIE || C->colour.colour_space == GRK_CLRSPC_CUSTOM_CIE) {
+            // CIELab: the parameter words travel in icc_profile_buf with a length of zero (read_colr :1076-1123)
+            uint32_t words[9] = {0}, nw = 0;
+            if (gk_probe_cielab(C->data.data(), C->data.size(), words, &nw) != 0 || nw < 2) {
+                error("cannot read the CIELab parameters");
+                return false;
+            }
+            grk_image_meta* m = grk_image_meta_new();
+            m->color.icc_profile_buf = (uint8_t*)malloc(nw * sizeof(uint32_t));
+            if (!m->color.icc_profile_buf) {
+                grk_object_unref(&m->obj);
+                error("cannot read the CIELab parameters");
+                return false;
+            }
+            memcpy(m->color.icc_profile_buf, words, nw * sizeof(uint32_t));
+            m->color.icc_profile_len = 0;
+            C->out->img.meta = m;
         }
     }
     if (hi) {

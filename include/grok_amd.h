@@ -186,7 +186,7 @@ int gk_jp2_header(gk_ctx* ctx, const gk_image_info* info, uint64_t cs_len, uint8
  * One effect reaches the codestream, raw or wrapped: sYCC and e-sYCC clear the MCT
  * (CodeStreamCompress.cpp:494-500).
  * Refused, each by name: GRK_CLRSPC_UNKNOWN and values Grok errors on; GRK_CLRSPC_DEFAULT_CIE (EnumCS
- * 14, which the decoder refuses); GRK_CLRSPC_ICC without a profile; a profile with another colour
+ * 14: CIELab is read, not written); GRK_CLRSPC_ICC without a profile; a profile with another colour
  * space (Grok drops it silently); typ / asoc for another component count; a cdef whose
  * color_channels exceed the component count; and every box the engine's own reader refuses
  * (gk_probe_colour's messages: NE outside 1..1024, NPC 0, a column above 16 bits, a LUT value
@@ -290,7 +290,8 @@ int gk_header_components(gk_ctx* ctx, uint32_t* dx, uint32_t* dy, uint32_t* prec
  * widest channel).  Files without pclr + cmap / cdef, and raw codestreams, decode as before. */
 #define GK_MAX_CHANNELS 256   /* channels described in gk_colour_info (more are counted, not described) */
 typedef struct gk_colour_info {
-    uint32_t colour_space;     /* GRK_COLOR_SPACE: 0 unknown, 2 sRGB, 3 grey, 4 sYCC, 5 e-YCC, 6 CMYK, 9 ICC */
+    uint32_t colour_space;     /* GRK_COLOR_SPACE: 0 unknown, 2 sRGB, 3 grey, 4 sYCC, 5 e-YCC, 6 CMYK, 7 default CIELab,
+                                  8 custom CIELab (colr EnumCS 14; gk_header_cielab), 9 ICC */
     uint32_t enumcs;           /* colr EnumCS as read (METH 1), else 0 */
     uint32_t meth;             /* colr METH of the accepted box (1 / 2), 0: none accepted */
     uint32_t icc_len;          /* bytes of the METH 2 profile (gk_header_icc) */
@@ -304,7 +305,8 @@ typedef struct gk_colour_info {
                                          without a cdef Grok's defaults: colour 1..3, then unspecified */
     uint32_t display_applied;  /* gk_set_decode_display: GK_DISPLAY_RGB set when a conversion to RGB runs,
                                   GK_DISPLAY_UPSAMPLE when components are upsampled, GK_DISPLAY_FORCE_RGB when
-                                  a grey channel is replicated (0 without flags) */
+                                  a grey channel is replicated, GK_DISPLAY_ICC when an ICC profile or CIELab is
+                                  converted to sRGB (0 without flags) */
 } gk_colour_info;
 /* Colour description of host codestream / JP2 bytes, no device needed (like gk_probe_header);
  * < 0 with the reason, naming the box, in msg. */
@@ -320,6 +322,14 @@ int gk_header_colour(gk_ctx* ctx, gk_colour_info* info);
 /* Its ICC profile (colr METH 2; grk_image_meta's color.icc_profile_buf): *len receives the size,
  * the bytes are copied when cap holds them (-2 otherwise). */
 int gk_header_icc(gk_ctx* ctx, uint8_t* buf, size_t cap, size_t* len);
+/* The CIELab parameters of that stream (colr EnumCS 14) as Grok keeps them in icc_profile_buf
+ * (FileFormatDecompress::read_colr :1076-1123): 14, GRK_DEFAULT_CIELAB_SPACE (0x44454600) or
+ * GRK_CUSTOM_CIELAB_SPACE (0), then rl, ol, ra, oa, rb, ob, il.  *n receives the word count: 2 for
+ * the 7-byte box (and any other size but 35: the default space), 9 for the 35-byte one, 0 for a
+ * stream that is not CIELab. */
+int gk_header_cielab(gk_ctx* ctx, uint32_t words[9], uint32_t* n);
+/* The same for host JP2 bytes, no device needed. */
+int gk_probe_cielab(const uint8_t* cs, size_t len, uint32_t words[9], uint32_t* n);
 /* apply = 1 (default): later gk_decode_header / gk_decode / gk_decode_window calls apply the
  * palette and channel definition.  apply = 0: they return the codestream's components untouched
  * (the colour description is still read). */
@@ -360,6 +370,37 @@ int gk_set_decode_colour(gk_ctx* ctx, int apply);
  * convert image to RGB colorspace"): unknown (a raw codestream of >= 3 components), sYCC or CMYK
  * left unconverted (add GK_DISPLAY_RGB), e-sYCC, ICC, CIELab. */
 #define GK_DISPLAY_FORCE_RGB 4u
+/* GK_DISPLAY_ICC: colour management, where postProcess does it (:1390-1443): after the
+ * GK_DISPLAY_RGB conversions, before GK_DISPLAY_FORCE_RGB, the upsampling, the precision list and
+ * the pixel pack.  A tensor cannot embed a profile, so this is the CLI's behaviour for an output
+ * format that cannot either.
+ * A file whose colr box carries an ICC profile (METH 2; color_apply_icc_profile,
+ * bin/common/color.cpp:423-776) of the two classes Part 1 allows there: channels 0..2 (data colour
+ * space 'RGB ', rXYZ / gXYZ / bXYZ + rTRC / gTRC / bTRC) or channel 0 ('GRAY', kTRC) become sRGB at
+ * the same precision p: v / (2^p - 1) -> tone curve -> colorants -> inverse of lcms2's sRGB
+ * colorants -> clip to [0, 1] -> sRGB encoding -> * (2^p - 1), rounded half up, p = 1..16.  Curves:
+ * 'curv' (identity, gamma, table with linear interpolation) and 'para' types 0..4; the header's
+ * rendering intent changes nothing for these classes.  Further channels (opacity through a cdef)
+ * pass through.  A grey profile takes 1 or 2 channels and leaves the colour space grey (with
+ * GK_DISPLAY_FORCE_RGB the result is replicated: R, G, B, then the other channel, sRGB).
+ * A CIELab file (colr EnumCS 14; color_cielab_to_rgb :779-964): L*, a*, b* through their ranges and
+ * offsets (the default ones, or the 35-byte box's), to XYZ under D50 (the illuminant word has no
+ * effect on lcms2's result), to sRGB; channels 0..2 become 16-bit unsigned.
+ * Above 8 bits Grok's own arithmetic is defective; the engine computes on
+ * v / (2^p - 1) and agrees with lcms2 run unoptimised.
+ * The header calls describe the output (colour space sRGB, or grey for a grey profile; precisions;
+ * display_applied gains this bit when a conversion runs).  A file with neither a METH 2 profile nor
+ * EnumCS 14 is untouched and the bit stays clear; so is an RGB-profile image whose first
+ * min(channels, 4) channels differ in dx / dy / precision / sign, or any image whose channels are
+ * not of one precision and sign (Grok's silent return).
+ * Refused, each by name: bytes that are not a profile (no 'acsp', a size field past the box, a tag
+ * table or a tag outside the profile, a curve count that overruns its tag); a profile with A2B0 /
+ * A2B1 / A2B2 (lcms2 would use the table); a data colour space other than 'RGB ' / 'GRAY'; a
+ * connection space other than 'XYZ '; a missing colorant or curve tag; an unknown curve type; signed
+ * channels; a precision above 16; an RGB profile or CIELab on fewer than 3 channels, a grey profile
+ * on more than 2; subsampled components; a palette; a stream that holds only some of its tiles;
+ * 8 / 16-bit planes that are not (output precision + 7) / 8 bytes (CIELab output is 16-bit). */
+#define GK_DISPLAY_ICC 8u
 int gk_set_decode_display(gk_ctx* ctx, uint32_t flags);
 /* What a decode of host codestream / JP2 bytes under `flags` and `reduce` returns, no device
  * needed: the image info and colour description of the output (either may be NULL), dx / dy /
