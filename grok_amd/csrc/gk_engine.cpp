@@ -3345,30 +3345,14 @@ struct HostBuf {
 
 struct gk_ctx {
     uint32_t dec_layers = 0;   // quality layers to decode (0 = all; grk_dparameters::cp_layer)
-    // JP2 colour boxes (pclr + cmap, cdef): applied on decode (gk_set_decode_colour); col_inner:
-    // the call in progress is the component decode under decode_colour, col_whole: which needs
-    // every tile (its palette stage expands the whole image)
-    bool dec_colour = true, col_inner = false, col_whole = false;
-    // gk_set_decode_display flags; disp_inner: the call in progress is the component decode under
-    // decode_display (which needs every tile as well)
-    uint32_t dec_display = 0;
-    bool disp_inner = false;
-    // gk_set_decode_precision's list; out_inner: the call in progress is the planar decode under
-    // decode_output (display flags and colour boxes still apply to it, GK_DISPLAY_FORCE_RGB and
-    // the list do not); pix: the call in progress is a pixel call and this is its destination
-    std::vector<gk_precision> dec_prec;
-    bool out_inner = false;
-    struct PixDst { void* pixels; size_t row_bytes; };
-    const PixDst* pix = nullptr;
-    DisplayOut hdr_disp;       // what the flags make of the last gk_decode_header's channels
+    bool dec_colour = true;    // JP2 colour boxes (pclr + cmap, cdef): applied on decode (gk_set_decode_colour)
+    uint32_t dec_display = 0;  // gk_set_decode_display flags
+    std::vector<gk_precision> dec_prec;   // gk_set_decode_precision's list
+    DisplayOut hdr_disp;      // what the flags make of the last gk_decode_header's channels
     Jp2Colour hdr_col;         // the last gk_decode_header's colour boxes and output channels
     ColourOut hdr_out;
     uint32_t hdr_ncs = 0;      // its codestream component count
     std::vector<uint8_t> col_blob;   // palette stage: channel table + palette as uploaded
-    // the decode in progress has a window: Grok then takes its partial-tile inverse
-    // (CodeStreamDecompress.cpp:389, WaveletReverse.cpp:2237-2246), whose 5/3 single odd sample
-    // across is H >> 1 (:1551-1554) where the whole-tile path has H / 2 (:583)
-    bool dwt_partial = false;
     uint32_t dec_reduce = 0;   // highest resolutions discarded on decode (grk_dparameters::cp_reduce)
     bool win_whole_tile = false;   // gk_set_window_rule: windows keep the whole-tile inverse DWT rule
     int device = 0;
@@ -3590,8 +3574,10 @@ struct L1Io {
 // level is one launch per tile shape with the components in grid.z.
 // lstop (inverse only): the last level undone (1 = full resolution; reduced-resolution decode
 // stops at reduce + 1, leaving resolution numres - 1 - reduce at the tiles' corners)
+// partial (inverse only): the call's inverse rule (DecReq)
 static void run_dwt(gk_ctx* ctx, const Region& RG, bool forward, uint32_t jb = 0, uint32_t je = 0xffffffffu,
-                    uint32_t ib = 0, uint32_t ie = 0xffffffffu, const L1Io* io = nullptr, uint32_t lstop = 1) {
+                    uint32_t ib = 0, uint32_t ie = 0xffffffffu, const L1Io* io = nullptr, uint32_t lstop = 1,
+                    bool partial = false) {
     Plan& P = ctx->plan;
     int32_t* arena = (int32_t*)ctx->arena.p;
     const uint64_t cst = 2 * (uint64_t)RG.plane;   // component plane pairs
@@ -3635,7 +3621,7 @@ static void run_dwt(gk_ctx* ctx, const Region& RG, bool forward, uint32_t jb = 0
                 int32_t* dst_l = (l & 1) ? B : A;
                 const uint64_t area = (uint64_t)w * h * S.tb.count();
                 gk_launch_dwt_any(ctx->st, irrev, forward, forward ? src_l : dst_l, forward ? dst_l : src_l, RG.stride,
-                                  w, h, S.parx[l - 1], S.pary[l - 1], S.tb, GkComps{cst, ncr}, !forward && ctx->dwt_partial);
+                                  w, h, S.parx[l - 1], S.pary[l - 1], S.tb, GkComps{cst, ncr}, !forward && partial);
                 ctx->tm.dwt_launches += 3;
                 ctx->tm.dwt_bytes += area * 8 * ncr;
                 continue;
@@ -5044,88 +5030,157 @@ static void merge_tile_parts(Header& Hd) {
     Hd.parts.swap(out);
 }
 
-// A pass over some of the stream's tiles (tiles coded with their own parameters): the tiles it
-// decodes, their coding (else the main header's), the output frame's origin (image-relative; the
-// caller's window origin) and the inverse rule of the whole call
-struct TilePass {
-    std::vector<uint8_t> tiles;   // by tile index: decoded in this pass
-    const TileCoding* coding = nullptr;
-    uint32_t fx = 0, fy = 0;
-    bool partial = false;
+// ---- One decode call.  The entry points fill these once; the stages pass them down by reference
+// and the chain only goes down: decode_call -> decode_output -> decode_planes -> decode_display or
+// decode_colour -> decode_components -> decode_core.
+using HostClock = std::chrono::steady_clock;
+namespace {
+// the bytes as the caller gave them
+struct DecSrc { const uint8_t* cs; size_t len; bool on_device; };
+// where the samples go: planes with their strides, or (a pixel call) one interleaved buffer
+struct DecDst {
+    void* const* comps; const uint32_t* strides;
+    void* pixels; size_t row_bytes;
+    uint32_t sample_bytes; bool on_device;
 };
-static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
-                        const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
-                        const TilePass* pass);
+// what is asked for: the window (image-relative x0, y0, x1, y1; null: the image) and the inverse
+// rule.  partial: the call has a window, and Grok then takes its partial-tile inverse
+// (CodeStreamDecompress.cpp:389, WaveletReverse.cpp:2237-2246), whose 5/3 single odd sample
+// across is H >> 1 (:1551-1554) where the whole-tile path has H / 2 (:583)
+struct DecReq { const uint32_t* win; bool partial; };
+// the stages between here and the component decode: the display flags as resolved for this level
+// (null: none; decode_planes applies them when they are active, colour boxes otherwise), and the
+// stage above that reads the whole image and so cannot take a stream with only some of its tiles
+struct DecStages {
+    const DisplayOut* display = nullptr;
+    enum Whole { ANY, OUTPUT, DISPLAY, PALETTE } whole = ANY;
+};
+// the stream as opened once per call: the codestream's bytes (of a JP2 file: its box), the
+// file's colour boxes and the parsed main header; t0 is GK_PROFILE's start of the host phases
+struct DecStream {
+    ByteSrc S;
+    Jp2Colour col;
+    Header Hd;
+    bool jp2 = false;
+    HostClock::time_point t0 = HostClock::now();
+};
+}  // namespace
+static void open_stream(DecStream& o, const DecSrc& src, hipStream_t st, bool colour) {
+    auto bytes = [&](size_t off, size_t len) {
+        o.S = ByteSrc(); o.S.len = len; o.S.st = st;
+        if (src.on_device) o.S.dev = src.cs + off; else o.S.host = src.cs + off;
+    };
+    bytes(0, src.len);
+    size_t joff = 0, jlen = 0;
+    o.jp2 = jp2_locate(o.S, joff, jlen, colour ? &o.col : nullptr);
+    if (o.jp2) bytes(joff, jlen);   // JP2 file: decode its codestream box
+    parse_header(o.S, o.Hd);
+}
+// its output channels: those of the colour boxes when they apply, else the components
+static ColourOut stream_channels(const DecStream& o, bool apply) {
+    const Jp2Colour none;
+    return resolve_colour(apply ? o.col : none, o.Hd.want);
+}
+static void decode_components(gk_ctx* ctx, DecStream& o, const DecDst& dst, const DecReq& rq, DecStages::Whole whole);
+
+// ---- what the stages share.  The planes a stage's inner decode writes and its kernel reads have
+// one sign -> the 8 / 16-bit type of the largest precision, else int32 (signed 8 / 16-bit planes
+// take the same bits as unsigned ones where a stage only copies them)
+static uint32_t stage_sample_bytes(bool any_signed, uint32_t prec) { return (!any_signed && prec <= 16) ? (prec + 7) / 8 : 4; }
+static int stage_type(uint32_t sb) { return sb == 1 ? GK_U8 : sb == 2 ? GK_U16 : GK_S32; }
+// Engine-owned source planes in buf, one per entry of w / h: rows padded to 16 samples for the
+// kernels' vector accesses, planes to 256 bytes.  dst() is the inner decode's destination.
+struct StagePlanes {
+    std::vector<void*> p;
+    std::vector<uint32_t> stride;
+    uint32_t sb = 4;
+    uint8_t* at(uint32_t j) const { return (uint8_t*)p[j]; }
+    DecDst dst() const { return DecDst{p.data(), stride.data(), nullptr, 0, sb == 4 ? 0 : sb, true}; }
+};
+static StagePlanes stage_planes(DevBuf& buf, const std::vector<uint32_t>& w, const std::vector<uint32_t>& h, uint32_t sb) {
+    const size_t n = w.size(), es = gk_sample_size(stage_type(sb));
+    StagePlanes S;
+    S.sb = sb; S.p.resize(n); S.stride.resize(n);
+    std::vector<size_t> off(n);
+    size_t total = 0;
+    for (size_t j = 0; j < n; ++j) {
+        S.stride[j] = (w[j] + 15) & ~15u;
+        off[j] = total;
+        total += (((size_t)S.stride[j] * h[j] * es) + 255) & ~(size_t)255;
+    }
+    uint8_t* base = (uint8_t*)buf.get(total);
+    for (size_t j = 0; j < n; ++j) S.p[j] = base + off[j];
+    return S;
+}
+// Destination planes of a stage's kernel, nout of ow x oh: the caller's device planes, or a
+// staging in buf that stage_to_host copies to the caller's host planes; vec: every plane takes
+// the kernels' vector stores
+struct StageDst {
+    std::vector<uint8_t*> p;
+    std::vector<uint32_t> stride;
+    uint32_t pstride = 0, vec = 1;
+};
+static StageDst stage_dst(DevBuf& buf, const DecDst& dst, uint32_t nout, uint32_t ow, uint32_t oh, size_t es) {
+    StageDst D;
+    D.p.resize(nout); D.stride.resize(nout);
+    D.pstride = (ow + 15) & ~15u;
+    if (dst.on_device) {
+        for (uint32_t k = 0; k < nout; ++k) { D.p[k] = (uint8_t*)dst.comps[k]; D.stride[k] = dst.strides[k]; }
+    } else {
+        const size_t plane = (((size_t)D.pstride * oh * es) + 255) & ~(size_t)255;
+        uint8_t* stage = (uint8_t*)buf.get(plane * nout);
+        for (uint32_t k = 0; k < nout; ++k) { D.p[k] = stage + plane * k; D.stride[k] = D.pstride; }
+    }
+    for (uint32_t k = 0; k < nout; ++k)
+        if (((uintptr_t)D.p[k] % (GK_PAL_PIX * es)) || (D.stride[k] % GK_PAL_PIX)) D.vec = 0;
+    return D;
+}
+static void stage_to_host(hipStream_t st, const DecDst& dst, const StageDst& D, uint32_t ow, uint32_t oh, size_t es) {
+    if (dst.on_device) return;
+    for (size_t k = 0; k < D.p.size(); ++k)
+        HIPCHK(hipMemcpy2DAsync(dst.comps[k], (size_t)dst.strides[k] * es, D.p[k], (size_t)D.pstride * es, (size_t)ow * es, oh,
+                                hipMemcpyDeviceToHost, st));
+}
+
 // Decode of a JP2 file whose colour boxes apply (FileFormatDecompress::applyColour :378-401).
 // A cdef alone costs nothing: the caller's plane pointers are permuted and the components are
 // decoded straight into them.  With a palette the components are decoded into engine-owned
 // planes of the narrowest sample type the egress writes and k_jp2_palette (gk_colour.hip)
 // expands them into the caller's planes on the same stream; only the samples of the decoded
 // rectangle (the image, the window, either reduced) are expanded.
-static void decode_colour(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
-                          const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
-                          const Jp2Colour& C, const ColourOut& O, const Plan& W) {
-    struct Inner {
-        gk_ctx* c;
-        Inner(gk_ctx* c_, bool whole) : c(c_) { c->col_inner = true; c->col_whole = whole; }
-        ~Inner() { c->col_inner = false; c->col_whole = false; }
-    };
+static void decode_colour(gk_ctx* ctx, DecStream& o, const DecDst& dst, const DecReq& rq, const ColourOut& O,
+                          DecStages::Whole whole) {
+    const Jp2Colour& C = o.col;
+    const Plan& W = o.Hd.want;
+    const uint32_t* win = rq.win;
+    const uint32_t sample_bytes = dst.sample_bytes;
     const uint32_t nout = (uint32_t)O.ch.size();
     if (!O.palette) {   // the channels are a permutation of the components
         std::vector<void*> cp(W.nc, nullptr);
         std::vector<uint32_t> sp(W.nc, 0);
-        for (uint32_t k = 0; k < nout; ++k) { cp[O.ch[k].src] = comps[k]; sp[O.ch[k].src] = strides[k]; }
-        Inner in(ctx, false);
-        decode_impl(ctx, cs, len, cs_on_device, cp.data(), sp.data(), sample_bytes, out_on_device, win, nullptr);
+        for (uint32_t k = 0; k < nout; ++k) { cp[O.ch[k].src] = dst.comps[k]; sp[O.ch[k].src] = dst.strides[k]; }
+        decode_components(ctx, o, DecDst{cp.data(), sp.data(), nullptr, 0, sample_bytes, dst.on_device}, rq, whole);
         return;
     }
     hipStream_t st = ctx->st;
-    const uint32_t red = ctx->dec_reduce;
-    auto cdp = [&](uint64_t v) { return (uint32_t)((v + ((1ull << red) - 1)) >> red); };
+    if (win && (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h)) throw GkError("bad decode window");
     uint32_t ow, oh;
-    if (win) {
-        if (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h) throw GkError("bad decode window");
-        ow = cdp((uint64_t)win[2] + W.x0) - cdp((uint64_t)win[0] + W.x0);
-        oh = cdp((uint64_t)win[3] + W.y0) - cdp((uint64_t)win[1] + W.y0);
-        if (!ow || !oh) throw GkError("the window is empty at this reduction");
-    } else {
-        ow = cdp((uint64_t)W.x0 + W.w) - cdp(W.x0);
-        oh = cdp((uint64_t)W.y0 + W.h) - cdp(W.y0);
-    }
+    comp_dims(W, 1, 1, ctx->dec_reduce, win, ow, oh);
+    if (win && (!ow || !oh)) throw GkError("the window is empty at this reduction");
     // component planes: one sign -> the 8 / 16-bit type of the largest precision, else int32
     bool any_signed = false;
     for (uint32_t c = 0; c < W.nc; ++c) any_signed = any_signed || W.c_sgnd(c);
-    const uint32_t sb_in = (!any_signed && W.prec <= 16) ? (W.prec + 7) / 8 : 4;
-    const int stype = sample_type(sb_in, W.prec, false);
+    const uint32_t sb_in = stage_sample_bytes(any_signed, W.prec);
+    const int stype = stage_type(sb_in);
     bool direct_signed = false;
     for (const auto& h : O.ch) direct_signed = direct_signed || (h.direct && W.c_sgnd(h.src));
     if ((sample_bytes == 1 || sample_bytes == 2) && direct_signed)
         throw GkError("8 / 16-bit output of a signed component beside palette channels: use int32 planes");
     const int dtype = sample_type(sample_bytes, O.max_prec(), false);
-    const size_t es_in = gk_sample_size(stype), es_out = gk_sample_size(dtype);
-    const uint32_t pstride = (ow + 15) & ~15u;   // rows aligned for the kernel's vector accesses
-    const size_t plane_in = (((size_t)pstride * oh * es_in) + 255) & ~(size_t)255;
-    uint8_t* src = (uint8_t*)ctx->dcol_src.get(plane_in * W.nc);
-    {
-        std::vector<void*> cp(W.nc);
-        std::vector<uint32_t> sp(W.nc, pstride);
-        for (uint32_t c = 0; c < W.nc; ++c) cp[c] = src + plane_in * c;
-        Inner in(ctx, true);
-        decode_impl(ctx, cs, len, cs_on_device, cp.data(), sp.data(), sb_in == 4 ? 0 : sb_in, 1, win, nullptr);
-    }
-    // destination planes: the caller's device planes, or a staging copied to the host afterwards
-    std::vector<uint8_t*> dst(nout);
-    std::vector<uint32_t> dstr(nout);
-    const size_t plane_out = (((size_t)pstride * oh * es_out) + 255) & ~(size_t)255;
-    if (out_on_device) {
-        for (uint32_t k = 0; k < nout; ++k) { dst[k] = (uint8_t*)comps[k]; dstr[k] = strides[k]; }
-    } else {
-        uint8_t* stage = (uint8_t*)ctx->dcol_out.get(plane_out * nout);
-        for (uint32_t k = 0; k < nout; ++k) { dst[k] = stage + plane_out * k; dstr[k] = pstride; }
-    }
-    uint32_t vec = 1;
-    for (uint32_t k = 0; k < nout; ++k)
-        if (((uintptr_t)dst[k] % (GK_PAL_PIX * es_out)) || (dstr[k] % GK_PAL_PIX)) vec = 0;
+    const size_t es_out = gk_sample_size(dtype);
+    const StagePlanes src = stage_planes(ctx->dcol_src, std::vector<uint32_t>(W.nc, ow), std::vector<uint32_t>(W.nc, oh), sb_in);
+    decode_components(ctx, o, src.dst(), rq, DecStages::PALETTE);
+    const StageDst out = stage_dst(ctx->dcol_out, dst, nout, ow, oh, es_out);
     // one launch per palette-mapped component (as a rule one); the first takes the direct channels
     std::vector<uint32_t> idx_comps;
     for (const auto& h : O.ch)
@@ -5138,8 +5193,8 @@ static void decode_colour(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
     for (uint32_t k = 0; k < nout; ++k) {
         const ColourOut::Ch& h = O.ch[k];
         GkPalChan pc{};
-        pc.dst = dst[k]; pc.dst_stride = dstr[k]; pc.col = h.col; pc.direct = h.direct ? 1 : 0;
-        pc.src = src + plane_in * h.src; pc.src_stride = pstride;
+        pc.dst = out.p[k]; pc.dst_stride = out.stride[k]; pc.col = h.col; pc.direct = h.direct ? 1 : 0;
+        pc.src = src.at(h.src); pc.src_stride = src.stride[h.src];
         const size_t g = h.direct ? 0 : (size_t)(std::find(idx_comps.begin(), idx_comps.end(), h.src) - idx_comps.begin());
         groups[g].push_back(pc);
     }
@@ -5165,33 +5220,26 @@ static void decode_colour(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
         if (groups[g].empty()) continue;
         GkPalArgs a{};
         a.npal = idx_comps.empty() ? 0 : (uint32_t)groups[g].size();
-        if (!idx_comps.empty()) { a.idx = src + plane_in * idx_comps[g]; a.idx_stride = pstride; }
+        if (!idx_comps.empty()) { a.idx = src.at(idx_comps[g]); a.idx_stride = src.stride[idx_comps[g]]; }
         a.w = ow; a.h = oh;
         a.chans = (const GkPalChan*)dblob + c0; a.nchan = (uint32_t)groups[g].size();
         a.table = (const uint32_t*)(dblob + chan_bytes); a.ne = C.ne; a.entry_words = ew; a.elem_bytes = eb;
-        a.vec_store = vec;
+        a.vec_store = out.vec;
         gk_launch_jp2_palette(st, stype, dtype, a);
         c0 += groups[g].size();
     }
     launch_check(__LINE__);
-    if (!out_on_device)
-        for (uint32_t k = 0; k < nout; ++k)
-            HIPCHK(hipMemcpy2DAsync(comps[k], (size_t)strides[k] * es_out, dst[k], (size_t)pstride * es_out, (size_t)ow * es_out, oh,
-                                    hipMemcpyDeviceToHost, st));
+    stage_to_host(st, dst, out, ow, oh, es_out);
     HIPCHK(hipStreamSynchronize(st));
 }
 // Decode under display flags that apply (gk_set_decode_display; DisplayOut::active): the
 // components are decoded into engine-owned planes of the narrowest sample type, each on its own
 // grid, and one pass of k_ycc_rgb / k_cmyk_rgb / k_upsample (gk_colour.hip) writes the caller's
 // device planes, or a staging that is copied to the host, on the same stream.
-static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
-                           const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
-                           const DisplayOut& D, const Plan& W) {
-    struct Inner {
-        gk_ctx* c;
-        Inner(gk_ctx* c_) : c(c_) { c->col_inner = true; c->col_whole = true; c->disp_inner = true; }
-        ~Inner() { c->col_inner = false; c->col_whole = false; c->disp_inner = false; }
-    };
+static void decode_display(gk_ctx* ctx, DecStream& o, const DecDst& dst, const DecReq& rq, const DisplayOut& D) {
+    const Plan& W = o.Hd.want;
+    const uint32_t* win = rq.win;
+    const uint32_t sample_bytes = dst.sample_bytes;
     hipStream_t st = ctx->st;
     const uint32_t red = ctx->dec_reduce, nc = W.nc, nout = (uint32_t)D.ch.size();
     // output sample type: int32, or the 8 / 16-bit type of the widest output channel
@@ -5209,64 +5257,42 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
     }
     // (signed 8 / 16-bit planes take the same bits as unsigned ones: the stage only copies them)
     const int dtype = sample_bytes == 1 ? GK_U8 : sample_bytes == 2 ? GK_U16 : GK_S32;
-    const uint32_t sb_in = (!any_signed && W.prec <= 16) ? (W.prec + 7) / 8 : 4;
-    const int stype = sb_in == 1 ? GK_U8 : sb_in == 2 ? GK_U16 : GK_S32;
-    const size_t es_in = gk_sample_size(stype), es_out = gk_sample_size(dtype);
-    // component planes, each on its own grid; rows aligned for the kernels' vector loads
-    std::vector<uint32_t> cw(nc), chh(nc), cstr(nc);
-    std::vector<size_t> coff(nc);
-    size_t total = 0;
+    const uint32_t sb_in = stage_sample_bytes(any_signed, W.prec);
+    const int stype = stage_type(sb_in);
+    const size_t es_out = gk_sample_size(dtype);
+    // component planes, each on its own grid
+    std::vector<uint32_t> cw(nc), chh(nc);
     for (uint32_t c = 0; c < nc; ++c) {
         comp_dims(W, W.sx(c), W.sy(c), red, win, cw[c], chh[c]);
         if (!cw[c] || !chh[c]) throw GkError("display: a component without samples in this area");
-        cstr[c] = (cw[c] + 15) & ~15u;
-        coff[c] = total;
-        total += (((size_t)cstr[c] * chh[c] * es_in) + 255) & ~(size_t)255;
     }
-    uint8_t* src = (uint8_t*)ctx->dcol_src.get(total);
-    {
-        std::vector<void*> cp(nc);
-        for (uint32_t c = 0; c < nc; ++c) cp[c] = src + coff[c];
-        Inner in(ctx);
-        decode_impl(ctx, cs, len, cs_on_device, cp.data(), cstr.data(), sb_in == 4 ? 0 : sb_in, 1, win, nullptr);
-    }
+    const StagePlanes src = stage_planes(ctx->dcol_src, cw, chh, sb_in);
+    decode_components(ctx, o, src.dst(), rq, DecStages::DISPLAY);
     // output planes: the image grid after an upsampling, component 0's otherwise
     uint32_t ow = cw[0], oh = chh[0];
     if (D.stage == DisplayOut::UPSAMPLE) comp_dims(W, 1, 1, 0, win, ow, oh);
-    const uint32_t pstride = (ow + 15) & ~15u;
-    std::vector<uint8_t*> dst(nout);
-    std::vector<uint32_t> dstr(nout);
-    const size_t plane_out = (((size_t)pstride * oh * es_out) + 255) & ~(size_t)255;
-    if (out_on_device) {
-        for (uint32_t k = 0; k < nout; ++k) { dst[k] = (uint8_t*)comps[k]; dstr[k] = strides[k]; }
-    } else {
-        uint8_t* stage = (uint8_t*)ctx->dcol_out.get(plane_out * nout);
-        for (uint32_t k = 0; k < nout; ++k) { dst[k] = stage + plane_out * k; dstr[k] = pstride; }
-    }
-    uint32_t vec = 1;
-    for (uint32_t k = 0; k < nout; ++k)
-        if (((uintptr_t)dst[k] % (GK_PAL_PIX * es_out)) || (dstr[k] % GK_PAL_PIX)) vec = 0;
+    const StageDst out = stage_dst(ctx->dcol_out, dst, nout, ow, oh, es_out);
     HIPCHK(hipEventRecord(ctx->ev[20], st));
     if (D.stage == DisplayOut::YCC) {
         GkYccArgs a{};
-        a.y = src + coff[0]; a.cb = src + coff[1]; a.cr = src + coff[2];
-        a.ys = cstr[0]; a.cs = cstr[1];
-        for (int k = 0; k < 3; ++k) { a.dst[k] = dst[k]; a.ds[k] = dstr[k]; }
+        a.y = src.at(0); a.cb = src.at(1); a.cr = src.at(2);
+        a.ys = src.stride[0]; a.cs = src.stride[1];
+        for (int k = 0; k < 3; ++k) { a.dst[k] = out.p[k]; a.ds[k] = out.stride[k]; }
         a.w = ow; a.h = oh; a.mode = D.mode; a.ofx = D.ofx; a.ofy = D.ofy;
         const uint32_t p0 = W.c_prec(0);
         a.offset = 1 << (p0 - 1); a.upb = (int32_t)((1u << p0) - 1);
         a.flip_cb = !W.c_sgnd(1); a.flip_cr = !W.c_sgnd(2);
-        a.vec_store = vec;
+        a.vec_store = out.vec;
         gk_launch_ycc_rgb(st, stype, dtype, a);
     } else if (D.stage == DisplayOut::CMYK) {
         GkCmykArgs a{};
         for (int k = 0; k < 4; ++k) {
-            a.src[k] = src + coff[k];
+            a.src[k] = src.at(k);
             a.scale[k] = 1.0F / (float)((1 << W.c_prec(k)) - 1);
         }
-        a.ss = cstr[0];
-        for (int k = 0; k < 3; ++k) { a.dst[k] = dst[k]; a.ds[k] = dstr[k]; }
-        a.w = ow; a.h = oh; a.vec_store = vec;
+        a.ss = src.stride[0];
+        for (int k = 0; k < 3; ++k) { a.dst[k] = out.p[k]; a.ds[k] = out.stride[k]; }
+        a.w = ow; a.h = oh; a.vec_store = out.vec;
         gk_launch_cmyk_rgb(st, stype, dtype, a);
     } else if (D.stage == DisplayOut::ICC || D.stage == DisplayOut::LAB) {
         const uint32_t p = D.src_prec;
@@ -5274,11 +5300,11 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
         if (D.stage == DisplayOut::LAB) {
             GkLabArgs a{};
             for (int k = 0; k < 3; ++k) {
-                a.src[k] = src + coff[D.ch[k].src]; a.ss[k] = cstr[D.ch[k].src];
-                a.dst[k] = dst[k]; a.ds[k] = dstr[k];
+                a.src[k] = src.at(D.ch[k].src); a.ss[k] = src.stride[D.ch[k].src];
+                a.dst[k] = out.p[k]; a.ds[k] = out.stride[k];
                 a.lo[k] = D.lab_lo[k]; a.range[k] = D.lab_range[k];
             }
-            a.w = ow; a.h = oh; a.vmax = (double)((1u << p) - 1); a.vec_store = vec;
+            a.w = ow; a.h = oh; a.vmax = (double)((1u << p) - 1); a.vec_store = out.vec;
             gk_inv3(GK_SRGB_COLORANTS, a.m);
             gk_launch_lab_rgb(st, stype, dtype, a);
         } else {
@@ -5286,10 +5312,10 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
             ncv = T.grey ? 1 : 3;
             GkIccArgs a{};
             for (uint32_t k = 0; k < ncv; ++k) {
-                a.src[k] = src + coff[D.ch[k].src]; a.ss[k] = cstr[D.ch[k].src];
-                a.dst[k] = dst[k]; a.ds[k] = dstr[k];
+                a.src[k] = src.at(D.ch[k].src); a.ss[k] = src.stride[D.ch[k].src];
+                a.dst[k] = out.p[k]; a.ds[k] = out.stride[k];
             }
-            a.w = ow; a.h = oh; a.nch = ncv; a.prec = p; a.vec_store = vec;
+            a.w = ow; a.h = oh; a.nch = ncv; a.prec = p; a.vec_store = out.vec;
             for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) a.m[i][j] = T.m[i][j];
             // the launch's table: a linearisation table per channel up to 8 bits, the `curv` tables above
             const bool dbl = p > GK_ICC_FLOAT_PREC;
@@ -5322,9 +5348,9 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
         }
         for (uint32_t k = ncv; k < nout; ++k) {   // the channels beside the colours (opacity): copied
             GkUpArgs a{};
-            a.src = src + coff[D.ch[k].src]; a.ss = cstr[D.ch[k].src];
-            a.dst = dst[k]; a.ds = dstr[k];
-            a.w = ow; a.h = oh; a.dx = 1; a.dy = 1; a.vec_store = vec;
+            a.src = src.at(D.ch[k].src); a.ss = src.stride[D.ch[k].src];
+            a.dst = out.p[k]; a.ds = out.stride[k];
+            a.w = ow; a.h = oh; a.dx = 1; a.dy = 1; a.vec_store = out.vec;
             gk_launch_upsample(st, stype, dtype, a);
         }
     } else {
@@ -5332,12 +5358,12 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
         for (uint32_t k = 0; k < nout; ++k) {   // (a component at 1 x 1 is copied)
             const uint32_t dx = W.sx(k), dy = W.sy(k);
             GkUpArgs a{};
-            a.src = src + coff[k]; a.ss = cstr[k];
-            a.dst = dst[k]; a.ds = dstr[k];
+            a.src = src.at(k); a.ss = src.stride[k];
+            a.dst = out.p[k]; a.ds = out.stride[k];
             a.w = ow; a.h = oh; a.dx = dx; a.dy = dy;
             a.xoff = (uint32_t)(((cx0 + dx - 1) / dx) * dx - cx0);
             a.yoff = (uint32_t)(((cy0 + dy - 1) / dy) * dy - cy0);
-            a.vec_store = vec;
+            a.vec_store = out.vec;
             // the last sample read must lie in the component's plane
             if (a.xoff >= dx || a.yoff >= dy || (ow > a.xoff && (ow - 1 - a.xoff) / dx >= cw[k]) ||
                 (oh > a.yoff && (oh - 1 - a.yoff) / dy >= chh[k]))
@@ -5347,13 +5373,32 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
     }
     launch_check(__LINE__);
     HIPCHK(hipEventRecord(ctx->ev[21], st));
-    if (!out_on_device)
-        for (uint32_t k = 0; k < nout; ++k)
-            HIPCHK(hipMemcpy2DAsync(comps[k], (size_t)strides[k] * es_out, dst[k], (size_t)pstride * es_out, (size_t)ow * es_out, oh,
-                                    hipMemcpyDeviceToHost, st));
+    stage_to_host(st, dst, out, ow, oh, es_out);
     HIPCHK(hipStreamSynchronize(st));
     const float ms = ev_ms(ctx, 20, 21);   // the display pass counts as sample stage
     ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+}
+// The display flags `flags` as they resolve on this stream (list: gk_set_decode_precision's, for
+// the level that owns the output stage)
+static DisplayOut call_display(gk_ctx* ctx, const DecStream& o, uint32_t flags, const uint32_t* win,
+                               const std::vector<gk_precision>* list) {
+    return resolve_display(o.col, stream_channels(o, ctx->dec_colour), o.Hd.want, flags, ctx->dec_reduce, win, list);
+}
+// The caller's planes: through the display stage when the flags make a conversion or an
+// upsampling that applies, else through colour boxes that change the channels, else the components
+static void decode_planes(gk_ctx* ctx, DecStream& o, const DecDst& dst, const DecReq& rq, const DecStages& stg) {
+    if (stg.display && stg.display->active()) {
+        decode_display(ctx, o, dst, rq, *stg.display);
+        return;
+    }
+    if (ctx->dec_colour && o.col.jp2 && (o.col.has_pclr || o.col.has_cdef)) {
+        const ColourOut co = resolve_colour(o.col, o.Hd.want);
+        if (co.active()) {
+            decode_colour(ctx, o, dst, rq, co, stg.whole);
+            return;
+        }
+    }
+    decode_components(ctx, o, dst, rq, stg.whole);
 }
 // The output stage (DisplayOut::out_active, and every pixel call): the image is decoded as the
 // display flags and colour boxes make it (GK_DISPLAY_FORCE_RGB and the precision list set aside)
@@ -5361,16 +5406,12 @@ static void decode_display(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on
 // once: forced precision, grey to RGB, and either packed pixels or, one launch per channel, the
 // caller's planes.  An image that needs no conversion, upsampling or palette is decoded straight
 // into those planes (one pass after the decode); the others go through their kernel first (two).
-static void decode_output(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
-                          const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win,
-                          const DisplayOut& D, const Plan& W) {
-    struct Inner {
-        gk_ctx* c; const gk_ctx::PixDst* pix;
-        Inner(gk_ctx* c_) : c(c_), pix(c_->pix) { c->out_inner = true; c->pix = nullptr; }
-        ~Inner() { c->out_inner = false; c->pix = pix; }
-    };
+static void decode_output(gk_ctx* ctx, DecStream& o, const DecDst& dst, const DecReq& rq, const DisplayOut& D) {
+    const Plan& W = o.Hd.want;
+    const uint32_t* win = rq.win;
+    const uint32_t sample_bytes = dst.sample_bytes;
+    const bool out_on_device = dst.on_device, pix = dst.pixels != nullptr;
     hipStream_t st = ctx->st;
-    const gk_ctx::PixDst* pix = ctx->pix;
     const uint32_t nout = (uint32_t)D.ch.size(), nst = D.nstage;
     const uint32_t red = D.upsampled ? 0 : ctx->dec_reduce;
     // every refusal first: nothing is allocated or launched before the call is known to be sound
@@ -5389,7 +5430,7 @@ static void decode_output(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
     const int dtype = sample_bytes == 1 ? GK_U8 : sample_bytes == 2 ? GK_U16 : GK_S32;
     const size_t es_out = gk_sample_size(dtype);
     // the stage's channels (those the inner decode writes) and their planes
-    std::vector<uint32_t> sw(nst), sh(nst), sstr(nst), sprec(nst, 0);
+    std::vector<uint32_t> sw(nst), sh(nst), sprec(nst, 0);
     bool st_signed = false;
     for (const auto& h : D.ch) {
         comp_dims(W, h.dx, h.dy, red, win, sw[h.from], sh[h.from]);
@@ -5406,34 +5447,30 @@ static void decode_output(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
             if (sw[j] != sw[0] || sh[j] != sh[0])
                 throw GkError("pixels: output channels of different sizes (subsampled components): set GK_DISPLAY_UPSAMPLE");
         const size_t need = (size_t)sw[0] * nout * es_out;
-        if (pix->row_bytes < need)
-            throw GkError("pixels: row_bytes " + std::to_string(pix->row_bytes) + " is below w * C * es = " + std::to_string(need));
-        if (pix->row_bytes % es_out) throw GkError("pixels: row_bytes must be a multiple of the sample size");
-        if (out_on_device && ((uintptr_t)pix->pixels % es_out)) throw GkError("pixels: the buffer is not aligned to its sample size");
+        if (dst.row_bytes < need)
+            throw GkError("pixels: row_bytes " + std::to_string(dst.row_bytes) + " is below w * C * es = " + std::to_string(need));
+        if (dst.row_bytes % es_out) throw GkError("pixels: row_bytes must be a multiple of the sample size");
+        if (out_on_device && ((uintptr_t)dst.pixels % es_out)) throw GkError("pixels: the buffer is not aligned to its sample size");
     }
     uint32_t smax = 0;
     for (uint32_t j = 0; j < nst; ++j) smax = std::max(smax, sprec[j]);
-    const uint32_t sb_in = (!st_signed && smax <= 16) ? (smax + 7) / 8 : 4;
-    const int stype = sb_in == 1 ? GK_U8 : sb_in == 2 ? GK_U16 : GK_S32;
-    const size_t es_in = gk_sample_size(stype);
-    std::vector<size_t> soff(nst);
-    size_t total = 0;
-    for (uint32_t j = 0; j < nst; ++j) {
-        sstr[j] = (sw[j] + 15) & ~15u;   // rows aligned for the kernel's vector loads
-        soff[j] = total;
-        total += (((size_t)sstr[j] * sh[j] * es_in) + 255) & ~(size_t)255;
-    }
-    uint8_t* src = (uint8_t*)ctx->dpix_src.get(total);
-    {
-        std::vector<void*> cp(nst);
-        for (uint32_t j = 0; j < nst; ++j) cp[j] = src + soff[j];
-        Inner in(ctx);
-        decode_impl(ctx, cs, len, cs_on_device, cp.data(), sstr.data(), sb_in == 4 ? 0 : sb_in, 1, win, nullptr);
+    const uint32_t sb_in = stage_sample_bytes(st_signed, smax);
+    const int stype = stage_type(sb_in);
+    const StagePlanes src = stage_planes(ctx->dpix_src, sw, sh, sb_in);
+    {   // the image as the display flags that belong below this stage and the colour boxes make it
+        DecStages below;
+        below.whole = DecStages::OUTPUT;
+        DisplayOut Db;
+        if (const uint32_t dflags = ctx->dec_display & ~GK_DISPLAY_FORCE_RGB) {
+            Db = call_display(ctx, o, dflags, win, nullptr);
+            below.display = &Db;
+        }
+        decode_planes(ctx, o, src.dst(), rq, below);
     }
     auto chan = [&](uint32_t k) {
         const DisplayOut::Ch& h = D.ch[k];
         GkPixChan c{};
-        c.src = src + soff[h.from]; c.ss = sstr[h.from];
+        c.src = src.at(h.from); c.ss = src.stride[h.from];
         c.op = h.op; c.lo = h.lo; c.hi = h.hi; c.scale = h.scale; c.shift = h.shift;
         return c;
     };
@@ -5447,15 +5484,15 @@ static void decode_output(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
             a.ch[k].same_prev = k > 0 && D.ch[k].from == D.ch[k - 1].from;
         }
         a.w = ow; a.h = oh; a.nch = nout;
-        if (out_on_device) { a.dst = pix->pixels; a.row_bytes = pix->row_bytes; }
+        if (out_on_device) { a.dst = dst.pixels; a.row_bytes = dst.row_bytes; }
         else { a.dst = ctx->dpix_out.get(pitch * oh); a.row_bytes = pitch; }
         gk_launch_pixels(st, stype, dtype, a);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[23], st));
         if (!out_on_device)
-            HIPCHK(hipMemcpy2DAsync(pix->pixels, pix->row_bytes, a.dst, pitch, tight, oh, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpy2DAsync(dst.pixels, dst.row_bytes, a.dst, pitch, tight, oh, hipMemcpyDeviceToHost, st));
     } else {   // planar: the one-channel case, launched per channel
-        std::vector<uint8_t*> dst(nout);
+        std::vector<uint8_t*> op(nout);
         std::vector<size_t> pitch(nout);
         if (!out_on_device) {
             size_t tot = 0;
@@ -5464,187 +5501,74 @@ static void decode_output(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
                 tot += pitch[k] * sh[D.ch[k].from];
             }
             uint8_t* stage = (uint8_t*)ctx->dpix_out.get(tot);
-            for (uint32_t k = 0; k < nout; ++k) { dst[k] = stage; stage += pitch[k] * sh[D.ch[k].from]; }
+            for (uint32_t k = 0; k < nout; ++k) { op[k] = stage; stage += pitch[k] * sh[D.ch[k].from]; }
         } else {
-            for (uint32_t k = 0; k < nout; ++k) { dst[k] = (uint8_t*)comps[k]; pitch[k] = (size_t)strides[k] * es_out; }
+            for (uint32_t k = 0; k < nout; ++k) { op[k] = (uint8_t*)dst.comps[k]; pitch[k] = (size_t)dst.strides[k] * es_out; }
         }
         for (uint32_t k = 0; k < nout; ++k) {
             GkPixArgs a{};
             a.ch[0] = chan(k);
             a.w = sw[D.ch[k].from]; a.h = sh[D.ch[k].from]; a.nch = 1;
-            a.dst = dst[k]; a.row_bytes = pitch[k];
+            a.dst = op[k]; a.row_bytes = pitch[k];
             gk_launch_pixels(st, stype, dtype, a);
         }
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[23], st));
         if (!out_on_device)
             for (uint32_t k = 0; k < nout; ++k)
-                HIPCHK(hipMemcpy2DAsync(comps[k], (size_t)strides[k] * es_out, dst[k], pitch[k], (size_t)sw[D.ch[k].from] * es_out,
+                HIPCHK(hipMemcpy2DAsync(dst.comps[k], (size_t)dst.strides[k] * es_out, op[k], pitch[k], (size_t)sw[D.ch[k].from] * es_out,
                                         sh[D.ch[k].from], hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     const float ms = ev_ms(ctx, 22, 23);   // the output pass counts as sample stage, as the display pass does
     ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
 }
-static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
-                        const uint32_t* strides, uint32_t sample_bytes, int out_on_device, const uint32_t* win = nullptr,
-                        const TilePass* pass = nullptr) {
+// A public decode call: the stream is opened once, and the output stage applies to a pixel call,
+// a forced precision and grey to RGB; everything else goes to decode_planes.
+static void decode_call(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const uint32_t* win) {
     hipStream_t st = ctx->st;
     launch_check(__LINE__);
     HIPCHK(hipEventRecord(ctx->ev[0], st));
-    const uint8_t* const cs_in = cs;
-    const size_t len_in = len;
     // Grok's partial-tile inverse (its single odd 5/3 sample shifted, not halved) follows a window
     // set with setDecompressWindow; decompressTile without one keeps the whole-tile rule
-    ctx->dwt_partial = pass ? pass->partial : win != nullptr && !ctx->win_whole_tile;
+    const DecReq rq{win, win != nullptr && !ctx->win_whole_tile};
+    const bool out_stage = dst.pixels || !ctx->dec_prec.empty();
+    DecStream o;
+    open_stream(o, src, st, ctx->dec_colour || ctx->dec_display || out_stage);
+    DecStages stg;
+    DisplayOut D;
+    if (ctx->dec_display || out_stage) {   // display flags, a precision list, a pixel call
+        D = call_display(ctx, o, ctx->dec_display, win, out_stage ? &ctx->dec_prec : nullptr);
+        if (dst.pixels || D.out_active()) {   // forced precision, grey to RGB, packed pixels
+            decode_output(ctx, o, dst, rq, D);
+            return;
+        }
+        stg.display = &D;
+    }
+    decode_planes(ctx, o, dst, rq, stg);
+}
+
+// The decode proper of the tile parts in Hd.parts, whose coding is Hd's and ctx->plan's, into
+// out: packet headers (T2), code-blocks (T1), inverse DWT and MCT, egress.  rq.win is the
+// rectangle written (null: the tile parts' own) and (fx, fy) the image-relative origin of out's
+// planes: the window's, and for a tile pass the whole call's.
+static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, const DecReq& rq, uint32_t fx, uint32_t fy,
+                        HostClock::time_point h0) {
+    hipStream_t st = ctx->st;
+    Plan& P = ctx->plan;
+    const uint8_t* const cs = S.dev ? S.dev : S.host;
+    const size_t len = S.len;
+    const bool cs_on_device = S.dev != nullptr, out_on_device = out.on_device;
+    void* const* comps = out.comps;
+    const uint32_t* strides = out.strides;
+    const uint32_t sample_bytes = out.sample_bytes, red = ctx->dec_reduce;
+    const uint32_t* win = rq.win;
     // GK_PROFILE=1: host phase times of the decode (stderr)
     static const bool prof = getenv("GK_PROFILE") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    auto now = [] { return HostClock::now(); };
+    auto ms = [](HostClock::time_point a, HostClock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();
     };
-    const auto h0 = now();
-    ByteSrc S;
-    S.len = len; S.st = st;
-    if (cs_on_device) S.dev = cs; else S.host = cs;
-    Jp2Colour col;
-    {
-        size_t joff = 0, jlen = 0;
-        const bool colour = (ctx->dec_colour || ctx->dec_display || !ctx->dec_prec.empty() || ctx->pix) && !ctx->col_inner && !pass;
-        if (jp2_locate(S, joff, jlen, colour ? &col : nullptr)) {   // JP2 file: decode its codestream box
-            cs += joff; len = jlen;
-            S = ByteSrc(); S.len = len; S.st = st;
-            if (cs_on_device) S.dev = cs; else S.host = cs;
-        }
-    }
-    Header Hd;
-    parse_header(S, Hd);
-    // (under decode_output the flags that belong to the output stage are set aside)
-    const uint32_t dflags = ctx->out_inner ? ctx->dec_display & ~GK_DISPLAY_FORCE_RGB : ctx->dec_display;
-    const bool out_stage = !ctx->out_inner && (ctx->pix || !ctx->dec_prec.empty());
-    if ((dflags || out_stage) && !ctx->col_inner && !pass) {   // display flags, a precision list, a pixel call
-        const Jp2Colour none;
-        const ColourOut co = resolve_colour(ctx->dec_colour ? col : none, Hd.want);
-        const DisplayOut D = resolve_display(col, co, Hd.want, dflags, ctx->dec_reduce, win, out_stage ? &ctx->dec_prec : nullptr);
-        if (ctx->pix || D.out_active()) {   // forced precision, grey to RGB, packed pixels
-            decode_output(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, D, Hd.want);
-            return;
-        }
-        if (D.active()) {   // a conversion or an upsampling that applies
-            decode_display(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, D, Hd.want);
-            return;
-        }
-    }
-    if (ctx->dec_colour && col.jp2 && (col.has_pclr || col.has_cdef)) {   // colour boxes that change the channels
-        const ColourOut co = resolve_colour(col, Hd.want);
-        if (co.active()) {
-            decode_colour(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, col, co, Hd.want);
-            return;
-        }
-    }
-    if (pass && pass->coding) {   // the pass's tiles: their own coding and quantisation
-        Hd.cod = pass->coding->cod; Hd.ccod = pass->coding->ccod; Hd.qbody = pass->coding->qbody;
-        read_cod_fields(Hd.cod, Hd.want.p);
-        Hd.want.p.roishift.assign(pass->coding->roi.begin(), pass->coding->roi.end());
-        bool any_roi = false;
-        for (uint8_t r : pass->coding->roi) any_roi = any_roi || r;
-        if (!any_roi) Hd.want.p.roishift.clear();
-        apply_coding(Hd);
-    }
-    if (Hd.want.nc < 3) Hd.want.p.mct = 0;
-    ensure_plan(ctx, Hd.want);
-    Plan& P = ctx->plan;
-    if (Hd.qcd != ctx->band_qcd) { apply_qcd(P, Hd.qcd); ctx->band_qcd = Hd.qcd; }
-    // the Part-1 decoders hold twice the magnitude plus the half-bit, (2M+1) << q, in an int32:
-    // a band (ROI shift included) of more than 30 bit-planes cannot be held (every tile has the
-    // same bands as tile 0)
-    for (uint32_t c = 0; c < P.nc; ++c)
-        if (!P.p.c_ht(c))
-            for (const ResG& R : P.tiles[0].comps[c].res)
-                for (const BandG& B : R.bands)
-                    if (B.numbps > 30) throw GkError("more than 30 band bit-planes (ROI shift included) not supported");
-    const uint32_t red = ctx->dec_reduce;
-    if (red >= P.min_numres()) throw GkError("reduce must be less than the number of resolutions");
-    // subsampled components: every component plane at its own size, rectangles on its grid
-    auto keep_window = [&]() {   // keep only the tile parts of tiles intersecting the window
-        if (!win) return;
-        if (win[0] >= win[2] || win[1] >= win[3] || win[2] > P.w || win[3] > P.h) throw GkError("bad decode window");
-        std::vector<TilePart> keep;
-        for (auto& TP : Hd.parts) {
-            if (TP.tile >= P.tiles.size()) throw GkError("corrupt SOT (tile index)");
-            const TileG& T = P.tiles[TP.tile];   // (canvas tile against the image-relative window)
-            if (T.x0 - P.x0 < win[2] && win[0] < T.x1 - P.x0 && T.y0 - P.y0 < win[3] && win[1] < T.y1 - P.y0)
-                keep.push_back(std::move(TP));
-        }
-        Hd.parts.swap(keep);
-        if (Hd.parts.empty()) throw GkError("no tile part intersects the window");
-    };
-    keep_window();
-    if (S.dev) {
-        try {
-            read_tile_part_headers(ctx, S, Hd);
-        } catch (const TlmMismatch&) {   // (R-BUG-8 streams) the SOT chain instead
-            Hd.parts.clear();
-            walk_sot_chain(S, Hd);
-            keep_window();
-        }
-    }
-    merge_tile_parts(Hd);
-    if ((ctx->col_whole || ctx->out_inner) && !win && !pass && Hd.parts.size() != P.tiles.size())
-        throw GkError(!ctx->col_whole ? "the output stage (pixel calls, forced precision, grey to RGB) on a stream that holds only some of "
-                                        "its tiles (sharded / tile-range decode) is not supported"
-                      : ctx->disp_inner ?"display flags (gk_set_decode_display) on a stream that holds only some of its tiles "
-                                        "(sharded / tile-range decode) are not supported"
-                                      : "a palette (pclr / cmap boxes) on a stream that holds only some of its tiles is not supported");
-    if (pass) {
-        std::vector<TilePart> keep;
-        for (auto& TP : Hd.parts)
-            if (TP.tile < pass->tiles.size() && pass->tiles[TP.tile]) keep.push_back(std::move(TP));
-        Hd.parts.swap(keep);
-        if (Hd.parts.empty()) throw GkError("internal: a tile pass without tiles");
-    } else {
-        // tiles coded with their own parameters (tile-part COD / COC / QCD / QCC): the tiles with
-        // the main header's coding in one pass, then each other tile in a pass of its own, through
-        // its rectangle (clipped to the window) into the same output frame.  Passes write disjoint
-        // tile rectangles in stream order on one HIP stream; a tile absent from a pass's tile
-        // rectangle is written as zero by that pass before its own pass writes it.
-        std::vector<TileCoding> own(Hd.parts.size());
-        std::vector<uint8_t> differs(Hd.parts.size(), 0);
-        bool any = false;
-        for (size_t q = 0; q < Hd.parts.size(); ++q) {
-            if (Hd.parts[q].cmark.empty()) continue;
-            differs[q] = tile_coding(Hd, Hd.parts[q], own[q]);
-            any = any || differs[q];
-        }
-        if (any) {
-            const size_t ntl = P.tiles.size();
-            const uint32_t full[4] = {0, 0, P.w, P.h};
-            const uint32_t* wv = win ? win : full;
-            TilePass base;
-            base.tiles.assign(ntl, 0);
-            base.fx = win ? win[0] : 0; base.fy = win ? win[1] : 0;
-            base.partial = ctx->dwt_partial;
-            bool main_tiles = false;
-            for (size_t q = 0; q < Hd.parts.size(); ++q)
-                if (!differs[q] && Hd.parts[q].tile < ntl) { base.tiles[Hd.parts[q].tile] = 1; main_tiles = true; }
-            if (main_tiles) decode_impl(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, win, &base);
-            for (size_t q = 0; q < Hd.parts.size(); ++q) {
-                if (!differs[q]) continue;
-                const uint32_t t = Hd.parts[q].tile;
-                if (t >= ntl) throw GkError("corrupt SOT (tile index)");
-                const TileG& T = P.tiles[t];
-                const uint32_t tw[4] = {std::max(T.x0 - P.x0, wv[0]), std::max(T.y0 - P.y0, wv[1]),
-                                        std::min(T.x1 - P.x0, wv[2]), std::min(T.y1 - P.y0, wv[3])};
-                if (tw[0] >= tw[2] || tw[1] >= tw[3]) continue;
-                TilePass tp = base;
-                tp.tiles.assign(ntl, 0);
-                tp.tiles[t] = 1;
-                tp.coding = &own[q];
-                decode_impl(ctx, cs_in, len_in, cs_on_device, comps, strides, sample_bytes, out_on_device, tw, &tp);
-            }
-            return;
-        }
-    }
     if (S.dev) prefetch_packet_headers(ctx, S, P, Hd);
     // ---- tiles present, their rectangle, and the code-blocks that reach the output
     std::vector<int32_t> part_of(P.tiles.size(), -1);
@@ -5665,12 +5589,11 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     const TileG& Tfirst = P.tiles[(size_t)jb * P.ntx + ib];
     const TileG& Tlast = P.tiles[(size_t)(je - 1) * P.ntx + ie - 1];
     const Region RG = make_region(Tfirst.x0 - P.x0, Tfirst.y0 - P.y0, Tlast.x1 - P.x0, Tlast.y1 - P.y0);   // image-relative
-    uint32_t rx0 = RG.x0, ry0 = RG.y0, rx1 = RG.x0 + RG.w, ry1 = RG.y0 + RG.h, ox = 0, oy = 0;
+    uint32_t rx0 = RG.x0, ry0 = RG.y0, rx1 = RG.x0 + RG.w, ry1 = RG.y0 + RG.h;
     if (win) {
         rx0 = std::max(rx0, win[0]); ry0 = std::max(ry0, win[1]); rx1 = std::min(rx1, win[2]); ry1 = std::min(ry1, win[3]);
-        ox = win[0]; oy = win[1];
     }
-    if (pass) { ox = pass->fx; oy = pass->fy; }
+    const uint32_t ox = fx, oy = fy;
     const uint32_t ncols = rx1 - rx0, nrows = ry1 - ry0;
     // the region on each sampling group's grid (RG itself without subsampling)
     std::vector<Region> RGg;
@@ -6368,7 +6291,7 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
         // writes it per tile into the ceil(size / 2^red) output (a tile's reduced origin is
         // ceil(origin / 2^red), B.5).  Subsampled components: the same on each component's grid
         // (tile-component ceil(tile / XRsiz), then reduced), one plane each.
-        run_dwt(ctx, RG, false, jb, je, ib, ie, nullptr, red + 1);
+        run_dwt(ctx, RG, false, jb, je, ib, ie, nullptr, red + 1, rq.partial);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[4], st));
         // reduced canvas: positions ceil(x / 2^red); output index = that less the image origin's.
@@ -6500,7 +6423,7 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     auto planeAf = [&](uint32_t c) { return reinterpret_cast<const float*>(planeA(c)); };
     const bool mct3 = P.mct3();
     if (P.max_numres() > 1 && !P.l1_fusable) {   // levels first, then the inverse MCT + DC shift + clamp below
-        run_dwt(ctx, RG, false, jb, je, ib, ie, nullptr);
+        run_dwt(ctx, RG, false, jb, je, ib, ie, nullptr, 1, rq.partial);
     }
     if (P.max_numres() > 1 && P.l1_fusable) {
         L1Io io;
@@ -6509,7 +6432,7 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
         io.strides = dstr;
         io.cx0 = rx0 + P.x0; io.cy0 = ry0 + P.y0; io.cx1 = rx1 + P.x0; io.cy1 = ry1 + P.y0;
         if (mct3 && (dstr[1] != dstr[0] || dstr[2] != dstr[0])) throw GkError("the first three components must share a stride");
-        run_dwt(ctx, RG, false, jb, je, ib, ie, &io);
+        run_dwt(ctx, RG, false, jb, je, ib, ie, &io, 1, rq.partial);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[4], st));
     } else {
@@ -6549,6 +6472,118 @@ static void decode_impl(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_de
     ctx->tm.assemble_ms = ev_ms(ctx, 1, 2);
     ctx->tm.total_ms = ev_ms(ctx, 0, 6);
     ctx->tm.t1_blocks = nbr;
+}
+
+// The engine's plan for Hd's image and coding (the main header's, or a tile pass's own), with
+// the refusals that need the plan
+static void plan_header(gk_ctx* ctx, Header& Hd) {
+    if (Hd.want.nc < 3) Hd.want.p.mct = 0;
+    ensure_plan(ctx, Hd.want);
+    Plan& P = ctx->plan;
+    if (Hd.qcd != ctx->band_qcd) { apply_qcd(P, Hd.qcd); ctx->band_qcd = Hd.qcd; }
+    // the Part-1 decoders hold twice the magnitude plus the half-bit, (2M+1) << q, in an int32:
+    // a band (ROI shift included) of more than 30 bit-planes cannot be held (every tile has the
+    // same bands as tile 0)
+    for (uint32_t c = 0; c < P.nc; ++c)
+        if (!P.p.c_ht(c))
+            for (const ResG& R : P.tiles[0].comps[c].res)
+                for (const BandG& B : R.bands)
+                    if (B.numbps > 30) throw GkError("more than 30 band bit-planes (ROI shift included) not supported");
+    if (ctx->dec_reduce >= P.min_numres()) throw GkError("reduce must be less than the number of resolutions");
+}
+
+// The component planes of the opened stream into dst: its tile parts are located, kept by the
+// window and merged once, and decode_core runs once, or once per tile pass.
+static void decode_components(gk_ctx* ctx, DecStream& o, const DecDst& dst, const DecReq& rq, DecStages::Whole whole) {
+    ByteSrc& S = o.S;
+    Header& Hd = o.Hd;
+    const uint32_t* win = rq.win;
+    plan_header(ctx, Hd);
+    Plan& P = ctx->plan;
+    // subsampled components: every component plane at its own size, rectangles on its grid
+    auto keep_window = [&]() {   // keep only the tile parts of tiles intersecting the window
+        if (!win) return;
+        if (win[0] >= win[2] || win[1] >= win[3] || win[2] > P.w || win[3] > P.h) throw GkError("bad decode window");
+        std::vector<TilePart> keep;
+        for (auto& TP : Hd.parts) {
+            if (TP.tile >= P.tiles.size()) throw GkError("corrupt SOT (tile index)");
+            const TileG& T = P.tiles[TP.tile];   // (canvas tile against the image-relative window)
+            if (T.x0 - P.x0 < win[2] && win[0] < T.x1 - P.x0 && T.y0 - P.y0 < win[3] && win[1] < T.y1 - P.y0)
+                keep.push_back(std::move(TP));
+        }
+        Hd.parts.swap(keep);
+        if (Hd.parts.empty()) throw GkError("no tile part intersects the window");
+    };
+    keep_window();
+    if (S.dev) {
+        try {
+            read_tile_part_headers(ctx, S, Hd);
+        } catch (const TlmMismatch&) {   // (R-BUG-8 streams) the SOT chain instead
+            Hd.parts.clear();
+            walk_sot_chain(S, Hd);
+            keep_window();
+        }
+    }
+    merge_tile_parts(Hd);
+    if (whole != DecStages::ANY && !win && Hd.parts.size() != P.tiles.size())
+        throw GkError(whole == DecStages::OUTPUT ? "the output stage (pixel calls, forced precision, grey to RGB) on a stream that holds only some of "
+                                                   "its tiles (sharded / tile-range decode) is not supported"
+                      : whole == DecStages::DISPLAY ? "display flags (gk_set_decode_display) on a stream that holds only some of its tiles "
+                                                      "(sharded / tile-range decode) are not supported"
+                                                    : "a palette (pclr / cmap boxes) on a stream that holds only some of its tiles is not supported");
+    const uint32_t fx = win ? win[0] : 0, fy = win ? win[1] : 0;
+    std::vector<TileCoding> own(Hd.parts.size());
+    std::vector<uint8_t> differs(Hd.parts.size(), 0);
+    bool any = false;
+    for (size_t q = 0; q < Hd.parts.size(); ++q) {
+        if (Hd.parts[q].cmark.empty()) continue;
+        differs[q] = tile_coding(Hd, Hd.parts[q], own[q]);
+        any = any || differs[q];
+    }
+    if (!any) {
+        decode_core(ctx, S, Hd, dst, rq, fx, fy, o.t0);
+        return;
+    }
+    // tiles coded with their own parameters (tile-part COD / COC / QCD / QCC): the tiles with
+    // the main header's coding in one pass, then each other tile in a pass of its own, through
+    // its rectangle (clipped to the window) into the same output frame.  Passes write disjoint
+    // tile rectangles in stream order on one HIP stream; a tile absent from a pass's tile
+    // rectangle is written as zero by that pass before its own pass writes it.
+    // A pass decodes its tile parts under a copy of the header (its tiles' coding goes into the
+    // copy) and reads through a copy of the byte source as the tile-part-header fetch left it:
+    // the packet headers a pass prefetches lie in a buffer that the next pass's prefetch reuses.
+    const size_t ntl = P.tiles.size();
+    const uint32_t full[4] = {0, 0, P.w, P.h};
+    const uint32_t* wv = win ? win : full;
+    std::vector<TilePart> parts;
+    parts.swap(Hd.parts);
+    auto run_pass = [&](Header& PH, const uint32_t* pw) {
+        plan_header(ctx, PH);
+        ByteSrc PS = S.fork();
+        PS.regp = std::make_shared<std::vector<ByteSrc::Region>>(*S.regp);
+        decode_core(ctx, PS, PH, dst, DecReq{pw, rq.partial}, fx, fy, o.t0);
+    };
+    Header main_pass = Hd;
+    for (size_t q = 0; q < parts.size(); ++q)
+        if (!differs[q] && parts[q].tile < ntl) main_pass.parts.push_back(parts[q]);
+    if (!main_pass.parts.empty()) run_pass(main_pass, win);
+    for (size_t q = 0; q < parts.size(); ++q) {
+        if (!differs[q]) continue;
+        const uint32_t t = parts[q].tile;
+        if (t >= ntl) throw GkError("corrupt SOT (tile index)");
+        const TileG& T = P.tiles[t];
+        const uint32_t tw[4] = {std::max(T.x0 - P.x0, wv[0]), std::max(T.y0 - P.y0, wv[1]),
+                                std::min(T.x1 - P.x0, wv[2]), std::min(T.y1 - P.y0, wv[3])};
+        if (tw[0] >= tw[2] || tw[1] >= tw[3]) continue;
+        Header PH = Hd;   // the pass's tile: its own coding and quantisation
+        PH.parts.push_back(parts[q]);
+        PH.cod = own[q].cod; PH.ccod = own[q].ccod; PH.qbody = own[q].qbody;
+        read_cod_fields(PH.cod, PH.want.p);
+        PH.want.p.roishift.assign(own[q].roi.begin(), own[q].roi.end());
+        if (std::none_of(own[q].roi.begin(), own[q].roi.end(), [](uint8_t r) { return r != 0; })) PH.want.p.roishift.clear();
+        apply_coding(PH);
+        run_pass(PH, tw);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -6742,22 +6777,6 @@ int gk_main_header(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters*
     }
 }
 
-// The header of a codestream or JP2 file with its colour boxes: Hd the codestream's, col the
-// jp2h boxes, out the output channels (those of the boxes when apply, else the components).
-static bool read_header_colour(ByteSrc& S, const uint8_t* cs, bool on_device, bool apply, Header& Hd, Jp2Colour& col,
-                               ColourOut& out) {
-    size_t joff = 0, jlen = 0;
-    const bool jp2 = jp2_locate(S, joff, jlen, &col);
-    if (jp2) {
-        hipStream_t st = S.st;
-        S = ByteSrc(); S.len = jlen; S.st = st;
-        if (on_device) S.dev = cs + joff; else S.host = cs + joff;
-    }
-    parse_header(S, Hd);
-    Jp2Colour none;
-    out = resolve_colour(apply ? col : none, Hd.want);
-    return jp2;
-}
 static void fill_image_info(gk_image_info* info, const Header& Hd, const ColourOut& out, const DisplayOut* disp = nullptr) {
     info->w = Hd.want.w; info->h = Hd.want.h; info->numcomps = Hd.want.nc; info->prec = Hd.want.prec;
     info->sgnd = Hd.want.sgnd; info->x0 = Hd.want.x0; info->y0 = Hd.want.y0;
@@ -6799,12 +6818,11 @@ int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
     if (!ctx || !cs || !info) return -1;
     try {
         (void)hipSetDevice(ctx->device);
-        ByteSrc S; S.len = len; S.st = ctx->st;
-        if (cs_on_device) S.dev = cs; else S.host = cs;
-        Header Hd;
-        Jp2Colour col;
-        ColourOut out;
-        read_header_colour(S, cs, cs_on_device != 0, ctx->dec_colour, Hd, col, out);
+        DecStream o;
+        open_stream(o, DecSrc{cs, len, cs_on_device != 0}, ctx->st, true);
+        Header& Hd = o.Hd;
+        Jp2Colour& col = o.col;
+        ColourOut out = stream_channels(o, ctx->dec_colour);
         // (display flags: the whole image's output; a refusal that depends on a window is the decode's)
         DisplayOut disp = resolve_display(col, out, Hd.want, ctx->dec_display, ctx->dec_reduce, nullptr, &ctx->dec_prec);
         fill_image_info(info, Hd, out, &disp);
@@ -6875,11 +6893,11 @@ int gk_probe_output(const uint8_t* cs, size_t len, uint32_t flags, uint32_t redu
         if (n && !list) throw GkError("gk_probe_output: no list");
         const std::vector<gk_precision> plist(list, list + n);
         if (reduce >= GK_MAXRLVLS) throw GkError("reduce must be less than the number of resolutions");
-        ByteSrc S; S.len = len; S.host = cs;
-        Header Hd;
-        Jp2Colour col;
-        ColourOut out;
-        read_header_colour(S, cs, false, true, Hd, col, out);
+        DecStream o;
+        open_stream(o, DecSrc{cs, len, false}, nullptr, true);
+        const Header& Hd = o.Hd;
+        const Jp2Colour& col = o.col;
+        const ColourOut out = stream_channels(o, true);
         for (uint32_t c = 0; c < Hd.want.nc; ++c)
             if (reduce >= Hd.want.p.c_numres(c)) throw GkError("reduce must be less than the number of resolutions");
         const DisplayOut disp = resolve_display(col, out, Hd.want, flags, reduce, nullptr, &plist);
@@ -6901,11 +6919,11 @@ int gk_probe_output(const uint8_t* cs, size_t len, uint32_t flags, uint32_t redu
 int gk_probe_colour(const uint8_t* cs, size_t len, gk_colour_info* ci, char* msg, size_t msg_cap) {
     if (!cs || !ci) return -1;
     try {
-        ByteSrc S; S.len = len; S.host = cs;
-        Header Hd;
-        Jp2Colour col;
-        ColourOut out;
-        read_header_colour(S, cs, false, true, Hd, col, out);
+        DecStream o;
+        open_stream(o, DecSrc{cs, len, false}, nullptr, true);
+        const Header& Hd = o.Hd;
+        const Jp2Colour& col = o.col;
+        const ColourOut out = stream_channels(o, true);
         fill_colour_info(ci, col, out, Hd.want.nc);
         return 0;
     } catch (const GkError& e) {
@@ -6971,11 +6989,10 @@ int gk_probe_header(const uint8_t* cs, size_t len, gk_image_info* info, gk_cpara
                     size_t msg_cap) {
     if (!cs || !info) return -1;
     try {
-        ByteSrc S; S.len = len; S.host = cs;
-        Header Hd;
-        Jp2Colour col;
-        ColourOut out;
-        const bool jp2 = read_header_colour(S, cs, false, true, Hd, col, out);
+        DecStream o;
+        open_stream(o, DecSrc{cs, len, false}, nullptr, true);
+        const Header& Hd = o.Hd;
+        const ColourOut out = stream_channels(o, true);
         fill_image_info(info, Hd, out);
         info->sample_bytes = 0;
         if (coding) {
@@ -7000,7 +7017,7 @@ int gk_probe_header(const uint8_t* cs, size_t len, gk_image_info* info, gk_cpara
             coding->tx0 = Hd.want.gx0; coding->ty0 = Hd.want.gy0;
             coding->writeTLM = !Hd.tlm.empty();
             coding->writePLT = 0;
-            coding->cod_format = jp2 ? 2 : 0;
+            coding->cod_format = o.jp2 ? 2 : 0;
             coding->prog_order = (int32_t)p.prog;
         }
         return 0;
@@ -7010,19 +7027,23 @@ int gk_probe_header(const uint8_t* cs, size_t len, gk_image_info* info, gk_cpara
     }
 }
 
-int gk_decode(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
-              const uint32_t* strides, uint32_t sample_bytes, int out_on_device) {
-    if (!ctx || !cs || !comps || !strides) return -1;
+// the four decode entry points: planes or pixels, the image or a window
+static int decode_entry(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const uint32_t* win) {
+    if (!ctx || !src.cs || (!dst.pixels && (!dst.comps || !dst.strides))) return -1;
     try {
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
-        decode_impl(ctx, cs, len, cs_on_device, comps, strides, sample_bytes, out_on_device);
+        decode_call(ctx, src, dst, win);
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;
         return -1;
     }
+}
+int gk_decode(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
+              const uint32_t* strides, uint32_t sample_bytes, int out_on_device) {
+    return decode_entry(ctx, DecSrc{cs, len, cs_on_device != 0}, DecDst{comps, strides, nullptr, 0, sample_bytes, out_on_device != 0}, nullptr);
 }
 
 int gk_set_subsampling(gk_ctx* ctx, uint32_t numcomps, const uint32_t* dx, const uint32_t* dy) {
@@ -7042,11 +7063,10 @@ static int probe_components(const uint8_t* cs, size_t len, uint32_t* dx, uint32_
                             uint32_t cap, bool apply) {
     if (!cs) return -1;
     try {
-        ByteSrc S; S.len = len; S.host = cs;
-        Header Hd;
-        Jp2Colour col;
-        ColourOut out;
-        read_header_colour(S, cs, false, apply, Hd, col, out);
+        DecStream o;
+        open_stream(o, DecSrc{cs, len, false}, nullptr, true);
+        const Header& Hd = o.Hd;
+        const ColourOut out = stream_channels(o, apply);
         for (uint32_t c = 0; c < out.ch.size() && c < cap; ++c) {
             if (dx) dx[c] = Hd.want.sx(out.ch[c].src);
             if (dy) dy[c] = Hd.want.sy(out.ch[c].src);
@@ -7135,37 +7155,14 @@ int gk_set_decode_layers(gk_ctx* ctx, uint32_t max_layers) {
 int gk_decode_window(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, uint32_t x0, uint32_t y0,
                      uint32_t x1, uint32_t y1, void* const* comps, const uint32_t* strides, uint32_t sample_bytes,
                      int out_on_device) {
-    if (!ctx || !cs || !comps || !strides) return -1;
-    try {
-        (void)hipSetDevice(ctx->device);
-        DevBusy busy(ctx->device);
-        ctx->tm.t1_shared = 0;
-        const uint32_t win[4] = {x0, y0, x1, y1};
-        decode_impl(ctx, cs, len, cs_on_device, comps, strides, sample_bytes, out_on_device, win);
-        return 0;
-    } catch (const GkError& e) {
-        ctx->err = e.msg;
-        return -1;
-    }
+    const uint32_t win[4] = {x0, y0, x1, y1};
+    return decode_entry(ctx, DecSrc{cs, len, cs_on_device != 0}, DecDst{comps, strides, nullptr, 0, sample_bytes, out_on_device != 0}, win);
 }
 
 static int decode_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const uint32_t* win, void* pixels,
                          size_t row_bytes, uint32_t sample_bytes, int out_on_device) {
-    if (!ctx || !cs || !pixels) return -1;
-    const gk_ctx::PixDst dst{pixels, row_bytes};
-    try {
-        (void)hipSetDevice(ctx->device);
-        DevBusy busy(ctx->device);
-        ctx->tm.t1_shared = 0;
-        ctx->pix = &dst;
-        decode_impl(ctx, cs, len, cs_on_device, nullptr, nullptr, sample_bytes, out_on_device, win);
-        ctx->pix = nullptr;
-        return 0;
-    } catch (const GkError& e) {
-        ctx->pix = nullptr;
-        ctx->err = e.msg;
-        return -1;
-    }
+    if (!pixels) return -1;
+    return decode_entry(ctx, DecSrc{cs, len, cs_on_device != 0}, DecDst{nullptr, nullptr, pixels, row_bytes, sample_bytes, out_on_device != 0}, win);
 }
 int gk_decode_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* pixels, size_t row_bytes,
                      uint32_t sample_bytes, int out_on_device) {

@@ -511,6 +511,16 @@ def _refuse_reduce(e, cs):
         e.set_decode_reduce(0)
 
 
+def _refuse_reduce_under_the_output_stage(e, cs):
+    # refused by the component decode, the innermost level, after the output stage has begun
+    e.set_decode_reduce(4)   # (numres 4)
+    try:
+        with pytest.raises(RuntimeError, match="reduce must be less"):
+            e.decode_pixels(cs, sample_bytes=1)
+    finally:
+        e.set_decode_reduce(0)
+
+
 def _refuse_window(e, cs):
     with pytest.raises(RuntimeError, match="bad decode window"):
         e.decode_window(cs, (90, 70, 104, 88))   # (past the 96 x 80 image)
@@ -543,7 +553,7 @@ def _refuse_display(e, cs):
 
 
 REFUSALS = {"reduce": _refuse_reduce, "window": _refuse_window, "truncated_header": _refuse_truncated_header,
-            "jp2h": _refuse_jp2h, "display": _refuse_display}
+            "jp2h": _refuse_jp2h, "display": _refuse_display, "reduce_in_pixels": _refuse_reduce_under_the_output_stage}
 
 
 @pytest.mark.parametrize("order", ORDERS)

@@ -122,6 +122,106 @@ def test_engine_tile_coding_subsampled():
         np.testing.assert_array_equal(g, s)   # (lossless either way)
 
 
+# ---- the output, display and colour stages over tile passes: each stage decodes the components
+# once, the component decode splits into passes.  Truth: the oracle's planar decode of the raw
+# codestream, through the restatements the stages' own suites use.
+def _jp2(cs, nc, h, w, boxes):
+    import jp2_boxes as J
+    return J.jp2_file(cs, [J.ihdr(h, w, nc, 8), J.colr_enum(16)] + boxes)
+
+
+def _dev(data):
+    import torch
+    return torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+
+
+def _spliced(src, **kw):
+    # as test_engine_tile_coding_subsampled splices: tile 1 with its own levels and code-blocks
+    import tile_coding as TC
+    a = O.encode(src, 8, tiles=TC.TILES, numres=3, **kw)
+    b = O.encode(src, 8, tiles=TC.TILES, numres=2, cblk=(16, 16), **kw)
+    return TC.splice(a, b, {1}, "cod")
+
+
+def test_pixels_over_passes(eng):
+    import torch
+    name = "levels_cblk"
+    cs = stream(name)
+    want = np.moveaxis(O.decode(cs)[0], 0, -1)
+    got = eng.decode_pixels(cs, sample_bytes=1)
+    assert got.dtype == np.uint8
+    np.testing.assert_array_equal(got, want)
+    y = torch.full(want.shape, 0xA5, dtype=torch.uint8, device="cuda")
+    eng.decode_pixels(cs, out=y)
+    np.testing.assert_array_equal(y.cpu().numpy(), want)
+    x0, y0, x1, y1 = win = (5, 7, 61, 50)
+    got = eng.decode_pixels(cs, sample_bytes=1, window=win)
+    np.testing.assert_array_equal(got, np.moveaxis(expected(name, partial=True)[:, y0:y1, x0:x1], 0, -1))
+
+
+def test_forced_precision_over_passes(eng):
+    import pixels_ref as P
+    name, spec = "rev_to_irrev", "6S,10S,5C"   # every channel changes: scaled down, scaled up, clamped
+    cs = stream(name)
+    planes, _ = O.decode(cs)
+    want, comps = P.force_precision(list(planes), [(1, 1, 8, 0)] * 3, spec)
+    assert [c[2] for c in comps] == [6, 10, 5] and all((w != p).any() for w, p in zip(want, planes))
+    eng.set_decode_precision(spec)
+    try:
+        got = eng.decode(cs)
+    finally:
+        eng.set_decode_precision(None)
+    np.testing.assert_array_equal(got, np.stack(want))
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_cdef_over_passes(eng, device):
+    import jp2_boxes as J
+    name, entries = "coc_form", [(0, 0, 3), (1, 0, 2), (2, 0, 1)]   # channels 0 and 2 change places
+    H, W = CASES[name][:2]
+    cs = stream(name, tlm=device)
+    planes, _ = O.decode(cs)
+    want, _ = J.expected(list(planes), cdef_entries=entries)
+    np.testing.assert_array_equal(want, planes[[2, 1, 0]])
+    f = _jp2(cs, 3, H, W, [J.cdef(entries)])
+    got = eng.decode(_dev(f), len(f)) if device else eng.decode(f)
+    np.testing.assert_array_equal(got, want)
+
+
+def test_palette_over_passes(eng):
+    import jp2_boxes as J
+    W, H = 96, 80
+    idx = J._indices(H, W, 256, 3)[None]
+    cs = _spliced(idx, mct=False)
+    planes, _ = O.decode(cs)
+    np.testing.assert_array_equal(planes, idx)
+    lut, cm = J._lut(256, [8, 8, 8], 4), [(0, 1, 0), (0, 1, 1), (0, 1, 2)]
+    want, _ = J.expected(list(planes), lut, cm)
+    got = eng.decode(_jp2(cs, 1, H, W, [J.pclr(lut, [8, 8, 8]), J.cmap(cm)]))
+    np.testing.assert_array_equal(got, want)
+
+
+def test_upsampling_over_passes(eng):
+    import display_ref as R
+    from subsampling_cases import comp_shape
+    W, H, sub = 96, 80, [(1, 1), (2, 2), (2, 2)]
+    rng = np.random.default_rng(5)
+    src = [rng.integers(0, 256, size=comp_shape(W, H, dx, dy)).astype(np.int32) for dx, dy in sub]
+    cs = _spliced(src, size=(W, H), subsampling=sub)
+    planes, _ = O.decode(cs)
+    want = R.post_process(planes, [(dx, dy, 8, 0) for dx, dy in sub], 0, (0, 0, W, H), upsample=True)[0]
+    want = np.stack(want)
+    assert want.shape == (3, H, W)
+    eng.set_decode_display(upsample=True)
+    try:
+        got = eng.decode(cs)
+        pix = eng.decode_pixels(cs, sample_bytes=1)   # output -> display -> components -> passes
+    finally:
+        eng.set_decode_display()
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(pix, np.moveaxis(want, 0, -1))
+
+
 @pytest.mark.parametrize("name", ["ht_and_part1", "mode_switches", "wide_block"])
 def test_engine_tile_cod_resets_main_coc(eng, name):
     import j2k_markers as J
