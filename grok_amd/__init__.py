@@ -28,7 +28,8 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_probe_colour", "gk_header_colour", "gk_header_icc", "gk_set_decode_colour", "gk_probe_icc",
            "gk_probe_stream_components", "gk_set_decode_display", "gk_probe_display", "gk_set_decode_precision",
            "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels", "gk_encode_pixels",
-           "gk_set_encode_colour", "gk_jp2_boxes", "gk_header_cielab", "gk_probe_cielab")
+           "gk_set_encode_colour", "gk_jp2_boxes", "gk_header_cielab", "gk_probe_cielab",
+           "gk_set_encode_convert", "gk_probe_encode_convert")
 GK_MAX_CHANNELS = 256
 GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB, GK_DISPLAY_ICC = 1, 2, 4, 8   # gk_set_decode_display flags
 GK_PREC_CLIP, GK_PREC_SCALE = 0, 1   # gk_precision::mode (grk_precision_mode)
@@ -150,6 +151,11 @@ class EncodeColour(ctypes.Structure):
                 ("lut", ctypes.POINTER(ctypes.c_int32)), ("cmap", ctypes.POINTER(CmapEntry))]
 
 
+class EncodeConvert(ctypes.Structure):
+    """gk_encode_convert"""
+    _fields_ = [("space", ctypes.c_uint32), ("chroma_dx", ctypes.c_uint32), ("chroma_dy", ctypes.c_uint32)]
+
+
 # GRK_COLOR_SPACE by name (gk_encode_colour::colour_space)
 COLOUR_SPACES = {"srgb": 2, "grey": 3, "gray": 3, "sycc": 4, "esycc": 5, "eycc": 5, "cmyk": 6, "cie": 7, "icc": 9}
 
@@ -197,6 +203,36 @@ def _encode_colour(space=None, icc=None, channels=None, palette=None):
         e.channel_prec, e.lut, e.cmap = pr, l32.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ce
     e._keep = keep
     return e
+
+
+def _encode_convert(space, chroma):
+    """gk_encode_convert of the Python arguments: space a GRK_COLOR_SPACE value or a name of
+    COLOUR_SPACES ("sycc", "esycc"), chroma = (dx, dy)."""
+    if isinstance(space, str):
+        if space.lower() not in COLOUR_SPACES:
+            raise ValueError("convert: unknown colour space name %r" % space)
+        space = COLOUR_SPACES[space.lower()]
+    dx, dy = chroma
+    if not (0 <= int(space) < 1 << 32 and 0 <= int(dx) < 1 << 32 and 0 <= int(dy) < 1 << 32):
+        raise ValueError("convert: colour space and chroma factors are unsigned 32-bit values")
+    return EncodeConvert(int(space), int(dx), int(dy))
+
+
+def probe_encode_convert(shape, prec, space, chroma=(1, 1), origin=None, signed=False, sample_bytes=0):
+    """gk_probe_encode_convert: what an encode of an (H, W, C) image of `prec` bits codes under
+    Engine.set_encode_convert(space, chroma), no engine or GPU needed: [(dx, dy)] and [(rows, cols)]
+    per component.  A refusal raises ValueError with the engine's message."""
+    lib = load_library()
+    h, w, c = shape
+    info = ImageInfo(w, h, c, prec, int(signed), sample_bytes)
+    if origin is not None:
+        info.x0, info.y0 = int(origin[0]), int(origin[1])
+    spec = _encode_convert(space, chroma)
+    dx, dy, cw, ch = [(ctypes.c_uint32 * 3)() for _ in range(4)]
+    msg = ctypes.create_string_buffer(512)
+    if lib.gk_probe_encode_convert(ctypes.byref(info), ctypes.byref(spec), dx, dy, cw, ch, msg, len(msg)) != 0:
+        raise ValueError("gk_probe_encode_convert: " + msg.value.decode())
+    return [(dx[k], dy[k]) for k in range(3)], [(ch[k], cw[k]) for k in range(3)]
 
 
 def jp2_boxes(shape, prec, cs_len, signed=False, space=None, icc=None, channels=None, palette=None):
@@ -312,6 +348,11 @@ def load_library(build_if_missing=True):
     lib.gk_jp2_boxes.restype = ctypes.c_int
     lib.gk_jp2_boxes.argtypes = [P(ImageInfo), P(EncodeColour), ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t,
                                  P(ctypes.c_size_t), ctypes.c_char_p, ctypes.c_size_t]
+    lib.gk_set_encode_convert.restype = ctypes.c_int
+    lib.gk_set_encode_convert.argtypes = [ctypes.c_void_p, P(EncodeConvert)]
+    lib.gk_probe_encode_convert.restype = ctypes.c_int
+    lib.gk_probe_encode_convert.argtypes = [P(ImageInfo), P(EncodeConvert)] + [P(ctypes.c_uint32)] * 4 + \
+        [ctypes.c_char_p, ctypes.c_size_t]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -636,6 +677,17 @@ class Engine:
         e = _encode_colour(space, icc, channels, palette)
         if self.lib.gk_set_encode_colour(self.ctx, ctypes.byref(e) if e is not None else None) != 0:
             raise ValueError("gk_set_encode_colour: " + self.lib.gk_last_error(self.ctx).decode())
+
+    def set_encode_convert(self, space=None, chroma=(1, 1)):
+        """gk_set_encode_convert (sticky): later encode_pixels calls with 3 channels and encode calls with
+        a (3, H, W) array take R, G, B, convert them to sYCC ("sycc") or e-sYCC ("esycc") on the
+        device with the chroma planes every chroma = (dx, dy) positions ((1, 1), (2, 1), (2, 2): 4:4:4,
+        4:2:2, 4:2:0) and encode those planes as encode(..., subsampling=[(1, 1), chroma, chroma])
+        does under set_encode_colour(space).  space=None clears it.  A refusal raises ValueError and
+        leaves the engine with none."""
+        spec = None if space is None else _encode_convert(space, chroma)
+        if self.lib.gk_set_encode_convert(self.ctx, ctypes.byref(spec) if spec is not None else None) != 0:
+            raise ValueError("gk_set_encode_convert: " + self.lib.gk_last_error(self.ctx).decode())
 
     def encode_pixels(self, pixels, prec, signed=False, params=None, out=None, origin=None):
         """gk_encode_pixels: encode packed pixels.  pixels: an (H, W, C) or (H, W) numpy array (host)

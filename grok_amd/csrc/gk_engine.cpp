@@ -3034,6 +3034,51 @@ static void set_enc_colour(EncColour& E, const gk_encode_colour* s) {
     E = N;
 }
 
+// gk_set_encode_convert's setting: R, G, B input becomes sYCC / e-sYCC with the chroma planes
+// every (dx, dy) positions (k_rgb_ycc).  Grok has no forward conversion (its CLI takes subsampled
+// raw YUV); the engine's own arithmetic is in DESIGN.md §3.
+struct EncConvert {
+    uint32_t space = 0, dx = 1, dy = 1;   // space: 0 none, 4 sYCC, 5 e-sYCC (GRK_COLOR_SPACE)
+    bool set() const { return space != 0; }
+    uint32_t mode() const { return dx == 1 ? GK_YCC_444 : dy == 1 ? GK_YCC_422 : GK_YCC_420; }
+};
+// What one encode call under a conversion codes: the planar call's state under gk_set_subsampling(3,
+// {1, dx, dx}, {1, dy, dy}) and the colour space, built by the entry point and passed down by value
+// (the engine's own enc_dx / enc_col are not touched).
+struct EncConvCall {
+    EncConvert c;
+    std::vector<uint8_t> cdx, cdy;
+    EncColour col;
+};
+// What no image can make valid.
+static void enc_convert_check(const gk_encode_convert& s) {
+    if (s.space != 4 && s.space != 5)
+        throw GkError("convert: colour space " + std::to_string(s.space) + " (must be GRK_CLRSPC_SYCC 4 or GRK_CLRSPC_EYCC 5)");
+    const bool ok = (s.chroma_dx == 1 && s.chroma_dy == 1) || (s.chroma_dx == 2 && (s.chroma_dy == 1 || s.chroma_dy == 2));
+    if (!ok)
+        throw GkError("convert: chroma subsampling " + std::to_string(s.chroma_dx) + " x " + std::to_string(s.chroma_dy) +
+                      " (must be 1 x 1, 2 x 1 or 2 x 2: 4:4:4, 4:2:2, 4:2:0)");
+    if (s.space == 5 && s.chroma_dx != 1)
+        throw GkError("convert: e-sYCC with subsampled chroma (the display stage converts e-sYCC components of one size only)");
+}
+// What depends on the image.
+static void enc_convert_check_image(const gk_image_info& info) {
+    if (info.numcomps != 3) throw GkError("convert: " + std::to_string(info.numcomps) + " channels (R, G, B: 3)");
+    if (info.sgnd) throw GkError("convert: signed samples");
+    if (info.prec == 0 || info.prec > 16) throw GkError("convert: precision " + std::to_string(info.prec) + " (must be 1..16 bits)");
+    if (!info.w || !info.h) throw GkError("empty image");
+}
+// The component grids under the conversion: (dx, dy) and the plane sizes (grk_image_comp w / h)
+static void enc_convert_grids(const gk_image_info& info, const EncConvert& c, uint32_t dx[3], uint32_t dy[3], uint32_t cw[3],
+                              uint32_t ch[3]) {
+    auto ceildiv64 = [](uint64_t a, uint64_t b) { return (a + b - 1) / b; };
+    for (uint32_t k = 0; k < 3; ++k) {
+        dx[k] = k ? c.dx : 1; dy[k] = k ? c.dy : 1;
+        cw[k] = (uint32_t)(ceildiv64((uint64_t)info.x0 + info.w, dx[k]) - ceildiv64(info.x0, dx[k]));
+        ch[k] = (uint32_t)(ceildiv64((uint64_t)info.y0 + info.h, dy[k]) - ceildiv64(info.y0, dy[k]));
+    }
+}
+
 // What the display flags (gk_set_decode_display) make of the output channels: the CLI's
 // GrkDecompress::postProcess (grk_decompress.cpp:1335-1389, 1495) resolved from the header alone.
 struct DisplayOut {
@@ -3392,6 +3437,7 @@ struct gk_ctx {
     uint32_t enc_b0 = 0, enc_b1 = 0;   // block range of the uploaded encode table
     std::vector<uint8_t> enc_dx, enc_dy;   // gk_set_subsampling: the next encodes' component subsampling
     EncColour enc_col;                     // gk_set_encode_colour: the next encodes' colour description
+    EncConvert enc_conv;                   // gk_set_encode_convert: sticky, read by the encode entry points, never written by an encode
     std::vector<uint8_t> enc_jp2h;         // the jp2h contents of the JP2 encode in progress (setup_plan)
     std::vector<uint32_t> hdr_dx, hdr_dy, hdr_prec, hdr_sgnd;   // the last gk_decode_header's components
     bool enc_rc = false;                // its rate-control flag (GkBlock::flags bit 1)
@@ -3695,7 +3741,12 @@ static float ev_ms(gk_ctx* ctx, int a, int b) {
 // Encode tiles [tb, te) (te = 0: all).  with_header: SOC..main header + tile parts + EOC
 // (a complete codestream); otherwise only the tile parts, back to back, with their
 // lengths in part_lens (tile sharding across devices).
-static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* cp) {
+// cv: the call converts R, G, B to sYCC first (gk_set_encode_convert): its component grids and
+// colour description stand for the engine's.
+static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* cp, const EncConvCall* cv = nullptr) {
+    const std::vector<uint8_t>& enc_dx = cv ? cv->cdx : ctx->enc_dx;
+    const std::vector<uint8_t>& enc_dy = cv ? cv->cdy : ctx->enc_dy;
+    const EncColour& enc_col = cv ? cv->col : ctx->enc_col;
     Plan want;
     want.w = info->w; want.h = info->h; want.nc = info->numcomps; want.prec = info->prec; want.sgnd = info->sgnd;
     set_params(want.p, cp, want.nc);
@@ -3704,9 +3755,9 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     // tile reaches into the image area
     want.x0 = info->x0; want.y0 = info->y0;
     want.gx0 = cp ? cp->tx0 : 0; want.gy0 = cp ? cp->ty0 : 0;
-    if (!ctx->enc_dx.empty()) {   // gk_set_subsampling
-        if (ctx->enc_dx.size() != want.nc) throw GkError("gk_set_subsampling was given a different component count");
-        want.cdx = ctx->enc_dx; want.cdy = ctx->enc_dy;
+    if (!enc_dx.empty()) {   // gk_set_subsampling
+        if (enc_dx.size() != want.nc) throw GkError("gk_set_subsampling was given a different component count");
+        want.cdx = enc_dx; want.cdy = enc_dy;
         if (!want.subsampled()) { want.cdx.clear(); want.cdy.clear(); }
     }
     if (want.gx0 > want.x0 || want.gy0 > want.y0) throw GkError("tile grid origin must lie at or above-left of the image origin");
@@ -3715,7 +3766,7 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     if (want.p.tw && ((uint64_t)want.gx0 + want.p.tw <= want.x0 || (uint64_t)want.gy0 + want.p.th <= want.y0))
         throw GkError("the first tile must overlap the image area");
     if (want.nc < 3) want.p.mct = 0;
-    if (ctx->enc_col.clears_mct()) want.p.mct = 0;   // sYCC / e-sYCC (CodeStreamCompress.cpp:494-500)
+    if (enc_col.clears_mct()) want.p.mct = 0;   // sYCC / e-sYCC (CodeStreamCompress.cpp:494-500)
     // CodeStreamCompress.cpp:501-512: no MCT unless the first three components share a grid
     if (want.p.mct && !want.mct3()) want.p.mct = 0;
     check_poc_coverage(want.p, want.nc);
@@ -3727,7 +3778,7 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     check_precision(want);
     if (want.w == 0 || want.h == 0) throw GkError("empty image");
     // the jp2h contents of this call, built (and a colour description refused) once, here
-    if (want.p.jp2) ctx->enc_jp2h = jp2h_content(want, &ctx->enc_col);
+    if (want.p.jp2) ctx->enc_jp2h = jp2h_content(want, &enc_col);
     // grk_compress.cpp:981-988 (and A.6.1's xcb, ycb): 4 <= side <= 1024, at most 4096 samples
     if (want.p.cbw < 2 || want.p.cbh < 2 || want.p.cbw > 10 || want.p.cbh > 10 || want.p.cbw + want.p.cbh > 12)
         throw GkError("code-block size must be 4..1024 per side with at most 4096 samples");
@@ -3816,8 +3867,9 @@ struct PixSrc { const void* pixels; size_t row_bytes; int on_device; };
 static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
                           int comps_on_device, const gk_cparameters* cp, uint8_t* out, size_t cap, int out_on_device,
                           int* rc, uint32_t tb = 0, uint32_t te = 0, bool with_header = true,
-                          uint32_t* part_lens = nullptr, bool blocks_only = false, const PixSrc* pix = nullptr) {
-    setup_plan(ctx, info, cp);
+                          uint32_t* part_lens = nullptr, bool blocks_only = false, const PixSrc* pix = nullptr,
+                          const EncConvCall* cv = nullptr) {
+    setup_plan(ctx, info, cp, cv);
     Plan& P = ctx->plan;
     const uint32_t ntiles = (uint32_t)P.tiles.size();
     if (te == 0) { tb = 0; te = ntiles; }
@@ -3845,7 +3897,46 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     // group's grid: every row of the image width); host planes are staged back to back
     std::vector<Region> RGg;
     for (const SGroup& G : P.groups) RGg.push_back(group_region(P, RG, G));
-    if (pix) {
+    if (cv) {
+        // R, G, B (packed pixels or three planes of the image's size; the whole image: tile ranges
+        // are refused under a conversion) become Y, Cb, Cr in dplanes, each plane at its own size,
+        // rows starting on GK_UNPIX_ALIGN bytes; host input is staged at its tight width first
+        const Region& RY = RGg[P.group_of[0]];
+        const Region& RC = RGg[P.group_of[1]];
+        GkRgbYccArgs ca{};
+        ca.w = RY.w; ca.h = RY.h; ca.cw = RC.w; ca.ch = RC.h;
+        ca.mode = cv->c.mode(); ca.prec = P.prec;
+        ca.ofx = cv->c.dx == 2 ? (P.x0 & 1u) : 0u; ca.ofy = cv->c.dy == 2 ? (P.y0 & 1u) : 0u;
+        if (RY.w != P.w || RY.h != P.h || ca.cw != (P.w - ca.ofx + cv->c.dx - 1) / cv->c.dx ||
+            ca.ch != (P.h - ca.ofy + cv->c.dy - 1) / cv->c.dy)
+            throw GkError("convert: the chroma grid of the plan is not the conversion's");
+        ca.ys = align_up(ca.w, GK_UNPIX_ALIGN); ca.cs = align_up(std::max(ca.cw, 1u), GK_UNPIX_ALIGN);
+        const size_t ysz = (size_t)ca.ys * ca.h, csz = (size_t)ca.cs * std::max(ca.ch, 1u);
+        uint8_t* dp = (uint8_t*)ctx->dplanes.get((ysz + 2 * csz) * es);
+        ca.y = dp; ca.cb = dp + ysz * es; ca.cr = dp + (ysz + csz) * es;
+        if (pix) {
+            const size_t tight = (size_t)ca.w * 3 * es;
+            ca.packed = 1; ca.src[0] = pix->pixels; ca.row_bytes = pix->row_bytes;
+            if (!pix->on_device) {
+                void* in = ctx->dpix_in.get(tight * ca.h);
+                HIPCHK(hipMemcpy2DAsync(in, tight, pix->pixels, pix->row_bytes, tight, ca.h, hipMemcpyHostToDevice, st));
+                ca.src[0] = in; ca.row_bytes = tight;
+            }
+        } else {
+            const size_t tight = (size_t)ca.w * es;
+            uint8_t* in = comps_on_device ? nullptr : (uint8_t*)ctx->dpix_in.get(tight * ca.h * 3);
+            for (uint32_t c = 0; c < 3; ++c) {
+                ca.src[c] = comps[c]; ca.ss[c] = strides[c];
+                if (comps_on_device) continue;
+                HIPCHK(hipMemcpy2DAsync(in + c * tight * ca.h, tight, comps[c], (size_t)strides[c] * es, tight, ca.h,
+                                        hipMemcpyHostToDevice, st));
+                ca.src[c] = in + c * tight * ca.h; ca.ss[c] = ca.w;
+            }
+        }
+        gk_launch_rgb_ycc(st, (int)es, ca);
+        src[0] = ca.y; src[1] = ca.cb; src[2] = ca.cr;
+        sstr[0] = ca.ys; sstr[1] = sstr[2] = ca.cs;
+    } else if (pix) {
         // packed pixels (one grid): the touched rows, staged at their tight width when they are the
         // host's, are separated into nc planes whose rows start on GK_UNPIX_ALIGN bytes
         const size_t tight = (size_t)RG.w * P.nc * es;
@@ -6655,6 +6746,32 @@ void gk_set_default_params(gk_cparameters* p) {
     for (int i = 0; i < GK_MAXRLVLS; ++i) { p->prcw_init[i] = 1u << 15; p->prch_init[i] = 1u << 15; }
 }
 
+// The call state of an encode under the engine's conversion (gk_set_encode_convert), refusing by
+// name what the conversion cannot take; false when none is set.  Nothing is allocated or launched.
+static bool enc_convert_call(const gk_ctx* ctx, const gk_image_info* info, EncConvCall& cv) {
+    if (!ctx->enc_conv.set()) return false;
+    enc_convert_check_image(*info);
+    for (size_t c = 0; c < ctx->enc_dx.size(); ++c)
+        if (ctx->enc_dx[c] != 1 || ctx->enc_dy[c] != 1)
+            throw GkError("convert: gk_set_subsampling is active (the conversion sets the component grids; R, G, B planes have one size)");
+    const EncColour& E = ctx->enc_col;
+    if (E.set && E.space != ctx->enc_conv.space)
+        throw GkError("convert: the encode colour names colour space " + std::to_string(E.space) + ", the conversion " +
+                      std::to_string(ctx->enc_conv.space));
+    if (E.set && E.palette) throw GkError("convert: the encode colour carries a palette");
+    cv.c = ctx->enc_conv;
+    cv.cdx = {1, (uint8_t)cv.c.dx, (uint8_t)cv.c.dx};
+    cv.cdy = {1, (uint8_t)cv.c.dy, (uint8_t)cv.c.dy};
+    if (E.set) cv.col = E;
+    else { cv.col.set = true; cv.col.space = cv.c.space; }
+    return true;
+}
+// gk_encode_tiles / gk_encode_blocks / gk_main_header: tile ranges of converted input are out of scope
+static void refuse_under_convert(const gk_ctx* ctx, const char* call) {
+    if (ctx->enc_conv.set())
+        throw GkError(std::string("convert: ") + call + " while gk_set_encode_convert is set (whole images only: use gk_encode / gk_encode_pixels, or clear it)");
+}
+
 int gk_encode(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
               int comps_on_device, const gk_cparameters* p, uint8_t* out, size_t cap, size_t* out_len,
               int out_on_device) {
@@ -6664,7 +6781,10 @@ int gk_encode(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, 
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
         int rc = 0;
-        size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc);
+        EncConvCall cv;
+        const bool conv = enc_convert_call(ctx, info, cv);
+        size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc, 0, 0, true,
+                               nullptr, false, nullptr, conv ? &cv : nullptr);
         if (out_len) *out_len = n;
         if (rc == -2) ctx->err = "output capacity too small";
         return rc;
@@ -6683,6 +6803,8 @@ int gk_encode_pixels(gk_ctx* ctx, const gk_image_info* info, const void* pixels,
         ctx->tm.t1_shared = 0;
         // what packed pixels cannot express; whatever gk_encode refuses follows in encode_impl
         // (setup_plan), which allocates nothing before it
+        EncConvCall cv;
+        const bool conv = enc_convert_call(ctx, info, cv);
         for (size_t c = 0; c < ctx->enc_dx.size(); ++c)
             if (ctx->enc_dx[c] != 1 || ctx->enc_dy[c] != 1)
                 throw GkError("pixels: gk_set_subsampling is active (packed pixels have one grid; use the planar call)");
@@ -6693,7 +6815,8 @@ int gk_encode_pixels(gk_ctx* ctx, const gk_image_info* info, const void* pixels,
         if ((uintptr_t)pixels % es) throw GkError("pixels: the buffer is not aligned to its sample size");
         const PixSrc px{pixels, row_bytes, pixels_on_device};
         int rc = 0;
-        size_t n = encode_impl(ctx, info, nullptr, nullptr, 1, p, out, cap, out_on_device, &rc, 0, 0, true, nullptr, false, &px);
+        size_t n = encode_impl(ctx, info, nullptr, nullptr, 1, p, out, cap, out_on_device, &rc, 0, 0, true, nullptr, false, &px,
+                               conv ? &cv : nullptr);
         if (out_len) *out_len = n;
         if (rc == -2) ctx->err = "output capacity too small";
         return rc;
@@ -6711,6 +6834,7 @@ int gk_encode_tiles(gk_ctx* ctx, const gk_image_info* info, const void* const* c
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
+        refuse_under_convert(ctx, "gk_encode_tiles");
         int rc = 0;
         size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc,
                                tile_begin, tile_end, false, part_lens);
@@ -6731,6 +6855,7 @@ int gk_encode_blocks(gk_ctx* ctx, const gk_image_info* info, const void* const* 
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
+        refuse_under_convert(ctx, "gk_encode_blocks");
         if (p && p->tile_size_on && (p->t_width < info->w || p->t_height < info->h))
             throw GkError("code-block results are produced for single-tile images only (Grok's plugin tile is one tile)");
         int rc = 0;
@@ -6761,6 +6886,7 @@ int gk_main_header(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters*
                    size_t* out_len, size_t* tlm_offset, uint32_t* num_tiles) {
     if (!ctx || !info || !out) return -1;
     try {
+        refuse_under_convert(ctx, "gk_main_header");
         setup_plan(ctx, info, p);
         std::vector<uint8_t> H;
         size_t tlm = 0;
@@ -6957,6 +7083,46 @@ int gk_set_encode_colour(gk_ctx* ctx, const gk_encode_colour* spec) {
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_set_encode_convert(gk_ctx* ctx, const gk_encode_convert* spec) {
+    if (!ctx) return -1;
+    try {
+        ctx->enc_conv = EncConvert();   // (cleared first: a refused spec leaves none)
+        if (!spec || spec->space == 0) return 0;
+        enc_convert_check(*spec);
+        ctx->enc_conv.space = spec->space; ctx->enc_conv.dx = spec->chroma_dx; ctx->enc_conv.dy = spec->chroma_dy;
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_probe_encode_convert(const gk_image_info* info, const gk_encode_convert* spec, uint32_t dx[3], uint32_t dy[3],
+                            uint32_t cw[3], uint32_t ch[3], char* msg, size_t msg_cap) {
+    if (!info || !spec) return -1;
+    try {
+        enc_convert_check(*spec);
+        enc_convert_check_image(*info);
+        if ((uint64_t)info->x0 + info->w > 0xffffffffull || (uint64_t)info->y0 + info->h > 0xffffffffull)
+            throw GkError("image area past the 32-bit canvas");
+        (void)sample_type(info->sample_bytes, info->prec, false);
+        EncConvert c;
+        c.space = spec->space; c.dx = spec->chroma_dx; c.dy = spec->chroma_dy;
+        uint32_t gx[3], gy[3], gw[3], gh[3];
+        enc_convert_grids(*info, c, gx, gy, gw, gh);
+        for (int k = 0; k < 3; ++k) {
+            if (dx) dx[k] = gx[k];
+            if (dy) dy[k] = gy[k];
+            if (cw) cw[k] = gw[k];
+            if (ch) ch[k] = gh[k];
+        }
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
         return -1;
     }
 }

@@ -209,6 +209,28 @@ struct GkUnpixArgs {
 };
 // es: bytes per sample (1, 2 or 4)
 void gk_launch_unpixels(hipStream_t st, int es, const GkUnpixArgs& args);
+// Input stage of an encode under gk_set_encode_convert (gk_rgbycc.hip): R, G, B to Y, Cb, Cr with
+// the chroma planes on the grid of `mode` (GK_YCC_444 / 422 / 420), in the same sample type.
+// packed: sample k of pixel (x, y) is read at src[0] + y * row_bytes + (x * 3 + k) * es, and no
+// byte outside the w * 3 * es bytes of a row; otherwise plane k is src[k], row stride ss[k]
+// samples, any alignment of its element.  y, cb, cr are the engine's own planes: bases and the
+// row strides ys / cs aligned to 32 bytes; luma w x h, chroma cw x ch = ceil((w - ofx) / 2) [x
+// ceil((h - ofy) / 2)] on a subsampled axis (ofx / ofy: the image origin's parity there).
+struct GkRgbYccArgs {
+    const void* src[3];
+    uint64_t row_bytes;        // packed
+    uint32_t ss[3];            // planar
+    uint32_t packed;
+    void* y; void* cb; void* cr;
+    uint32_t ys, cs;
+    uint32_t w, h, cw, ch;
+    uint32_t mode;             // GkYccMode below GK_YCC_ESYCC
+    uint32_t ofx, ofy;
+    uint32_t prec;             // 1..16, unsigned
+    uint32_t rows;             // (set by the launcher)
+};
+// es: bytes per sample (1, 2 or 4)
+void gk_launch_rgb_ycc(hipStream_t st, int es, const GkRgbYccArgs& args);
 // Colour management of the display stage (gk_icc.hip): a JP2 file's ICC profile (colr METH 2,
 // matrix / tone-curve classes; gk_icc.h reads it) and the CIELab enumerated space (EnumCS 14)
 // to sRGB, as color_apply_icc_profile / color_cielab_to_rgb (bin/common/color.cpp:423-964) on

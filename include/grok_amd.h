@@ -223,6 +223,43 @@ int gk_set_encode_colour(gk_ctx* ctx, const gk_encode_colour* spec);
 int gk_jp2_boxes(const gk_image_info* info, const gk_encode_colour* spec, uint64_t cs_len, uint8_t* out, size_t cap,
                  size_t* out_len, char* msg, size_t msg_cap);
 
+/* R, G, B in, sYCC out: the mirror of GK_DISPLAY_RGB's sYCC / e-sYCC conversions, done by the
+ * device in front of the encode (k_rgb_ycc).  Grok has no forward conversion to restate (grk_compress
+ * takes subsampled raw YUV, -F); the arithmetic is the engine's own, in integers, p = precision,
+ * offset = 2^(p-1), upb = 2^p - 1:
+ *   Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16                                    per pixel
+ *   Cb = floor((-11059 SR - 21709 SG + 32768 SB + 2^(s-1)) / 2^s) + offset, clamped to [0, upb]
+ *   Cr = floor(( 32768 SR - 27439 SG -  5329 SB + 2^(s-1)) / 2^s) + offset, clamped to [0, upb]
+ * SR, SG, SB: the sums over the chroma sample's box of n = 1, 2 or 4 pixels, s = 16 + log2(n).
+ * Chroma sample (i, j) takes image columns chroma_dx * j + ofx .. + chroma_dx - 1 and rows likewise,
+ * cut at the image's edge; ofx = x0 & 1 when chroma_dx = 2 (ofy likewise): column 0 under an odd x0
+ * and row 0 under an odd y0 belong to no box and give luma only, the pixels sycc422_to_rgb /
+ * sycc420_to_rgb convert without a chroma sample.  e-sYCC: the same formulas (unsigned chroma).
+ * While a conversion is set, gk_encode_pixels with 3 channels and gk_encode with three planes of the
+ * image's size (host or device; u8 / u16 / int32 by gk_image_info::sample_bytes) convert into the
+ * engine's planes and encode them exactly as gk_encode does under gk_set_subsampling(3, {1, dx, dx},
+ * {1, dy, dy}) with colour space `space`: the MCT is cleared, a JP2 file gets colr EnumCS 18 / 24, an
+ * encode colour of the same space is honoured (its cdef), every coding parameter, origin and tile
+ * grid too; the stream is byte for byte the planar encode of the planes defined above.
+ * Refused, each by name, before anything is allocated or launched: a space other than
+ * GRK_CLRSPC_SYCC (4) / GRK_CLRSPC_EYCC (5); (chroma_dx, chroma_dy) other than (1, 1), (2, 1), (2, 2);
+ * e-sYCC with subsampled chroma; a channel count other than 3; signed samples; a precision above 16;
+ * an active gk_set_subsampling (the only way to hand over planes of different sizes); an encode
+ * colour of another colour space or with a palette; gk_encode_tiles / gk_encode_blocks /
+ * gk_main_header while a conversion is set; whatever the subsampled planar encode refuses (a tile
+ * size the factors do not divide). */
+typedef struct gk_encode_convert {
+    uint32_t space;                  /* 0 none, GRK_CLRSPC_SYCC (4), GRK_CLRSPC_EYCC (5) */
+    uint32_t chroma_dx, chroma_dy;
+} gk_encode_convert;
+/* Sticky; spec = NULL (or space 0) clears it: every call is then byte for byte as without.  A
+ * refused spec leaves none set.  No encode changes it. */
+int gk_set_encode_convert(gk_ctx* ctx, const gk_encode_convert* spec);
+/* What an encode of `info` under `spec` codes, no device needed: the components' dx / dy and plane
+ * sizes cw x ch (any may be NULL); 0, or -1 with the refusal in msg. */
+int gk_probe_encode_convert(const gk_image_info* info, const gk_encode_convert* spec, uint32_t dx[3], uint32_t dy[3],
+                            uint32_t cw[3], uint32_t ch[3], char* msg, size_t msg_cap);
+
 /* grk_decompress_read_header (grok.cpp:287-297, CodeStreamDecompress::readHeader) of a raw
  * codestream or a JP2 file (its jp2c box; FileFormatDecompress::read_box_hdr :632-672). */
 int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, gk_image_info* info);
