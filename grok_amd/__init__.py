@@ -29,7 +29,9 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_probe_stream_components", "gk_set_decode_display", "gk_probe_display", "gk_set_decode_precision",
            "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels", "gk_encode_pixels",
            "gk_set_encode_colour", "gk_jp2_boxes", "gk_header_cielab", "gk_probe_cielab",
-           "gk_set_encode_convert", "gk_probe_encode_convert")
+           "gk_set_encode_convert", "gk_probe_encode_convert", "gk_set_default_transcode", "gk_transcode",
+           "gk_probe_transcode")
+GK_TRANSCODE_HT, GK_TRANSCODE_PART1 = 1, 2   # gk_transcode_params::target
 GK_MAX_CHANNELS = 256
 GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB, GK_DISPLAY_ICC = 1, 2, 4, 8   # gk_set_decode_display flags
 GK_PREC_CLIP, GK_PREC_SCALE = 0, 1   # gk_precision::mode (grk_precision_mode)
@@ -105,6 +107,19 @@ class CParameters(ctypes.Structure):
         ("num_comments", ctypes.c_uint32), ("comment", ctypes.c_char_p * 256), ("comment_len", ctypes.c_uint16 * 256),
         ("is_binary_comment", ctypes.c_uint8 * 256),
     ]
+
+
+class TranscodeParams(ctypes.Structure):
+    """gk_transcode_params (include/grok_amd.h)."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("target", "tlm", "plt", "com")]
+
+
+def _transcode_params(target, tlm=False, plt=False, com=True):
+    """target: "ht" | "part1" (or GK_TRANSCODE_HT / GK_TRANSCODE_PART1)."""
+    t = {"ht": GK_TRANSCODE_HT, "part1": GK_TRANSCODE_PART1}.get(target, target)
+    if t not in (GK_TRANSCODE_HT, GK_TRANSCODE_PART1):
+        raise ValueError("transcode target %r: expected 'ht' or 'part1'" % (target,))
+    return TranscodeParams(t, int(bool(tlm)), int(bool(plt)), int(bool(com)))
 
 
 class ImageInfo(ctypes.Structure):
@@ -353,6 +368,13 @@ def load_library(build_if_missing=True):
     lib.gk_probe_encode_convert.restype = ctypes.c_int
     lib.gk_probe_encode_convert.argtypes = [P(ImageInfo), P(EncodeConvert)] + [P(ctypes.c_uint32)] * 4 + \
         [ctypes.c_char_p, ctypes.c_size_t]
+    lib.gk_set_default_transcode.argtypes = [P(TranscodeParams)]
+    lib.gk_transcode.restype = ctypes.c_int
+    lib.gk_transcode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(TranscodeParams),
+                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_size_t)]
+    lib.gk_probe_transcode.restype = ctypes.c_int
+    lib.gk_probe_transcode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, P(TranscodeParams), ctypes.c_char_p,
+                                       ctypes.c_size_t]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -440,6 +462,18 @@ def probe_header(cs):
     if lib.gk_probe_header(b.ctypes.data, len(b), ctypes.byref(info), None, msg, 256) != 0:
         raise ValueError(msg.value.decode())
     return info
+
+
+def probe_transcode(cs, target="ht", tlm=False, plt=False, com=True):
+    """gk_probe_transcode: whether host codestream / JP2 bytes would transcode to `target` ("ht" |
+    "part1"); no engine or GPU needed (headers and packet headers are parsed on the host).  Returns
+    None, or raises ValueError with the refusal Engine.transcode would give."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    tp = _transcode_params(target, tlm, plt, com)
+    msg = ctypes.create_string_buffer(512)
+    if lib.gk_probe_transcode(b.ctypes.data, len(b), ctypes.byref(tp), msg, 512) != 0:
+        raise ValueError(msg.value.decode())
 
 
 def probe_colour(cs):
@@ -667,6 +701,38 @@ class Engine:
                                     buf.ctypes.data, n.value, ctypes.byref(n), 0)
         if rc != 0:
             self._err("gk_encode")
+        return buf[:n.value].tobytes()
+
+    def transcode(self, cs, target="ht", out=None, tlm=False, plt=False, com=True, length=None):
+        """gk_transcode: the codestream or JP2 file `cs` (bytes, or a torch cuda uint8 tensor with
+        `length`) re-coded with the other block coder, target "ht" | "part1", coefficient for
+        coefficient (no DWT, no second lossy generation).  Returns bytes, or with ``out`` (a torch
+        cuda uint8 tensor) the length written into it on the device, as encode does.  A refusal
+        (include/grok_amd.h lists them) raises RuntimeError with its message."""
+        tp = _transcode_params(target, tlm, plt, com)
+        on_dev = _is_torch_cuda(cs)
+        if on_dev:
+            assert cs.is_contiguous() and cs.element_size() == 1
+            src, n_in = cs.data_ptr(), int(length if length is not None else cs.numel())
+        else:
+            keep = np.frombuffer(bytes(cs), np.uint8)
+            src, n_in = keep.ctypes.data, len(keep)
+        n = ctypes.c_size_t()
+        if out is not None:
+            rc = self.lib.gk_transcode(self.ctx, src, n_in, int(on_dev), ctypes.byref(tp), ctypes.c_void_p(out.data_ptr()),
+                                       out.numel(), 1, ctypes.byref(n))
+            if rc != 0:
+                self._err("gk_transcode")
+            return n.value
+        cap = 2 * n_in + (1 << 16)
+        buf = np.empty(cap, np.uint8)
+        rc = self.lib.gk_transcode(self.ctx, src, n_in, int(on_dev), ctypes.byref(tp), buf.ctypes.data, cap, 0, ctypes.byref(n))
+        if rc == -2:
+            buf = np.empty(n.value, np.uint8)
+            rc = self.lib.gk_transcode(self.ctx, src, n_in, int(on_dev), ctypes.byref(tp), buf.ctypes.data, n.value, 0,
+                                       ctypes.byref(n))
+        if rc != 0:
+            self._err("gk_transcode")
         return buf[:n.value].tobytes()
 
     def set_encode_colour(self, space=None, icc=None, channels=None, palette=None):

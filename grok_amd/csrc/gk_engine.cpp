@@ -3864,12 +3864,101 @@ static void dump_blocks(gk_ctx* ctx, const uint32_t* hinfo, const GkPass* dps, u
 // where it would stage host planes, and goes on as if the caller had passed those device planes.
 struct PixSrc { const void* pixels; size_t row_bytes; int on_device; };
 
+// ---- Transcode (gk_transcode): Part-1 <-> HTJ2K at the block-coder level.  The source coder's
+// decoders leave signed quantisation indices in work plane A (decode_core stops after T1), the
+// target coder's encoders read them there (encode_impl starts at T1): no DWT, MCT or sample stage.
+struct Xcode {
+    bool to_ht = true;
+    uint32_t tlm = 0, plt = 0, com = 1;
+    uint32_t rsiz = 0, mct = 0;                             // the source's Rsiz and SGcod MCT byte
+    std::vector<std::pair<uint32_t, std::string>> coms;     // the source's COM markers (Rcom, bytes)
+    std::vector<uint8_t> prefix;                            // a JP2 source: the file up to its jp2c box
+    std::vector<uint8_t> suffix;                            // and the boxes behind it
+    bool jp2 = false, jp2c_xl = false, jp2c_to_end = false; // jp2c: XLBox form, LBox 0 (to the end of the file)
+    std::vector<uint8_t> qcd_body;                          // the source's QCD body and, per component, its
+    std::vector<std::vector<uint8_t>> qbody;                // quantisation body (its QCC's, else the QCD's)
+    float t2_parse_ms = 0.f, stage_ms = 0.f, t1_dec_ms = 0.f;   // the decode half's times
+};
+// The main header of a transcode: the source's SIZ, coding and quantisation (QCD / QCC bodies as
+// read, band_qcd in the plan's bands), RGN and COM, with the target coder's code-block style, Rsiz
+// bit 14 and CAP; markers in write_main_header's order.
+static void write_xcode_header(std::vector<uint8_t>& o, const Plan& P, const Xcode& X, size_t* tlm_pos) {
+    put16(o, 0xff4f);
+    put16(o, 0xff51); put16(o, 38 + 3 * P.nc);
+    put16(o, P.p.ht() ? (X.rsiz | 0x4000u) : (X.rsiz & ~0x4000u));
+    put32(o, P.x0 + P.w); put32(o, P.y0 + P.h); put32(o, P.x0); put32(o, P.y0);
+    put32(o, P.p.tw ? P.p.tw : P.x0 + P.w - P.gx0); put32(o, P.p.th ? P.p.th : P.y0 + P.h - P.gy0);
+    put32(o, P.gx0); put32(o, P.gy0);
+    put16(o, P.nc);
+    for (uint32_t i = 0; i < P.nc; ++i) {
+        o.push_back((uint8_t)((P.c_prec(i) - 1) | (P.c_sgnd(i) ? 0x80 : 0)));
+        o.push_back((uint8_t)P.sx(i)); o.push_back((uint8_t)P.sy(i));
+    }
+    if (P.p.ht()) {
+        // CAP: MAGBp bounds the coded magnitudes.  Reversible: the largest band bit-plane count of
+        // the stream, exponent + guard bits - 1 plus the component's ROI shift (the bands' numbps
+        // under the source's QCD / QCC).  Irreversible: write_main_header's count (Grok's
+        // get_MAGBp takes a scalar-expounded band's decomposition level off), so that a stream the
+        // engine's HT encoder wrote comes back with the CAP it had.
+        uint32_t B = 0;
+        for (uint32_t c = 0; c < P.nc; ++c)
+            for (uint32_t r = 0; r < P.p.numres; ++r)
+                for (const BandG& Bd : P.tiles[0].comps[c].res[r].bands) {
+                    const uint32_t lev = (P.p.numres - 1) - (r ? r - 1 : 0);
+                    B = std::max(B, P.p.irrev ? Bd.numbps + 1 - std::min(lev, Bd.numbps + 1) : Bd.numbps);
+                }
+        const uint32_t Bp = B <= 8 ? 0 : B < 28 ? B - 8 : B < 48 ? 13 + (B >> 2) : 31;
+        put16(o, 0xff50); put16(o, 8); put32(o, 0x00020000); put16(o, (P.p.irrev ? 0x20 : 0) | Bp);
+    }
+    put16(o, 0xff52); put16(o, 12 + (P.p.custom_prc ? P.p.numres : 0));
+    o.push_back((uint8_t)(P.p.custom_prc ? 1 : 0));   // Scod: no SOP / EPH
+    o.push_back((uint8_t)P.p.prog);
+    put16(o, 1);                                      // one layer
+    o.push_back((uint8_t)X.mct);
+    o.push_back((uint8_t)(P.p.numres - 1));
+    o.push_back((uint8_t)(P.p.cbw - 2)); o.push_back((uint8_t)(P.p.cbh - 2));
+    o.push_back((uint8_t)P.p.cblk_sty);
+    o.push_back(P.p.irrev ? 0 : 1);
+    if (P.p.custom_prc) for (uint32_t r = 0; r < P.p.numres; ++r) o.push_back((uint8_t)(P.p.prcw[r] | (P.p.prch[r] << 4)));
+    put16(o, 0xff5c); put16(o, 2 + (uint32_t)X.qcd_body.size());
+    o.insert(o.end(), X.qcd_body.begin(), X.qcd_body.end());
+    for (uint32_t c = 0; c < P.nc; ++c)
+        if (X.qbody[c] != X.qcd_body) {
+            const uint32_t cw = P.nc <= 256 ? 1 : 2;
+            put16(o, 0xff5d); put16(o, 2 + cw + (uint32_t)X.qbody[c].size());
+            if (cw == 1) o.push_back((uint8_t)c); else put16(o, c);
+            o.insert(o.end(), X.qbody[c].begin(), X.qbody[c].end());
+        }
+    if (P.p.tlm) {
+        const uint32_t nt = (uint32_t)P.tiles.size();
+        if (4 + 6 * (size_t)nt > 65535) throw GkError("too many tiles for one TLM marker");
+        put16(o, 0xff55); put16(o, (uint32_t)(4 + 6 * (size_t)nt)); o.push_back(0); o.push_back(0x60);
+        if (tlm_pos) *tlm_pos = o.size();
+        o.insert(o.end(), (size_t)(6 * (size_t)nt), 0);
+    }
+    for (uint32_t c = 0; c < P.nc; ++c)
+        if (P.p.roi(c)) {
+            const uint32_t cw = P.nc <= 256 ? 1 : 2;
+            put16(o, 0xff5e); put16(o, 4 + cw);
+            if (cw == 1) o.push_back((uint8_t)c); else put16(o, c);
+            o.push_back(0);
+            o.push_back((uint8_t)P.p.roi(c));
+        }
+    if (X.com)
+        for (const auto& c : X.coms) {
+            put16(o, 0xff64); put16(o, 4 + (uint32_t)c.second.size()); put16(o, c.first);
+            o.insert(o.end(), c.second.begin(), c.second.end());
+        }
+}
+
 static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
                           int comps_on_device, const gk_cparameters* cp, uint8_t* out, size_t cap, int out_on_device,
                           int* rc, uint32_t tb = 0, uint32_t te = 0, bool with_header = true,
                           uint32_t* part_lens = nullptr, bool blocks_only = false, const PixSrc* pix = nullptr,
-                          const EncConvCall* cv = nullptr) {
-    setup_plan(ctx, info, cp, cv);
+                          const EncConvCall* cv = nullptr, const Xcode* xc = nullptr) {
+    // xc (a transcode): the plan is the target's and work plane A holds the source's quantisation
+    // indices; the call starts at T1 and writes the header the transcode keeps
+    if (!xc) setup_plan(ctx, info, cp, cv);
     Plan& P = ctx->plan;
     const uint32_t ntiles = (uint32_t)P.tiles.size();
     if (te == 0) { tb = 0; te = ntiles; }
@@ -3887,6 +3976,10 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     // work planes for the sample rows of the selected tiles only
     const Region RG = make_region(0, ry0, P.w, ry1);
     int32_t* arena = (int32_t*)ctx->arena.get(RG.plane * P.nc * 2 * sizeof(int32_t));
+    if (xc) {
+        HIPCHK(hipEventRecord(ctx->ev[1], st));
+        HIPCHK(hipEventRecord(ctx->ev[2], st));
+    } else {
     const uint32_t nrows = ry1 - ry0;
     // the caller's planes (int32 or 8/16-bit samples); host planes are staged (those rows only)
     const int stype = sample_type(info->sample_bytes, P.prec, P.sgnd != 0);
@@ -4011,6 +4104,7 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
             fclose(f);
         }
     }
+    }
     launch_check(__LINE__);
     HIPCHK(hipEventRecord(ctx->ev[3], st));
     // T1 over the block range [b0, b1): every per-block device array is range-local
@@ -4025,12 +4119,33 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     uint32_t* dinfo = (uint32_t*)ctx->dinfo.get(16 * (size_t)nbx + 16);
     int* derr = (int*)ctx->derr.get(64);
     uint32_t* dpcount = (uint32_t*)(derr + 4);
-    uint8_t* dsym = P.p.ht() ? nullptr : (uint8_t*)ctx->dsym.get(P.sym_off[b1] - P.sym_off[b0] + 256);
+    // a transcode's bands carry the source's bit-plane counts: its symbol streams are sized by them
+    // (per block: its band's count under the source's QCD / QCC, which the plan's own table does not hold)
+    std::vector<uint8_t> xnumbps;
+    std::vector<uint64_t> xsym;
+    if (xc) {
+        xnumbps.resize(nb);
+        for (const TileG& T : P.tiles)
+            for (uint32_t c = 0; c < P.nc; ++c)
+                for (const ResG& R : T.comps[c].res)
+                    for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
+                        for (const PrecG& PG : R.prc[bi])
+                            for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) xnumbps[PG.first_block + k] = (uint8_t)R.bands[bi].numbps;
+        xsym.resize((size_t)nb + 1);
+        uint64_t so = 0;
+        for (uint32_t i = 0; i < nb; ++i) {
+            xsym[i] = so;
+            so = (so + (uint64_t)(xnumbps[i] + 1) * 11264u + 255) & ~255ull;
+        }
+        xsym[nb] = so;
+    }
+    const std::vector<uint64_t>& sym_off = xc && !P.p.ht() ? xsym : P.sym_off;
+    uint8_t* dsym = P.p.ht() ? nullptr : (uint8_t*)ctx->dsym.get(sym_off[b1] - sym_off[b0] + 256);
     uint64_t* dsymoff = (uint64_t*)ctx->dsymoff.get(8 * ((size_t)nbr + 1));
     uint32_t* dpe = (uint32_t*)ctx->dpassend.get(4 * GK_MAX_PASSES * (size_t)nbx);
     uint32_t* dcm = (uint32_t*)ctx->dcminfo.get(8 * (size_t)nbx);
     int32_t* dnmse = do_rc ? (int32_t*)ctx->dnmse.get(4 * GK_MAX_PASSES * (size_t)nbx) : nullptr;
-    if (!ctx->blocks_uploaded || ctx->enc_b0 != b0 || ctx->enc_b1 != b1 || ctx->enc_rc != do_rc) {
+    if (xc || !ctx->blocks_uploaded || ctx->enc_b0 != b0 || ctx->enc_b1 != b1 || ctx->enc_rc != do_rc) {
         // the range's blocks with offsets into this call's planes and slots
         GkBlock* hb = (GkBlock*)ctx->hpasses.get(sizeof(GkBlock) * nbx + 8 * ((size_t)nbr + 1));
         uint64_t* hso = (uint64_t*)(hb + nbx);
@@ -4041,11 +4156,12 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
             hb[i].data_off -= slot0;
             hb[i].flags = (uint8_t)((hb[i].flags & ~2u) | (do_rc ? 2u : 0u));
         }
-        for (uint32_t i = 0; i <= nbr; ++i) hso[i] = P.sym_off[b0 + i] - P.sym_off[b0];
+        if (xc) for (uint32_t i = 0; i < nbr; ++i) hb[i].band_numbps = xnumbps[b0 + i];
+        for (uint32_t i = 0; i <= nbr; ++i) hso[i] = sym_off[b0 + i] - sym_off[b0];
         HIPCHK(hipMemcpyAsync(dblk, hb, sizeof(GkBlock) * nbr, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(dsymoff, hso, 8 * ((size_t)nbr + 1), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));   // the staging buffer is reused below
-        ctx->blocks_uploaded = true; ctx->enc_b0 = b0; ctx->enc_b1 = b1; ctx->enc_rc = do_rc;
+        ctx->blocks_uploaded = !xc; ctx->enc_b0 = b0; ctx->enc_b1 = b1; ctx->enc_rc = do_rc;
     }
     HIPCHK(hipMemsetAsync(derr, 0, 64, st));
     // solo MQ waves (gk_t1enc.hip mq_solo_block): GK_T1ENC_SOLO = how many of the heaviest blocks
@@ -4056,15 +4172,17 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
         uint8_t* mel = (uint8_t*)ctx->dsym.get((size_t)nbx * GK_HT_MEL_CAP + 256);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[8], st));
-        gk_launch_ht_enc(st, arena, dblk, dbytes, mel, GK_HT_MEL_CAP, dinfo, nbr, derr, P.p.wide());
+        gk_launch_ht_enc(st, arena, dblk, dbytes, mel, GK_HT_MEL_CAP, dinfo, nbr, derr, P.p.wide(), xc != nullptr);
     } else if (P.p.t1_generic()) {
         // mode switches: lane-per-block coder with per-pass termination rules (gk_t1ms.hip)
         uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(nbx));
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[8], st));
-        gk_launch_t1_enc_ms(st, arena, dblk, dbytes, dps, dinfo, nbr, derr, ctx->nmse_tab, dpcount, mst, P.p.cblk_sty & 0x3f);
+        gk_launch_t1_enc_ms(st, arena, dblk, dbytes, dps, dinfo, nbr, derr, ctx->nmse_tab, dpcount, mst, P.p.cblk_sty & 0x3f,
+                            xc != nullptr);
     } else if (nbr < 8192 || getenv("GK_T1ENC_SERIAL")) {
-        gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse);
+        gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse, nullptr, 0, 0xffffffffu,
+                        xc != nullptr);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[8], st));
         gk_launch_t1_mq(st, dsym, dsymoff, dpe, dcm, dblk, dbytes, dps, dinfo, nbr, derr, dnmse, dpcount, nullptr, 0,
@@ -4120,7 +4238,8 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
         const int nch = (int)cut.size() - 1;
         for (int k = 0; k < nch; ++k) {
             const uint32_t base = cut[k], cnt = cut[k + 1] - cut[k];
-            gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse, dord, base, cnt);
+            gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse, dord, base, cnt,
+                            xc != nullptr);
             if (k + 1 < nch) {
                 HIPCHK(hipEventRecord(ctx->xev[k], st));
                 HIPCHK(hipStreamWaitEvent(ctx->aux[k], ctx->xev[k], 0));
@@ -4168,7 +4287,8 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     std::vector<uint8_t> H;
     H.reserve(1 << 12);
     size_t tlm_pos = 0;
-    write_main_header(H, P, &tlm_pos);
+    if (xc) write_xcode_header(H, P, *xc, &tlm_pos);
+    else write_main_header(H, P, &tlm_pos);
     // updateRates' header bytes: the stream position after the main header (JP2 boxes and the
     // jp2c box header come first in a .jp2), CodeStreamCompress.cpp:963
     const size_t rc_header_size = H.size() + (P.p.jp2 ? jp2_prefix_size(P, ctx->enc_jp2h) : 0);
@@ -4232,6 +4352,7 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     std::vector<uint8_t> J;
     const bool jp2 = P.p.jp2 && with_header;
     if (jp2) write_jp2_prefix(J, P, 0, ctx->enc_jp2h);
+    if (xc && xc->jp2) J = xc->prefix;   // a JP2 source: its boxes as they are, up to the jp2c header
     add_host(J.data(), J.size());
     const size_t main_at = J.size();   // the main header's position in hdrs
     add_host(H.data(), H.size());
@@ -4511,6 +4632,19 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     }
     uint8_t eoc[2] = {0xff, 0xd9};
     if (with_header) add_host(eoc, 2);
+    if (xc && xc->jp2) {   // the new jp2c length (its form kept), then the boxes behind the codestream
+        const uint64_t cs_len = pos - J.size();
+        uint8_t* h = hdrs.data() + J.size() - (xc->jp2c_xl ? 16 : 8);
+        if (xc->jp2c_xl) {
+            const uint64_t L = cs_len + 16;
+            for (int k = 0; k < 8; ++k) h[8 + k] = (uint8_t)(L >> (8 * (7 - k)));
+        } else if (!xc->jp2c_to_end) {
+            const uint64_t L = cs_len + 8;
+            if (L >= (1ull << 32)) throw GkError("transcode: the codestream no longer fits the jp2c box's 32-bit length");
+            for (int k = 0; k < 4; ++k) h[k] = (uint8_t)(L >> (8 * (3 - k)));
+        }
+        add_host(xc->suffix.data(), xc->suffix.size());
+    }
     const size_t total = pos;
     if (jp2) {
         const size_t prefix = J.size();
@@ -5639,12 +5773,214 @@ static void decode_call(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const
     decode_planes(ctx, o, dst, rq, stg);
 }
 
+// ---- T2 parse of one tile (T2Decompress.cpp:216-570): its packets in progression order into
+// tile-local state (index = block - tile's first block).
+namespace {
+struct Chunk { uint64_t pos; uint32_t b, len, boff; };   // boff: the block's bytes before this chunk
+struct PartState {
+    std::vector<Chunk> chunks;
+    std::vector<uint8_t> included, numbps;
+    std::vector<uint16_t> npasses;
+    std::vector<uint32_t> numlenbits, len;
+    // BYPASS / TERMALL: per block the byte length of each codeword segment and the passes
+    // of its last segment (T2Decompress::initSegment, T2Decompress.cpp:28-54)
+    std::vector<std::vector<uint32_t>> seglens;
+    std::vector<uint16_t> segp;
+};
+}  // namespace
+// need: per tile-local block, whether its bytes are wanted; dec_layers / dec_reduce: the layer limit
+// (0 = all) and the resolutions discarded
+static void t2_parse_part(const Plan& P, const TilePart& TPt, const std::vector<uint8_t>& need, uint32_t dec_layers,
+                          uint32_t dec_reduce, ByteSrc& BS, PartState& st2) {
+    // BYPASS / TERMALL components: several codeword segments per block (per component with COC)
+    auto comp_multiseg = [&](uint32_t c) { return (P.p.c_sty(c) & (GK_STY_LAZY | GK_STY_TERMALL)) != 0; };
+    bool multiseg = false;
+    for (uint32_t c = 0; c < P.nc; ++c) multiseg = multiseg || comp_multiseg(c);
+    auto seg_max = [&](uint32_t c, uint32_t sg) -> uint32_t {
+        if (P.p.c_sty(c) & GK_STY_TERMALL) return 1;
+        return sg == 0 ? 10 : ((sg & 1) ? 2 : 1);
+    };
+    struct Trees { DecTree incl, imsb; };
+    std::vector<Trees> trees;
+    std::unordered_map<uint32_t, size_t> tidx;   // trees by first_block of each precinct-band
+    const TileG& TG = P.tiles[TPt.tile];
+    const uint32_t tb0 = TG.b0, ntb = TG.b1 - TG.b0;
+    st2.included.assign(ntb, 0); st2.numbps.assign(ntb, 0); st2.npasses.assign(ntb, 0);
+    st2.numlenbits.assign(ntb, 0); st2.len.assign(ntb, 0);
+    if (multiseg) { st2.seglens.assign(ntb, {}); st2.segp.assign(ntb, 0); }
+    st2.chunks.reserve(ntb);
+    size_t tile_end = TPt.end;
+    size_t pos = TPt.data, pk = 0, nextp = 0;
+    ByteSrc HS;   // the tile's packed packet headers (PPM / PPT)
+    HS.host = TPt.hdrs.data(); HS.len = TPt.hdrs.size();
+    size_t hpos = 0;
+    const std::vector<PacketRef> order = packet_order(P, TG, P.p.nlayers, TPt.pocs.empty() ? &P.p.pocs : &TPt.pocs);
+    // layer limit (tcp->numLayersToDecompress): packets of later layers are skipped through
+    // PLT or parsed without their data (T2Decompress::processPacket, T2Decompress.cpp:55-116)
+    const uint32_t maxl = dec_layers ? std::min(dec_layers, P.p.nlayers) : P.p.nlayers;
+    for (size_t oi = 0; oi < order.size(); ++oi, ++pk) {
+                    const uint32_t l = order[oi].l, r = order[oi].r, c = order[oi].c, pi = order[oi].pi;
+                    const ResG& R = TG.comps[c].res[r];
+                    const uint32_t rmax = P.p.c_numres(c) - dec_reduce;   // resolutions decoded
+                    const bool mseg = comp_multiseg(c);
+                    while (pos >= tile_end && nextp < TPt.more.size()) {   // the tile's next tile part
+                        pos = TPt.more[nextp].first; tile_end = TPt.more[nextp].second; ++nextp;
+                    }
+                    if (pos >= tile_end) return;
+                    const bool skip_l = l >= maxl || r >= rmax;
+                    if (skip_l && pk < TPt.plt.size()) { pos += TPt.plt[pk]; continue; }
+                    if (pk < TPt.plt.size()) {   // PLT: a packet with no needed block is skipped unread
+                        bool any = false;
+                        for (uint32_t bi = 0; bi < R.bands.size() && !any; ++bi) {
+                            const PrecG& PG = R.prc[bi][pi];
+                            for (uint32_t k = 0; k < PG.cw * PG.ch && !any; ++k) any = need[PG.first_block + k - tb0];
+                        }
+                        if (!any) { pos += TPt.plt[pk]; continue; }
+                    }
+                    if (P.p.sop_eph & 2) {   // SOP: FF91 0004 Nsop (T2Decompress::readPacketHeader :226-250)
+                        if (tile_end - pos < 6 || BS.be16(pos) != 0xff91) throw GkError("expected SOP marker");
+                        if (BS.be16(pos + 4) != (pk & 0xffff)) throw GkError("SOP marker packet counter mismatch");
+                        pos += 6;
+                    }
+                    // the header from the packed headers (PPM / PPT) when the tile has them, else in
+                    // front of the body (T2Decompress.cpp:255-270)
+                    BitReader br = TPt.packed ? BitReader(HS, hpos, HS.len) : BitReader(BS, pos, tile_end);
+                    std::vector<std::pair<uint32_t, uint32_t>> contrib;
+                    if (br.read(1)) {
+                        for (uint32_t bi = 0; bi < R.bands.size(); ++bi) {
+                            const PrecG& PG = R.prc[bi][pi];
+                            if (!PG.cw || !PG.ch) continue;
+                            auto it = tidx.find(PG.first_block);
+                            if (it == tidx.end()) {
+                                trees.emplace_back();
+                                trees.back().incl.build(PG.cw, PG.ch);
+                                trees.back().imsb.build(PG.cw, PG.ch);
+                                it = tidx.emplace(PG.first_block, trees.size() - 1).first;
+                            }
+                            Trees& T = trees[it->second];
+                            for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
+                                const uint32_t b = PG.first_block + k - tb0;
+                                uint32_t inc;
+                                if (!st2.included[b]) inc = T.incl.decode(br, k, l + 1) <= l ? 1 : 0;
+                                else inc = br.read(1);
+                                if (!inc) continue;
+                                if (!st2.included[b]) {
+                                    // zero bit-planes: Grok raises the threshold one plane at a time
+                                    // until the leaf is known; a tag tree reads a node's bits only
+                                    // once its parent is known, so one walk with threshold 64 reads
+                                    // exactly the same bits
+                                    const uint32_t v = T.imsb.decode(br, k, 64);
+                                    const uint32_t kmsbs = v < 64 ? v : 64;
+                                    const uint32_t bnb = R.bands[bi].numbps;
+                                    st2.numbps[b] = (uint8_t)(kmsbs > bnb ? 0 : bnb - kmsbs);
+                                    st2.numlenbits[b] = 3;
+                                    st2.included[b] = 1;
+                                }
+                                const uint32_t np = br.numpasses();
+                                st2.numlenbits[b] += br.commacode();
+                                uint32_t sl = 0;
+                                if (!mseg) {
+                                    const uint32_t nbits = st2.numlenbits[b] + floorlog2(np);
+                                    if (nbits > 32) throw GkError("corrupt packet header (segment length)");
+                                    sl = br.read((int)nbits);
+                                } else {
+                                    // one length per segment part; a segment continues across
+                                    // packets until it holds its maximum pass count
+                                    std::vector<uint32_t>& SL = st2.seglens[b];
+                                    for (uint32_t left = np; left;) {
+                                        if (SL.empty() || st2.segp[b] == seg_max(c, (uint32_t)SL.size() - 1)) {
+                                            if (SL.size() >= GK_MAX_PASSES) throw GkError("corrupt packet header (segments)");
+                                            SL.push_back(0); st2.segp[b] = 0;
+                                        }
+                                        const uint32_t n = std::min(seg_max(c, (uint32_t)SL.size() - 1) - st2.segp[b], left);
+                                        const uint32_t nbits = st2.numlenbits[b] + floorlog2(n);
+                                        if (nbits > 32) throw GkError("corrupt packet header (segment length)");
+                                        const uint32_t part = br.read((int)nbits);
+                                        if (!skip_l) SL.back() += part;
+                                        sl += part;
+                                        st2.segp[b] = (uint16_t)(st2.segp[b] + n);
+                                        left -= n;
+                                    }
+                                }
+                                if (st2.npasses[b] + np > GK_MAX_PASSES) throw GkError("corrupt packet header (pass count)");
+                                if (!skip_l) st2.npasses[b] = (uint16_t)(st2.npasses[b] + np);
+                                contrib.push_back({b, sl});
+                            }
+                        }
+                    }
+                    br.align();
+                    if (TPt.packed) {
+                        hpos = br.off;
+                        if (hpos > HS.len) throw GkError("corrupt packed packet headers");
+                        if (P.p.sop_eph & 4) {   // EPH after the header, in the packed headers
+                            if (HS.len - hpos < 2 || HS.be16(hpos) != 0xff92) throw GkError("expected EPH marker");
+                            hpos += 2;
+                        }
+                    } else {
+                    pos = br.off;
+                    if (P.p.sop_eph & 4) {   // EPH after the header (:469-486)
+                        if (tile_end - pos < 2 || BS.be16(pos) != 0xff92) throw GkError("expected EPH marker");
+                        pos += 2;
+                    }
+                    }
+                    for (auto& ct : contrib) {
+                        const uint32_t n = (uint32_t)std::min<size_t>(ct.second, tile_end > pos ? tile_end - pos : 0);
+                        if (n && need[ct.first] && !skip_l) {
+                            st2.chunks.push_back({pos, ct.first, n, st2.len[ct.first]});
+                            st2.len[ct.first] += n;
+                        }
+                        pos += ct.second;
+                    }
+    }
+}
+
+static const char* const kBandName[4] = {"LL", "HL", "LH", "HH"};
+// The refusals that need the parsed packet headers of one tile: a Part-1 block some of whose
+// passes are missing (its undecoded planes would have to be invented), an HT block with SigProp /
+// MagRef passes (k_ht_dec decodes the cleanup pass only).
+static void xcode_check_part(const Plan& P, const TilePart& TPt, const PartState& st2) {
+    const TileG& T = P.tiles[TPt.tile];
+    for (uint32_t c = 0; c < P.nc; ++c)
+        for (uint32_t r = 0; r < (uint32_t)T.comps[c].res.size(); ++r) {
+            const ResG& R = T.comps[c].res[r];
+            for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
+                for (uint32_t pi = 0; pi < R.pw * R.ph; ++pi) {
+                    const PrecG& PG = R.prc[bi][pi];
+                    for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
+                        const uint32_t b = PG.first_block + k, lb = b - T.b0;
+                        if (!st2.included[lb]) continue;
+                        const uint32_t np = st2.npasses[lb], nbp = st2.numbps[lb];
+                        char msg[256];
+                        if (P.p.c_ht(c)) {
+                            if (np <= 1) continue;
+                            snprintf(msg, sizeof msg, "transcode: HT code-block with SigProp / MagRef passes (tile %u, component %u, "
+                                     "resolution %u, band %s, block %u: %u passes)", TPt.tile, c, r, kBandName[R.bands[bi].orient & 3],
+                                     lb, np);
+                            throw GkError(msg);
+                        }
+                        const uint32_t full = nbp ? 3 * nbp - 2 : 0, rs = P.p.roi(c);
+                        if (np >= full) continue;
+                        // Under an ROI shift s (RGN, maxshift) a region coefficient has no bit below
+                        // plane s and a background coefficient none at or above it, so a block coded
+                        // exactly down to plane s (OpenJPEG stops there) is complete as far as a decoder
+                        // can tell: its indices are those of the planes decoded, the rest zero.
+                        if (rs && nbp > rs && np == 3 * (nbp - rs) - 2) continue;
+                        snprintf(msg, sizeof msg, "transcode: truncated code-block (tile %u, component %u, resolution %u, band %s, "
+                                 "block %u: %u of %u passes)", TPt.tile, c, r, kBandName[R.bands[bi].orient & 3], lb, np, full);
+                        throw GkError(msg);
+                    }
+                }
+        }
+}
+
 // The decode proper of the tile parts in Hd.parts, whose coding is Hd's and ctx->plan's, into
 // out: packet headers (T2), code-blocks (T1), inverse DWT and MCT, egress.  rq.win is the
 // rectangle written (null: the tile parts' own) and (fx, fy) the image-relative origin of out's
 // planes: the window's, and for a tile pass the whole call's.
+// xc (a transcode): every tile of the image; the T1 decoders write quantisation indices and the
+// call returns after them (out is not written).
 static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, const DecReq& rq, uint32_t fx, uint32_t fy,
-                        HostClock::time_point h0) {
+                        HostClock::time_point h0, Xcode* xc = nullptr) {
     hipStream_t st = ctx->st;
     Plan& P = ctx->plan;
     const uint8_t* const cs = S.dev ? S.dev : S.host;
@@ -5675,6 +6011,7 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
         ib = std::min(ib, t % P.ntx); ie = std::max(ie, t % P.ntx + 1);
         jb = std::min(jb, t / P.ntx); je = std::max(je, t / P.ntx + 1);
     }
+    if (xc) { ib = 0; ie = P.ntx; jb = 0; je = P.nty; }   // the planes the encoders read hold the image
     // work planes cover the tile rectangle only (tiles of the rectangle without a tile part
     // decode as zero); the output region is the rectangle, clipped to the window
     const TileG& Tfirst = P.tiles[(size_t)jb * P.ntx + ib];
@@ -5764,17 +6101,6 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
     // ---- T2 (T2Decompress.cpp:216-570), LRCP, per tile part.  Tile parts are independent
     // (own precincts, tag trees and code-blocks), so they are parsed in parallel host threads
     // into tile-local state (index = block - tile's first block).
-    struct Chunk { uint64_t pos; uint32_t b, len, boff; };   // boff: the block's bytes before this chunk
-    struct PartState {
-        std::vector<Chunk> chunks;
-        std::vector<uint8_t> included, numbps;
-        std::vector<uint16_t> npasses;
-        std::vector<uint32_t> numlenbits, len;
-        // BYPASS / TERMALL: per block the byte length of each codeword segment and the passes
-        // of its last segment (T2Decompress::initSegment, T2Decompress.cpp:28-54)
-        std::vector<std::vector<uint32_t>> seglens;
-        std::vector<uint16_t> segp;
-    };
     // BYPASS / TERMALL components: several codeword segments per block (per component with COC)
     auto comp_multiseg = [&](uint32_t c) { return (P.p.c_sty(c) & (GK_STY_LAZY | GK_STY_TERMALL)) != 0; };
     bool multiseg = false;
@@ -5785,141 +6111,7 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
     };
     std::vector<PartState> ps(Hd.parts.size());
     auto t2_part = [&](size_t q, ByteSrc& BS) {
-        const TilePart& TPt = Hd.parts[q];
-        PartState& st2 = ps[q];
-        const std::vector<uint8_t>& need = part_need[q];
-        struct Trees { DecTree incl, imsb; };
-        std::vector<Trees> trees;
-        std::unordered_map<uint32_t, size_t> tidx;   // trees by first_block of each precinct-band
-        const TileG& TG = P.tiles[TPt.tile];
-        const uint32_t tb0 = TG.b0, ntb = TG.b1 - TG.b0;
-        st2.included.assign(ntb, 0); st2.numbps.assign(ntb, 0); st2.npasses.assign(ntb, 0);
-        st2.numlenbits.assign(ntb, 0); st2.len.assign(ntb, 0);
-        if (multiseg) { st2.seglens.assign(ntb, {}); st2.segp.assign(ntb, 0); }
-        st2.chunks.reserve(ntb);
-        size_t tile_end = TPt.end;
-        size_t pos = TPt.data, pk = 0, nextp = 0;
-        ByteSrc HS;   // the tile's packed packet headers (PPM / PPT)
-        HS.host = TPt.hdrs.data(); HS.len = TPt.hdrs.size();
-        size_t hpos = 0;
-        const std::vector<PacketRef> order = packet_order(P, TG, P.p.nlayers, TPt.pocs.empty() ? &P.p.pocs : &TPt.pocs);
-        // layer limit (tcp->numLayersToDecompress): packets of later layers are skipped through
-        // PLT or parsed without their data (T2Decompress::processPacket, T2Decompress.cpp:55-116)
-        const uint32_t maxl = ctx->dec_layers ? std::min(ctx->dec_layers, P.p.nlayers) : P.p.nlayers;
-        for (size_t oi = 0; oi < order.size(); ++oi, ++pk) {
-                        const uint32_t l = order[oi].l, r = order[oi].r, c = order[oi].c, pi = order[oi].pi;
-                        const ResG& R = TG.comps[c].res[r];
-                        const uint32_t rmax = P.p.c_numres(c) - ctx->dec_reduce;   // resolutions decoded
-                        const bool mseg = comp_multiseg(c);
-                        while (pos >= tile_end && nextp < TPt.more.size()) {   // the tile's next tile part
-                            pos = TPt.more[nextp].first; tile_end = TPt.more[nextp].second; ++nextp;
-                        }
-                        if (pos >= tile_end) return;
-                        const bool skip_l = l >= maxl || r >= rmax;
-                        if (skip_l && pk < TPt.plt.size()) { pos += TPt.plt[pk]; continue; }
-                        if (pk < TPt.plt.size()) {   // PLT: a packet with no needed block is skipped unread
-                            bool any = false;
-                            for (uint32_t bi = 0; bi < R.bands.size() && !any; ++bi) {
-                                const PrecG& PG = R.prc[bi][pi];
-                                for (uint32_t k = 0; k < PG.cw * PG.ch && !any; ++k) any = need[PG.first_block + k - tb0];
-                            }
-                            if (!any) { pos += TPt.plt[pk]; continue; }
-                        }
-                        if (P.p.sop_eph & 2) {   // SOP: FF91 0004 Nsop (T2Decompress::readPacketHeader :226-250)
-                            if (tile_end - pos < 6 || BS.be16(pos) != 0xff91) throw GkError("expected SOP marker");
-                            if (BS.be16(pos + 4) != (pk & 0xffff)) throw GkError("SOP marker packet counter mismatch");
-                            pos += 6;
-                        }
-                        // the header from the packed headers (PPM / PPT) when the tile has them, else in
-                        // front of the body (T2Decompress.cpp:255-270)
-                        BitReader br = TPt.packed ? BitReader(HS, hpos, HS.len) : BitReader(BS, pos, tile_end);
-                        std::vector<std::pair<uint32_t, uint32_t>> contrib;
-                        if (br.read(1)) {
-                            for (uint32_t bi = 0; bi < R.bands.size(); ++bi) {
-                                const PrecG& PG = R.prc[bi][pi];
-                                if (!PG.cw || !PG.ch) continue;
-                                auto it = tidx.find(PG.first_block);
-                                if (it == tidx.end()) {
-                                    trees.emplace_back();
-                                    trees.back().incl.build(PG.cw, PG.ch);
-                                    trees.back().imsb.build(PG.cw, PG.ch);
-                                    it = tidx.emplace(PG.first_block, trees.size() - 1).first;
-                                }
-                                Trees& T = trees[it->second];
-                                for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
-                                    const uint32_t b = PG.first_block + k - tb0;
-                                    uint32_t inc;
-                                    if (!st2.included[b]) inc = T.incl.decode(br, k, l + 1) <= l ? 1 : 0;
-                                    else inc = br.read(1);
-                                    if (!inc) continue;
-                                    if (!st2.included[b]) {
-                                        // zero bit-planes: Grok raises the threshold one plane at a time
-                                        // until the leaf is known; a tag tree reads a node's bits only
-                                        // once its parent is known, so one walk with threshold 64 reads
-                                        // exactly the same bits
-                                        const uint32_t v = T.imsb.decode(br, k, 64);
-                                        const uint32_t kmsbs = v < 64 ? v : 64;
-                                        const uint32_t bnb = R.bands[bi].numbps;
-                                        st2.numbps[b] = (uint8_t)(kmsbs > bnb ? 0 : bnb - kmsbs);
-                                        st2.numlenbits[b] = 3;
-                                        st2.included[b] = 1;
-                                    }
-                                    const uint32_t np = br.numpasses();
-                                    st2.numlenbits[b] += br.commacode();
-                                    uint32_t sl = 0;
-                                    if (!mseg) {
-                                        const uint32_t nbits = st2.numlenbits[b] + floorlog2(np);
-                                        if (nbits > 32) throw GkError("corrupt packet header (segment length)");
-                                        sl = br.read((int)nbits);
-                                    } else {
-                                        // one length per segment part; a segment continues across
-                                        // packets until it holds its maximum pass count
-                                        std::vector<uint32_t>& SL = st2.seglens[b];
-                                        for (uint32_t left = np; left;) {
-                                            if (SL.empty() || st2.segp[b] == seg_max(c, (uint32_t)SL.size() - 1)) {
-                                                if (SL.size() >= GK_MAX_PASSES) throw GkError("corrupt packet header (segments)");
-                                                SL.push_back(0); st2.segp[b] = 0;
-                                            }
-                                            const uint32_t n = std::min(seg_max(c, (uint32_t)SL.size() - 1) - st2.segp[b], left);
-                                            const uint32_t nbits = st2.numlenbits[b] + floorlog2(n);
-                                            if (nbits > 32) throw GkError("corrupt packet header (segment length)");
-                                            const uint32_t part = br.read((int)nbits);
-                                            if (!skip_l) SL.back() += part;
-                                            sl += part;
-                                            st2.segp[b] = (uint16_t)(st2.segp[b] + n);
-                                            left -= n;
-                                        }
-                                    }
-                                    if (st2.npasses[b] + np > GK_MAX_PASSES) throw GkError("corrupt packet header (pass count)");
-                                    if (!skip_l) st2.npasses[b] = (uint16_t)(st2.npasses[b] + np);
-                                    contrib.push_back({b, sl});
-                                }
-                            }
-                        }
-                        br.align();
-                        if (TPt.packed) {
-                            hpos = br.off;
-                            if (hpos > HS.len) throw GkError("corrupt packed packet headers");
-                            if (P.p.sop_eph & 4) {   // EPH after the header, in the packed headers
-                                if (HS.len - hpos < 2 || HS.be16(hpos) != 0xff92) throw GkError("expected EPH marker");
-                                hpos += 2;
-                            }
-                        } else {
-                        pos = br.off;
-                        if (P.p.sop_eph & 4) {   // EPH after the header (:469-486)
-                            if (tile_end - pos < 2 || BS.be16(pos) != 0xff92) throw GkError("expected EPH marker");
-                            pos += 2;
-                        }
-                        }
-                        for (auto& ct : contrib) {
-                            const uint32_t n = (uint32_t)std::min<size_t>(ct.second, tile_end > pos ? tile_end - pos : 0);
-                            if (n && need[ct.first] && !skip_l) {
-                                st2.chunks.push_back({pos, ct.first, n, st2.len[ct.first]});
-                                st2.len[ct.first] += n;
-                            }
-                            pos += ct.second;
-                        }
-        }
+        t2_parse_part(P, Hd.parts[q], part_need[q], ctx->dec_layers, ctx->dec_reduce, BS, ps[q]);
     };
     const auto h1 = now();
     if (Hd.parts.size() == 1) {
@@ -5931,6 +6123,8 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
         });
     }
     const auto h2 = now();
+    if (xc)   // (before anything is staged or launched)
+        for (size_t q = 0; q < Hd.parts.size(); ++q) xcode_check_part(P, Hd.parts[q], ps[q]);
     // ---- the decode table: the needed blocks of the rectangle's tiles, compacted, with offsets
     // into this call's planes and staging slots, band quantisation from QCD (decoder semantics)
     // (written straight into the pinned upload buffer: no vector growth, no extra copy)
@@ -6177,7 +6371,7 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
             HIPCHK(hipMemcpyAsync(dsel, hsel, 4 * (size_t)nbr, hipMemcpyHostToDevice, st));
             int* derr = (int*)ctx->derr.get(64);
             HIPCHK(hipMemsetAsync(derr, 0, 64, st));
-            gk_launch_ht_dec(st, src_bytes, dblk, dsel, arena, nbr, derr, cls_wide);
+            gk_launch_ht_dec(st, src_bytes, dblk, dsel, arena, nbr, derr, cls_wide, xc != nullptr);
             launch_check(__LINE__);
             HIPCHK(hipEventRecord(ctx->ev[8], st));
             int herr = 0;
@@ -6195,7 +6389,7 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
                 HIPCHK(hipMemcpyAsync(dsl, hsl, 4 * hseglen.size(), hipMemcpyHostToDevice, st));
             }
             uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(nbx));
-            gk_launch_t1_dec_ms(st, src_bytes, dblk, dsl, arena, nbr, mst, cls_sty);
+            gk_launch_t1_dec_ms(st, src_bytes, dblk, dsl, arena, nbr, mst, cls_sty, xc != nullptr);
             launch_check(__LINE__);
             HIPCHK(hipEventRecord(ctx->ev[8], st));
             if (dsl) HIPCHK(hipStreamSynchronize(st));   // the pinned table is reused
@@ -6349,7 +6543,7 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
             HIPCHK(hipEventRecord(ctx->ev[8], st));
             uint32_t maxnp = 1;
             for (uint32_t q = 0; q < nbr; ++q) maxnp = std::max<uint32_t>(maxnp, blk[q].numbps);
-            gk_launch_t1_recon(st, dblk, dids, dpos, dscr, dwo, arena, nbr, maxnp);
+            gk_launch_t1_recon(st, dblk, dids, dpos, dscr, dwo, arena, nbr, maxnp, xc != nullptr);
         }
     };
     for (size_t k = 0; k < cls_range.size(); ++k) {
@@ -6359,6 +6553,12 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
     }
     launch_check(__LINE__);
     HIPCHK(hipEventRecord(ctx->ev[3], st));
+    if (xc) {   // the indices are in place: the target coder's encoders take over
+        HIPCHK(hipStreamSynchronize(st));
+        xc->t2_parse_ms = ev_ms(ctx, 0, 1); xc->stage_ms = ev_ms(ctx, 1, 2); xc->t1_dec_ms = ev_ms(ctx, 2, 3);
+        ctx->tm.t1_blocks = nbr;
+        return;
+    }
     // ---- inverse DWT; its last level writes the output region through the inverse MCT + DC
     // shift + clamp into the output planes (without decomposition levels a separate pass does)
     // DC shift and clamp per component (its precision and sign: mct::decompress_dc_shift_* per
@@ -6675,6 +6875,158 @@ static void decode_components(gk_ctx* ctx, DecStream& o, const DecDst& dst, cons
         apply_coding(PH);
         run_pass(PH, tw);
     }
+}
+
+// ---------------------------------------------------------------------------
+// Transcode: Part-1 <-> HTJ2K without touching a coefficient
+// ---------------------------------------------------------------------------
+// The stream opened for a transcode (a raw codestream or a JP2 file) with the refusals the main
+// header decides, and what the new header and file keep of the source (X).  Host reads only.
+static void xcode_open(DecStream& o, const DecSrc& src, hipStream_t st, const gk_transcode_params& tp, Xcode& X) {
+    if (tp.target != GK_TRANSCODE_HT && tp.target != GK_TRANSCODE_PART1)
+        throw GkError("transcode: target must be GK_TRANSCODE_HT or GK_TRANSCODE_PART1");
+    X.to_ht = tp.target == GK_TRANSCODE_HT;
+    X.tlm = tp.tlm; X.plt = tp.plt; X.com = tp.com;
+    open_stream(o, src, st, false);
+    ByteSrc& S = o.S;
+    Header& Hd = o.Hd;
+    const Plan& W = Hd.want;
+    if (!W.p.pocs.empty()) throw GkError("transcode: progression order changes (POC) are not supported");
+    if (!W.p.cc.empty()) throw GkError("transcode: a COC that changes a component's coding is not supported");
+    if (W.p.ht() == X.to_ht)
+        throw GkError(X.to_ht ? "transcode: the source is already coded with the target coder (HTJ2K)"
+                              : "transcode: the source is already coded with the target coder (Part-1)");
+    // Rsiz and the COM markers of the main header (SIZ comes first, A.5.1)
+    if (S.be16(2) != 0xff51) throw GkError("corrupt main header (SIZ must follow SOC)");
+    X.rsiz = S.be16(6);
+    for (size_t i = 2; i + 4 <= Hd.first_sot;) {
+        const uint32_t m = S.be16(i), L = S.be16(i + 2);
+        if (m == 0xff64 && L >= 4) {
+            std::string v(L - 4, '\0');
+            for (uint32_t k = 0; k + 4 < L; ++k) v[k] = (char)S.at(i + 6 + k);
+            X.coms.push_back({S.be16(i + 4), std::move(v)});
+        }
+        i += 2 + (size_t)L;
+    }
+    X.qcd_body = Hd.qcd_body; X.qbody = Hd.qbody;
+    X.mct = Hd.cod[4];
+    if (o.jp2) {   // the boxes around the codestream, byte for byte
+        ByteSrc F;
+        F.len = src.len; F.st = st;
+        if (src.on_device) F.dev = src.cs; else F.host = src.cs;
+        const size_t joff = (size_t)((S.dev ? S.dev : S.host) - src.cs), jend = joff + S.len;
+        X.jp2 = true;
+        X.jp2c_xl = !(joff >= 8 && F.be32(joff - 4) == BOX_JP2C);
+        X.jp2c_to_end = !X.jp2c_xl && F.be32(joff - 8) == 0;
+        X.prefix.resize(joff);
+        for (size_t i = 0; i < joff; ++i) X.prefix[i] = F.at(i);
+        X.suffix.resize(src.len - jend);
+        for (size_t i = jend; i < src.len; ++i) X.suffix[i - jend] = F.at(i);
+    }
+}
+// The refusals that need the tile parts (merged) and the bands under the source's quantisation
+static void xcode_check_plan(const Plan& P, const Header& Hd, const Xcode& X) {
+    for (const TilePart& TP : Hd.parts) {
+        if (TP.tile >= P.tiles.size()) throw GkError("corrupt SOT (tile index)");
+        if (!TP.pocs.empty()) throw GkError("transcode: progression order changes (POC) are not supported");
+        TileCoding tc;
+        if (!TP.cmark.empty() && tile_coding(Hd, TP, tc))
+            throw GkError("transcode: a tile-part COD / COC / QCD / QCC / RGN that changes a tile's coding is not supported");
+    }
+    // what the target coder holds: HT blocks sit under k_msbs = numbps - 1 <= 29; the Part-1
+    // encoders keep magnitude << 6 in 32 bits (check_precision)
+    const uint32_t hold = X.to_ht ? 30 : P.p.wide() ? 25 : 26;
+    for (uint32_t c = 0; c < P.nc; ++c)
+        for (uint32_t r = 0; r < P.p.c_numres(c); ++r)
+            for (const BandG& B : P.tiles[0].comps[c].res[r].bands)
+                if (B.numbps > hold) {
+                    char msg[256];
+                    snprintf(msg, sizeof msg, "transcode: %u bit-planes in the %s band (component %u, resolution %u, ROI shift "
+                             "included), the %s coder holds %u", B.numbps, kBandName[B.orient & 3], c, r,
+                             X.to_ht ? "HT" : P.p.wide() ? "wide-block Part-1" : "Part-1", hold);
+                    throw GkError(msg);
+                }
+}
+// The plan's parameters under the target coder: one layer, one tile part per tile, no SOP / EPH
+static Params xcode_target_params(const Params& src, const Xcode& X) {
+    Params p = src;
+    p.cblk_sty = X.to_ht ? GK_STY_HT : 0;
+    p.nlayers = 1; p.sop_eph = 0; p.quality = false; p.tp_div = 0; p.jp2 = false;
+    for (uint32_t l = 0; l < GK_MAX_LAYERS; ++l) { p.rates[l] = 0.0; p.dist[l] = 0.0; }
+    p.tlm = X.tlm != 0; p.plt = X.plt != 0;
+    p.pocs.clear(); p.cc.clear();
+    return p;
+}
+// gk_probe_transcode: every refusal of gk_transcode, on the host
+static void xcode_probe(const uint8_t* cs, size_t len, const gk_transcode_params& tp) {
+    DecStream o;
+    Xcode X;
+    xcode_open(o, DecSrc{cs, len, false}, nullptr, tp, X);
+    Header& Hd = o.Hd;
+    if (Hd.want.nc < 3) Hd.want.p.mct = 0;
+    Plan P = Hd.want;
+    build_plan(P);
+    apply_qcd(P, Hd.qcd);
+    merge_tile_parts(Hd);
+    xcode_check_plan(P, Hd, X);
+    for (uint32_t c = 0; c < P.nc; ++c)   // (plan_header's limit of the Part-1 decoders)
+        if (!P.p.c_ht(c))
+            for (const ResG& R : P.tiles[0].comps[c].res)
+                for (const BandG& B : R.bands)
+                    if (B.numbps > 30) throw GkError("more than 30 band bit-planes (ROI shift included) not supported");
+    for (const TilePart& TP : Hd.parts) {
+        const TileG& T = P.tiles[TP.tile];
+        const std::vector<uint8_t> need(T.b1 - T.b0, 1);
+        PartState st2;
+        t2_parse_part(P, TP, need, 0, 0, o.S, st2);
+        xcode_check_part(P, TP, st2);
+    }
+}
+static size_t xcode_call(gk_ctx* ctx, const DecSrc& src, const gk_transcode_params& tp, uint8_t* out, size_t cap,
+                         int out_on_device, int* rc) {
+    if (ctx->dec_layers) throw GkError("transcode: gk_set_decode_layers is set (a transcode takes every layer)");
+    if (ctx->dec_reduce) throw GkError("transcode: gk_set_decode_reduce is set (a transcode takes every resolution)");
+    hipStream_t st = ctx->st;
+    DecStream o;
+    Xcode X;
+    xcode_open(o, src, st, tp, X);
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    ByteSrc& S = o.S;
+    Header& Hd = o.Hd;
+    plan_header(ctx, Hd);
+    Plan& P = ctx->plan;
+    if (S.dev) {
+        try {
+            read_tile_part_headers(ctx, S, Hd);
+        } catch (const TlmMismatch&) {
+            Hd.parts.clear();
+            walk_sot_chain(S, Hd);
+        }
+    }
+    merge_tile_parts(Hd);
+    xcode_check_plan(P, Hd, X);
+    // the source coder's T1 decoders leave the indices in the work planes
+    decode_core(ctx, S, Hd, DecDst{nullptr, nullptr, nullptr, 0, 4, true}, DecReq{nullptr, false}, 0, 0, o.t0, &X);
+    // the target coder's T1 encoders and T2 on the same plan (its bands keep the source's
+    // quantisation, band_qcd, as after a decode), under the target's parameters for this call
+    struct Restore {
+        Plan& P; Params keep;
+        ~Restore() { P.p = std::move(keep); }
+    } restore{P, P.p};
+    P.p = xcode_target_params(restore.keep, X);
+    gk_image_info info{};
+    size_t n = encode_impl(ctx, &info, nullptr, nullptr, 1, nullptr, out, cap, out_on_device, rc, 0, 0, true, nullptr, false,
+                           nullptr, nullptr, &X);
+    // the call's times: T1 is the source coder's decode (t1_cm_ms) and the target coder's encode
+    // (t1_coder_ms); T2 is the packet-header parse and the packet write; no DWT, no sample stage
+    gk_timings& tm = ctx->tm;
+    const float enc_t1 = tm.t1_ms;
+    tm.t1_cm_ms = X.t1_dec_ms; tm.t1_coder_ms = enc_t1; tm.t1_ms = X.t1_dec_ms + enc_t1;
+    tm.t2_ms += X.t2_parse_ms; tm.assemble_ms += X.stage_ms;
+    tm.total_ms += X.t2_parse_ms + X.stage_ms + X.t1_dec_ms;
+    tm.mct_ms = 0.f; tm.dwt_ms = 0.f; tm.dwt_launches = 0; tm.dwt_bytes = 0;
+    return n;
 }
 
 // ---------------------------------------------------------------------------
@@ -7210,6 +7562,43 @@ static int decode_entry(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const
 int gk_decode(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, void* const* comps,
               const uint32_t* strides, uint32_t sample_bytes, int out_on_device) {
     return decode_entry(ctx, DecSrc{cs, len, cs_on_device != 0}, DecDst{comps, strides, nullptr, 0, sample_bytes, out_on_device != 0}, nullptr);
+}
+
+void gk_set_default_transcode(gk_transcode_params* p) {
+    memset(p, 0, sizeof(*p));
+    p->target = GK_TRANSCODE_HT;
+    p->com = 1;
+}
+int gk_transcode(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_transcode_params* p, uint8_t* out,
+                 size_t cap, int out_on_device, size_t* out_len) {
+    if (!ctx || !cs || !out) return -1;
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
+        gk_transcode_params dp;
+        gk_set_default_transcode(&dp);
+        int rc = 0;
+        const size_t n = xcode_call(ctx, DecSrc{cs, len, cs_on_device != 0}, p ? *p : dp, out, cap, out_on_device, &rc);
+        if (out_len) *out_len = n;
+        if (rc == -2) ctx->err = "output capacity too small";
+        return rc;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+int gk_probe_transcode(const uint8_t* cs, size_t len, const gk_transcode_params* p, char* msg, size_t msg_cap) {
+    if (!cs) return -1;
+    try {
+        gk_transcode_params dp;
+        gk_set_default_transcode(&dp);
+        xcode_probe(cs, len, p ? *p : dp);
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
+        return -1;
+    }
 }
 
 int gk_set_subsampling(gk_ctx* ctx, uint32_t numcomps, const uint32_t* dx, const uint32_t* dy) {

@@ -55,7 +55,9 @@ __device__ __forceinline__ void uvlc_code(int u, uint32_t& pre, int& plen, uint3
 // =============================================================================
 // Encoder
 // =============================================================================
-template <int HT_WG, int HT_LINE>
+// INDEX (transcode): the coefficients are signed quantisation indices (ROI shift included), coded
+// as they are: no quantisation, no ROI up-shift.
+template <int HT_WG, int HT_LINE, bool INDEX = false>
 __global__ __launch_bounds__(HT_WG) void k_ht_enc(const int32_t* __restrict__ coef, const GkBlock* __restrict__ blocks,
                                                   uint8_t* __restrict__ bytes, uint8_t* __restrict__ mel_scratch,
                                                   uint32_t mel_cap, uint32_t* __restrict__ info, uint32_t nblocks,
@@ -204,6 +206,7 @@ __global__ __launch_bounds__(HT_WG) void k_ht_enc(const int32_t* __restrict__ co
     };
     auto ld = [&](uint32_t x, uint32_t y) -> int32_t {
         const int32_t raw = s_in[y & 1][x & 7][tid];
+        if constexpr (INDEX) return raw;
         const int32_t v = irrev ? (int32_t)(__int_as_float(raw) * inv_step) : raw;
         return v < 0 ? -(int32_t)((uint32_t)-v << rshift) : (int32_t)((uint32_t)v << rshift);
     };
@@ -380,7 +383,9 @@ __global__ __launch_bounds__(HT_WG) void k_ht_enc(const int32_t* __restrict__ co
 // =============================================================================
 // Decoder
 // =============================================================================
-template <int HT_WG, int HT_LINE>
+// INDEX (transcode): the signed quantisation indices as decoded (int32): no ROI down-shift, no
+// dequantisation.
+template <int HT_WG, int HT_LINE, bool INDEX = false>
 __global__ __launch_bounds__(HT_WG) void k_ht_dec(const uint8_t* __restrict__ bytes, const GkBlock* __restrict__ blocks,
                                                   const uint32_t* __restrict__ ids, int32_t* __restrict__ coef,
                                                   uint32_t nblocks, int* __restrict__ err, uint32_t nl) {
@@ -535,11 +540,11 @@ __global__ __launch_bounds__(HT_WG) void k_ht_dec(const uint8_t* __restrict__ by
                 else v = (m ? ms_get(m) : 0u) | ((uint32_t)((e1 >> n) & 1) << m);
                 const uint32_t mu = (v >> 1) + 1;
                 e[n] = 32 - __clz(2 * mu - 1);
-                const uint32_t mo = (rshift && mu >= (1u << rshift)) ? mu >> rshift : mu;
+                const uint32_t mo = (!INDEX && rshift && mu >= (1u << rshift)) ? mu >> rshift : mu;
                 val = (v & 1) ? -(int32_t)mo : (int32_t)mo;
             }
             uint32_t bits = (uint32_t)val;
-            if (irrev) {
+            if (!INDEX && irrev) {
                 const uint32_t mag = ((uint32_t)(val < 0 ? -val : val) << pbit) & 0x7fffffffu;
                 const float f = (float)mag * G.step;
                 bits = __float_as_uint(val < 0 ? -f : f);
@@ -653,9 +658,21 @@ static uint32_t ht_lanes(const char* var) {
     return (uint32_t)(n < 1 ? 1 : (n > 64 ? 64 : n));
 }
 void gk_launch_ht_enc(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, uint8_t* mel_scratch,
-                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide) {
+                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide, bool index) {
     if (!nblocks) return;
     static const uint32_t nl = ht_lanes("GK_HT_ENC_LANES");
+    if (index) {
+        if (wide) {
+            const uint32_t per = (HT_WG_WIDE / 64) * nl;
+            hipLaunchKernelGGL((k_ht_enc<HT_WG_WIDE, HT_LINE_WIDE, true>), dim3((nblocks + per - 1) / per), dim3(HT_WG_WIDE), 0,
+                               st, coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl);
+        } else {
+            const uint32_t per = (HT_WG_STD / 64) * nl;
+            hipLaunchKernelGGL((k_ht_enc<HT_WG_STD, HT_LINE_STD, true>), dim3((nblocks + per - 1) / per), dim3(HT_WG_STD), 0, st,
+                               coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl);
+        }
+        return;
+    }
     if (wide) {
         const uint32_t per = (HT_WG_WIDE / 64) * nl;
         hipLaunchKernelGGL((k_ht_enc<HT_WG_WIDE, HT_LINE_WIDE>), dim3((nblocks + per - 1) / per), dim3(HT_WG_WIDE), 0, st,
@@ -668,9 +685,21 @@ void gk_launch_ht_enc(hipStream_t st, const int32_t* coef, const GkBlock* blocks
 }
 
 void gk_launch_ht_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* ids, int32_t* coef,
-                      uint32_t nblocks, int* err, bool wide) {
+                      uint32_t nblocks, int* err, bool wide, bool index) {
     if (!nblocks) return;
     static const uint32_t nl = ht_lanes("GK_HT_DEC_LANES");
+    if (index) {
+        if (wide) {
+            const uint32_t per = (HT_WG_WIDE / 64) * nl;
+            hipLaunchKernelGGL((k_ht_dec<HT_WG_WIDE, HT_LINE_WIDE, true>), dim3((nblocks + per - 1) / per), dim3(HT_WG_WIDE), 0,
+                               st, bytes, blocks, ids, coef, nblocks, err, nl);
+        } else {
+            const uint32_t per = (HT_WG_STD / 64) * nl;
+            hipLaunchKernelGGL((k_ht_dec<HT_WG_STD, HT_LINE_STD, true>), dim3((nblocks + per - 1) / per), dim3(HT_WG_STD), 0, st,
+                               bytes, blocks, ids, coef, nblocks, err, nl);
+        }
+        return;
+    }
     if (wide) {
         const uint32_t per = (HT_WG_WIDE / 64) * nl;
         hipLaunchKernelGGL((k_ht_dec<HT_WG_WIDE, HT_LINE_WIDE>), dim3((nblocks + per - 1) / per), dim3(HT_WG_WIDE), 0, st,

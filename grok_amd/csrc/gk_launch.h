@@ -42,7 +42,8 @@ void gk_launch_gather(hipStream_t st, const uint8_t* src, uint8_t* dst, const ui
 // [base, base + count) without one; count = ~0u: all nblocks
 void gk_launch_t1_cm(hipStream_t st, const int32_t* coef, const GkBlock* blocks, const uint64_t* sym_off, uint8_t* sym,
                      uint32_t* pass_end, uint32_t* cm_info, uint32_t nblocks, int* err, const int16_t* nmse_tab,
-                     int32_t* pass_nmse, const uint32_t* order = nullptr, uint32_t base = 0, uint32_t count = 0xffffffffu);
+                     int32_t* pass_nmse, const uint32_t* order = nullptr, uint32_t base = 0, uint32_t count = 0xffffffffu,
+                     bool index = false);
 void gk_launch_t1_mq(hipStream_t st, const uint8_t* sym, const uint64_t* sym_off, const uint32_t* pass_end,
                      const uint32_t* cm_info, const GkBlock* blocks, uint8_t* bytes, GkPass* passes, uint32_t* info,
                      uint32_t nblocks, int* err, const int32_t* pass_nmse, uint32_t* pass_counter,
@@ -63,7 +64,9 @@ void gk_launch_t1_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* block
                       uint64_t* scratch, const uint64_t* wave_off, uint32_t nblocks, uint32_t nsolo);
 void gk_launch_t1_recon(hipStream_t st, const GkBlock* blocks, const uint32_t* ids, const uint32_t* pos,
                         const uint64_t* scratch, const uint64_t* wave_off, int32_t* coef, uint32_t nblocks,
-                        uint32_t maxnp);   // maxnp: the blocks' largest numbps
+                        uint32_t maxnp, bool index = false);   // maxnp: the blocks' largest numbps
+// index (transcode; the decoders' and encoders' last argument): the coefficient planes hold signed
+// quantisation indices (int32, ROI shift included) instead of dequantised / unquantised samples
 // one DWT level of any parity, either filter, one line per thread (gk_dwt_any.hip): forward
 // reads the input region of `in` and leaves the Mallat level in `out`, inverse the reverse
 void gk_launch_dwt_any(hipStream_t st, bool irrev, bool forward, int32_t* in, int32_t* out, uint32_t stride, uint32_t w,
@@ -72,9 +75,9 @@ void gk_launch_dwt_any(hipStream_t st, bool irrev, bool forward, int32_t* in, in
 // code-blocks with mode switches (gk_t1ms.hip)
 void gk_launch_t1_enc_ms(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, GkPass* passes,
                          uint32_t* info, uint32_t nblocks, int* err, const int16_t* nmse_tab, uint32_t* pass_counter,
-                         uint8_t* state, uint32_t sty);
+                         uint8_t* state, uint32_t sty, bool index = false);
 void gk_launch_t1_dec_ms(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* seglen, int32_t* coef,
-                         uint32_t nblocks, uint8_t* state, uint32_t sty);
+                         uint32_t nblocks, uint8_t* state, uint32_t sty, bool index = false);
 size_t gk_t1ms_state_bytes(uint32_t nblocks);
 void gk_launch_dc_ict_fwd(hipStream_t st, int stype, const void* r, const void* g, const void* b, uint32_t sin, float* y,
                           float* u, float* v, uint32_t sout, uint32_t w, uint32_t h, int32_t shift);
@@ -97,9 +100,9 @@ void gk_launch_dwt97_inv_l1(hipStream_t st, int stype, int nc, const float* src,
                             int32_t mn, int32_t mx);
 // HTJ2K cleanup-pass block coder (gk_ht.hip); wide: some block is wider than 64 samples
 void gk_launch_ht_enc(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, uint8_t* mel_scratch,
-                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide = false);
+                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide = false, bool index = false);
 void gk_launch_ht_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* ids, int32_t* coef,
-                      uint32_t nblocks, int* err, bool wide = false);
+                      uint32_t nblocks, int* err, bool wide = false, bool index = false);
 // JP2 palette expansion (gk_colour.hip).  One output channel: palette column `col` of the launch's
 // index plane, or (direct) a copy of the component plane `src`.
 struct GkPalChan {

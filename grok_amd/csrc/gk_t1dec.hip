@@ -1058,6 +1058,9 @@ __global__ __launch_bounds__(64 * W) void k_t1_dec2(const uint8_t* __restrict__ 
 // LDS broadcasts instead of one uniform global load per (row, plane).
 // The staging holds the launch's largest plane count (dynamic LDS: 16 KB for 32 planes capped
 // a CU at 9 such waves; C2's 11 planes take 6 KB).
+// INDEX (transcode): the signed quantisation index +-M of a block whose every pass was decoded,
+// as decoded: no half bit, no ROI down-shift, no dequantisation.
+template <bool INDEX>
 __global__ __launch_bounds__(64) void k_t1_recon(const GkBlock* __restrict__ blocks, const uint32_t* __restrict__ ids,
                                                  const uint32_t* __restrict__ pos,
                                                  const uint64_t* __restrict__ scratch,
@@ -1103,7 +1106,9 @@ __global__ __launch_bounds__(64) void k_t1_recon(const GkBlock* __restrict__ blo
         if (any) {
             uint32_t M = 0;
             for (int i = 0; i < np; ++i) M |= __builtin_amdgcn_ubfe(Lh[2 * (i * 64 + y)], xb, 1) << ((int)numbps - 1 - i);
-            if (M) {
+            if constexpr (INDEX) {
+                if (M) v = ((Ls[y] >> x) & 1) ? -(int32_t)M : (int32_t)M;
+            } else if (M) {
                 int qq = (t == 0 && (M >> (bpl + 1)) != 0) ? bpl + 1 : bpl;
                 int32_t mag = (int32_t)(((M >> qq) << 1 | 1) << qq);
                 bool ng = (Ls[y] >> x) & 1;
@@ -1111,6 +1116,7 @@ __global__ __launch_bounds__(64) void k_t1_recon(const GkBlock* __restrict__ blo
             }
         }
         size_t o = B.band_off + (size_t)y * B.stride + x;
+        if constexpr (INDEX) { coef[o] = v; continue; }
         if (rs) {   // RoiShiftFilter / RoiScaleFilter (PostDecompressFilters.h:7-72)
             const int32_t m = v < 0 ? -v : v;
             if (m >= (1 << rs)) v = v < 0 ? -(m >> rs) : (m >> rs);
@@ -1240,9 +1246,15 @@ void gk_launch_t1_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* block
     }
 }
 void gk_launch_t1_recon(hipStream_t st, const GkBlock* blocks, const uint32_t* ids, const uint32_t* pos,
-                        const uint64_t* scratch, const uint64_t* wave_off, int32_t* coef, uint32_t nblocks, uint32_t maxnp) {
+                        const uint64_t* scratch, const uint64_t* wave_off, int32_t* coef, uint32_t nblocks, uint32_t maxnp,
+                        bool index) {
     if (!nblocks) return;
     const uint32_t npmax = maxnp < 1 ? 1 : (maxnp > 32 ? 32 : maxnp);
-    hipLaunchKernelGGL(k_t1_recon, dim3(nblocks), dim3(64), (size_t)(npmax + 1) * 64 * 8, st, blocks, ids, pos, scratch,
+    if (index) {
+        hipLaunchKernelGGL(k_t1_recon<true>, dim3(nblocks), dim3(64), (size_t)(npmax + 1) * 64 * 8, st, blocks, ids, pos,
+                           scratch, wave_off, coef, nblocks, npmax);
+        return;
+    }
+    hipLaunchKernelGGL(k_t1_recon<false>, dim3(nblocks), dim3(64), (size_t)(npmax + 1) * 64 * 8, st, blocks, ids, pos, scratch,
                        wave_off, coef, nblocks, npmax);
 }

@@ -102,7 +102,9 @@ __device__ __forceinline__ int32_t wave_sum(int32_t v) {
 
 // RC: also accumulate Grok's per-pass nmsedec (T1.cpp:483-764 getnmsedec_sig/_ref)
 // into pass_nmse[b * GK_MAX_PASSES + pass].
-template <bool RC>
+// INDEX (transcode; never with RC): the coefficients are signed quantisation indices (ROI shift
+// included), taken as the magnitudes: no quantisation, no ROI up-shift.
+template <bool RC, bool INDEX = false>
 __global__ __launch_bounds__(64) void k_t1_cm(const int32_t* __restrict__ coef, const GkBlock* __restrict__ blocks,
                                               const uint64_t* __restrict__ sym_off, uint8_t* __restrict__ sym,
                                               uint32_t* __restrict__ pass_end, uint32_t* __restrict__ cm_info,
@@ -133,14 +135,15 @@ __global__ __launch_bounds__(64) void k_t1_cm(const int32_t* __restrict__ coef, 
         uint32_t a = 0;
         if (y < (int)h && lane < (int)w) {
             raw = coef[B.band_off + (size_t)y * B.stride + lane];
-            if (irrev) a = (uint32_t)fabsf(rintf((__int_as_float(raw) / B.step) * 64.0f));
+            if constexpr (INDEX) a = (uint32_t)(raw < 0 ? -raw : raw) * 64u;
+            else if (irrev) a = (uint32_t)fabsf(rintf((__int_as_float(raw) / B.step) * 64.0f));
             else a = (uint32_t)(raw < 0 ? -raw : raw) * 64u;
         }
         m[y] = a;
         mx = a > mx ? a : mx;
         negcol |= (uint64_t)(raw < 0) << y;
     }
-    if (const uint32_t rs = B.flags >> 3) {   // ROI maxshift (the component is the region): index integer part up
+    if (const uint32_t rs = INDEX ? 0u : B.flags >> 3) {   // ROI maxshift (the component is the region): index integer part up
         mx = 0;
 #pragma unroll
         for (int y = 0; y < 64; ++y) {
@@ -835,11 +838,14 @@ __global__ __launch_bounds__(256) void k_t1_mq(const uint8_t* __restrict__ sym, 
 #include "gk_launch.h"
 void gk_launch_t1_cm(hipStream_t st, const int32_t* coef, const GkBlock* blocks, const uint64_t* sym_off, uint8_t* sym,
                      uint32_t* pass_end, uint32_t* cm_info, uint32_t nblocks, int* err, const int16_t* nmse_tab,
-                     int32_t* pass_nmse, const uint32_t* order, uint32_t base, uint32_t count) {
+                     int32_t* pass_nmse, const uint32_t* order, uint32_t base, uint32_t count, bool index) {
     if (!nblocks) return;
     if (count == 0xffffffffu) count = nblocks;
     if (!count) return;
-    if (pass_nmse)
+    if (index)
+        hipLaunchKernelGGL((k_t1_cm<false, true>), dim3(count), dim3(64), 0, st, coef, blocks, sym_off, sym, pass_end,
+                           cm_info, nblocks, err, nmse_tab, nullptr, order, base, count);
+    else if (pass_nmse)
         hipLaunchKernelGGL(k_t1_cm<true>, dim3(count), dim3(64), 0, st, coef, blocks, sym_off, sym, pass_end, cm_info,
                            nblocks, err, nmse_tab, pass_nmse, order, base, count);
     else

@@ -162,6 +162,9 @@ __device__ __forceinline__ bool ms_term_pass(uint32_t sty, int numbps, int bpno,
 }
 
 // Lane = code-block.  state: MS_STATE_BYTES per block slot of this launch (lane index).
+// INDEX (transcode): the coefficients are signed quantisation indices (ROI shift included), taken
+// as the magnitudes: no quantisation, no ROI up-shift.
+template <bool INDEX>
 __global__ __launch_bounds__(64) void k_t1_enc_ms(const int32_t* __restrict__ coef, const GkBlock* __restrict__ blocks,
                                                   uint8_t* __restrict__ bytes, GkPass* __restrict__ passes,
                                                   uint32_t* __restrict__ info, uint32_t nblocks, int* err,
@@ -174,6 +177,7 @@ __global__ __launch_bounds__(64) void k_t1_enc_ms(const int32_t* __restrict__ co
     const bool irrev = G.flags & 1, rc = (G.flags & 2) != 0;
     auto smr = [&](int x, int y) -> int32_t {   // T1Part1::preCompress (T1Part1.cpp:36-87)
         const int32_t raw = coef[G.band_off + (size_t)y * G.stride + x];
+        if constexpr (INDEX) return raw * 64;
         const int32_t v = irrev ? (int32_t)rintf((__int_as_float(raw) / G.step) * 64.0f) : raw * 64;
         if (!(G.flags >> 3)) return v;
         // ROI maxshift (the component is the region): the index's integer part scaled up
@@ -403,6 +407,9 @@ __device__ __forceinline__ uint32_t ms_seg_maxpasses(uint32_t sty, uint32_t s) {
 // Block b's segments: seglen[G.data_cap ...] (data_cap carries the segment-table offset on
 // decode).  Output: dequantised samples in the band window (ShiftFilter / ScaleFilter,
 // PostDecompressFilters.h:31-177), the decoder's 2x values staged in place first.
+// INDEX (transcode): the signed quantisation index of a block whose every pass was decoded (the
+// 2x value halved): no ROI down-shift, no dequantisation.
+template <bool INDEX>
 __global__ __launch_bounds__(64) void k_t1_dec_ms(const uint8_t* __restrict__ bytes, const GkBlock* __restrict__ blocks,
                                                   const uint32_t* __restrict__ seglen, int32_t* __restrict__ coef,
                                                   uint32_t nblocks, uint8_t* __restrict__ state, uint32_t sty) {
@@ -514,6 +521,14 @@ __global__ __launch_bounds__(64) void k_t1_dec_ms(const uint8_t* __restrict__ by
         for (int x = 0; x < w; ++x) {
             const size_t i = (size_t)y * os + x;
             int32_t v = o[i];
+            if constexpr (INDEX) {
+                // planes left undecoded (0, or the ROI shift's: the host admits no other count): the
+                // 2x value carries its half bit at bit k
+                const int k = (numbps && npasses) ? (int)numbps - (int)(min(npasses, 3 * numbps - 2) + 2) / 3 : 0;
+                const int32_t m = (int32_t)(((uint32_t)(v < 0 ? -v : v) >> (k + 1)) << k);
+                o[i] = v < 0 ? -m : m;
+                continue;
+            }
             if (rs) {
                 const int32_t m = v < 0 ? -v : v;
                 if (m >= (1 << rs)) v = v < 0 ? -(m >> rs) : (m >> rs);
@@ -526,15 +541,25 @@ __global__ __launch_bounds__(64) void k_t1_dec_ms(const uint8_t* __restrict__ by
 #include "gk_launch.h"
 void gk_launch_t1_enc_ms(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, GkPass* passes,
                          uint32_t* info, uint32_t nblocks, int* err, const int16_t* nmse_tab, uint32_t* pass_counter,
-                         uint8_t* state, uint32_t sty) {
+                         uint8_t* state, uint32_t sty, bool index) {
     if (!nblocks) return;
-    hipLaunchKernelGGL(k_t1_enc_ms, dim3((nblocks + 63) / 64), dim3(64), 0, st, coef, blocks, bytes, passes, info, nblocks,
+    if (index) {
+        hipLaunchKernelGGL(k_t1_enc_ms<true>, dim3((nblocks + 63) / 64), dim3(64), 0, st, coef, blocks, bytes, passes, info,
+                           nblocks, err, nmse_tab, pass_counter, state, sty);
+        return;
+    }
+    hipLaunchKernelGGL(k_t1_enc_ms<false>, dim3((nblocks + 63) / 64), dim3(64), 0, st, coef, blocks, bytes, passes, info, nblocks,
                        err, nmse_tab, pass_counter, state, sty);
 }
 void gk_launch_t1_dec_ms(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* seglen, int32_t* coef,
-                         uint32_t nblocks, uint8_t* state, uint32_t sty) {
+                         uint32_t nblocks, uint8_t* state, uint32_t sty, bool index) {
     if (!nblocks) return;
-    hipLaunchKernelGGL(k_t1_dec_ms, dim3((nblocks + 63) / 64), dim3(64), 0, st, bytes, blocks, seglen, coef, nblocks, state,
+    if (index) {
+        hipLaunchKernelGGL(k_t1_dec_ms<true>, dim3((nblocks + 63) / 64), dim3(64), 0, st, bytes, blocks, seglen, coef, nblocks,
+                           state, sty);
+        return;
+    }
+    hipLaunchKernelGGL(k_t1_dec_ms<false>, dim3((nblocks + 63) / 64), dim3(64), 0, st, bytes, blocks, seglen, coef, nblocks, state,
                        sty);
 }
 size_t gk_t1ms_state_bytes(uint32_t nblocks) { return (size_t)nblocks * MS_STATE_BYTES; }

@@ -551,7 +551,48 @@ int gk_encode_blocks(gk_ctx* ctx, const gk_image_info* info, const void* const* 
 int gk_encode_blocks_get(gk_ctx* ctx, gk_band_result* bands, gk_block_result* blocks, uint8_t* data,
                          gk_pass_result* passes);
 
-/* Stage timings of the last gk_encode / gk_decode. */
+/* Transcode between the two block coders, Part-1 (EBCOT / MQ) and HTJ2K, without touching a
+ * coefficient: the source coder's T1 decoders leave signed quantisation indices in the work
+ * planes and the target coder's T1 encoders read them there.  No DWT, MCT or sample stage runs,
+ * so a 9/7 stream takes no second lossy generation.  (Grok 9.2.0 has no counterpart: its
+ * CodeStreamTranscode / FileFormatTranscode classes are empty.)
+ * cs: a raw codestream or a JP2 file (device memory if cs_on_device).  Of a JP2 file every box
+ * outside jp2c is copied byte for byte and jp2c gets the new codestream and its length (the XL
+ * form stays).  The new codestream keeps SIZ, the COD's levels, code-block size, precincts,
+ * progression order, MCT flag and transform, QCD / QCC verbatim, RGN and (com) the COM markers.
+ * It changes the code-block style (0x40 for HT, 0 for Part-1), Rsiz bit 14 and the CAP marker
+ * (MAGBp from the largest band bit-plane count, ROI shift included; for a 9/7 stream the count
+ * the engine's HT encoder writes for those bands); it has one layer, one tile
+ * part per tile, no SOP / EPH, packet headers in the packets (PPM / PPT unpacked) and TLM / PLT as
+ * the params say.  Blocks the Part-1 coder finds all zero are written as not included; the HT
+ * coder writes every block, as on encode.
+ * Refused, each by name and before any kernel runs (gk_probe_transcode gives the same answer on
+ * the host): a truncated code-block of a Part-1 source (an included block with fewer than
+ * 3 * numbps - 2 passes: streams cut by rate control or quality layers); an HT block with
+ * SigProp / MagRef passes; a band of more bit-planes than the target coder holds (HT 30, Part-1
+ * 26, Part-1 with a code-block side above 64: 25); POC; a COC, or a tile-part COD / COC / QCD /
+ * QCC / RGN, that changes a component's or tile's coding; Part-2 markers; a source already in the
+ * target coder; a non-zero gk_set_decode_layers or gk_set_decode_reduce (display, precision and
+ * colour settings are output settings and are ignored).
+ * gk_transcode returns 0, -2 with *out_len = the size needed, or -1 (gk_last_error).  Afterwards
+ * gk_get_timings has t1_cm_ms = the source coder's decode kernels, t1_coder_ms = the target
+ * coder's encode kernels, t1_ms their sum, t2_ms the packet parse and write, and 0 in the DWT and
+ * MCT fields. */
+#define GK_TRANSCODE_HT 1u
+#define GK_TRANSCODE_PART1 2u
+typedef struct gk_transcode_params {
+    uint32_t target;          /* GK_TRANSCODE_HT | GK_TRANSCODE_PART1 */
+    uint32_t tlm, plt, com;   /* write TLM / PLT markers (as gk_cparameters), keep the source's COM markers */
+} gk_transcode_params;
+/* target HT, no TLM / PLT (Grok's defaults), COM kept */
+void gk_set_default_transcode(gk_transcode_params* p);
+int gk_transcode(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_transcode_params* p,
+                 uint8_t* out, size_t cap, int out_on_device, size_t* out_len);
+/* 0 if the host bytes would transcode, -1 with the refusal in msg.  Needs no device: it parses
+ * the headers and every packet header on the host. */
+int gk_probe_transcode(const uint8_t* cs, size_t len, const gk_transcode_params* p, char* msg, size_t msg_cap);
+
+/* Stage timings of the last gk_encode / gk_decode / gk_transcode. */
 int gk_get_timings(gk_ctx* ctx, gk_timings* t);
 /* Last error message for this context (grk_set_error_handler equivalent). */
 const char* gk_last_error(gk_ctx* ctx);
