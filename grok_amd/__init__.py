@@ -30,7 +30,7 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels", "gk_encode_pixels",
            "gk_set_encode_colour", "gk_jp2_boxes", "gk_header_cielab", "gk_probe_cielab",
            "gk_set_encode_convert", "gk_probe_encode_convert", "gk_set_default_transcode", "gk_transcode",
-           "gk_probe_transcode")
+           "gk_probe_transcode", "gk_set_encode_roi", "gk_probe_encode_roi", "gk_roi_band_mask")
 GK_TRANSCODE_HT, GK_TRANSCODE_PART1 = 1, 2   # gk_transcode_params::target
 GK_MAX_CHANNELS = 256
 GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB, GK_DISPLAY_ICC = 1, 2, 4, 8   # gk_set_decode_display flags
@@ -133,7 +133,8 @@ class Timings(ctypes.Structure):
                [("dwt_launches", ctypes.c_uint32), ("t1_blocks", ctypes.c_uint32)] + \
                [(n, ctypes.c_uint64) for n in ("dwt_bytes", "cs_bytes", "t1_bytes", "t1_steps_max", "t1_steps_total",
                                                "t1_symbols", "t1_solo_blocks", "t1_solo_decisions",
-                                               "t1_solo_decisions_max", "t1_shared")]
+                                               "t1_solo_decisions_max", "t1_shared")] + \
+               [("roi_ms", ctypes.c_float)]
 
 
 class ColourInfo(ctypes.Structure):
@@ -169,6 +170,90 @@ class EncodeColour(ctypes.Structure):
 class EncodeConvert(ctypes.Structure):
     """gk_encode_convert"""
     _fields_ = [("space", ctypes.c_uint32), ("chroma_dx", ctypes.c_uint32), ("chroma_dy", ctypes.c_uint32)]
+
+
+class Rect(ctypes.Structure):
+    """gk_rect: half-open, in samples from the image's top-left sample"""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("x0", "y0", "x1", "y1")]
+
+
+class EncodeRoi(ctypes.Structure):
+    """gk_encode_roi"""
+    _fields_ = [("shift", ctypes.c_uint32), ("num_comps", ctypes.c_uint32), ("comps", ctypes.POINTER(ctypes.c_uint32)),
+                ("num_rects", ctypes.c_uint32), ("rects", ctypes.POINTER(Rect)), ("mask", ctypes.c_void_p),
+                ("mask_w", ctypes.c_uint32), ("mask_h", ctypes.c_uint32), ("mask_row_bytes", ctypes.c_size_t),
+                ("mask_on_device", ctypes.c_int)]
+
+
+def _encode_roi(rects, mask, shift, components):
+    """gk_encode_roi of the Python arguments: rects [(x0, y0, x1, y1)] half-open in image samples, mask
+    an (H, W) array of 8-bit elements (numpy, or a torch cuda tensor: non-zero = region), shift 0..31
+    (0: the smallest legal shift), components a list of indices (None: all).  None when there is
+    neither a rectangle nor a mask."""
+    if not rects and mask is None:
+        return None
+    if not 0 <= int(shift) < 1 << 32:
+        raise ValueError("roi: shift is an unsigned 32-bit value")
+    r = EncodeRoi()
+    r.shift = int(shift)
+    keep = []
+    if components is not None and len(components):
+        if any(not 0 <= int(c) < 1 << 32 for c in components):
+            raise ValueError("roi: component indices are unsigned 32-bit values")
+        ca = (ctypes.c_uint32 * len(components))(*[int(c) for c in components])
+        keep.append(ca)
+        r.num_comps, r.comps = len(components), ca
+    if rects:
+        for q in rects:
+            if len(q) != 4 or any(not 0 <= int(v) < 1 << 32 for v in q):
+                raise ValueError("roi: a rectangle is (x0, y0, x1, y1), unsigned 32-bit values")
+        ra = (Rect * len(rects))(*[Rect(*[int(v) for v in q]) for q in rects])
+        keep.append(ra)
+        r.num_rects, r.rects = len(rects), ra
+    if mask is not None:
+        if _is_torch_cuda(mask):
+            if mask.dim() != 2 or mask.element_size() != 1 or (mask.shape[1] > 1 and mask.stride(1) != 1):
+                raise ValueError("roi: the mask is an (H, W) tensor of 8-bit elements with unit column stride")
+            r.mask, r.mask_on_device = mask.data_ptr(), 1
+            r.mask_h, r.mask_w = int(mask.shape[0]), int(mask.shape[1])
+            r.mask_row_bytes = int(mask.stride(0)) if mask.shape[0] > 1 else r.mask_w
+        else:
+            m = np.asarray(mask)
+            if m.ndim != 2:
+                raise ValueError("roi: the mask is an (H, W) array")
+            m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+            r.mask, r.mask_on_device = m.ctypes.data, 0
+            r.mask_h, r.mask_w = m.shape
+            r.mask_row_bytes = m.shape[1]
+            mask = m
+        keep.append(mask)
+    r._keep = keep
+    return r
+
+
+def probe_encode_roi(shape, prec, params=None, rects=None, mask=None, shift=0, components=None, signed=False,
+                     origin=None):
+    """gk_probe_encode_roi: what an encode of a (C, H, W) image of `prec` bits under `params` and
+    Engine.set_encode_roi(rects, mask, shift, components) would answer, no engine or GPU needed: the
+    shift of each component (0: it does not carry the region).  A refusal raises ValueError with
+    the engine's message."""
+    lib = load_library()
+    c, h, w = shape
+    info = ImageInfo(w, h, c, prec, int(signed), 0)
+    if params is None:
+        params = default_params()
+    if origin is not None:
+        info.x0, info.y0 = int(origin[0]), int(origin[1])
+    else:   # as Engine.encode: without an origin the image sits at the tile grid's
+        info.x0, info.y0 = params.tx0, params.ty0
+    r = _encode_roi(rects, mask, shift, components)
+    if r is None:
+        raise ValueError("gk_probe_encode_roi: roi: empty region (no rectangle and no non-zero mask byte)")
+    out = (ctypes.c_uint32 * max(c, 1))()
+    msg = ctypes.create_string_buffer(512)
+    if lib.gk_probe_encode_roi(ctypes.byref(info), ctypes.byref(params), ctypes.byref(r), out, msg, len(msg)) != 0:
+        raise ValueError("gk_probe_encode_roi: " + msg.value.decode())
+    return [out[k] for k in range(c)]
 
 
 # GRK_COLOR_SPACE by name (gk_encode_colour::colour_space)
@@ -368,6 +453,14 @@ def load_library(build_if_missing=True):
     lib.gk_probe_encode_convert.restype = ctypes.c_int
     lib.gk_probe_encode_convert.argtypes = [P(ImageInfo), P(EncodeConvert)] + [P(ctypes.c_uint32)] * 4 + \
         [ctypes.c_char_p, ctypes.c_size_t]
+    lib.gk_set_encode_roi.restype = ctypes.c_int
+    lib.gk_set_encode_roi.argtypes = [ctypes.c_void_p, P(EncodeRoi)]
+    lib.gk_probe_encode_roi.restype = ctypes.c_int
+    lib.gk_probe_encode_roi.argtypes = [P(ImageInfo), P(CParameters), P(EncodeRoi), P(ctypes.c_uint32), ctypes.c_char_p,
+                                        ctypes.c_size_t]
+    lib.gk_roi_band_mask.restype = ctypes.c_int
+    lib.gk_roi_band_mask.argtypes = [ctypes.c_void_p, P(ImageInfo), P(CParameters)] + [ctypes.c_uint32] * 4 + \
+        [ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_uint32), P(ctypes.c_uint32), ctypes.c_int]
     lib.gk_set_default_transcode.argtypes = [P(TranscodeParams)]
     lib.gk_transcode.restype = ctypes.c_int
     lib.gk_transcode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(TranscodeParams),
@@ -754,6 +847,44 @@ class Engine:
         spec = None if space is None else _encode_convert(space, chroma)
         if self.lib.gk_set_encode_convert(self.ctx, ctypes.byref(spec) if spec is not None else None) != 0:
             raise ValueError("gk_set_encode_convert: " + self.lib.gk_last_error(self.ctx).decode())
+
+    def set_encode_roi(self, rects=None, mask=None, shift=0, components=None):
+        """gk_set_encode_roi (sticky): later encode / encode_pixels calls code the region, the union of
+        rects [(x0, y0, x1, y1)] (half-open, image samples) and the non-zero elements of mask (an
+        (H, W) numpy array or torch cuda tensor of 8-bit elements), ahead of the background
+        (maxshift): components (None: all) get an RGN marker with `shift` (0: the smallest legal one).
+        No rectangle and no mask clears it.  A refusal raises ValueError and leaves the engine with
+        none; what depends on the image is refused by the encode (RuntimeError)."""
+        r = _encode_roi(rects, mask, shift, components)
+        if self.lib.gk_set_encode_roi(self.ctx, ctypes.byref(r) if r is not None else None) != 0:
+            raise ValueError("gk_set_encode_roi: " + self.lib.gk_last_error(self.ctx).decode())
+
+    def roi_band_mask(self, shape, prec, params=None, comp=0, tile=0, resolution=0, band=0, signed=False, origin=None,
+                      out=None):
+        """gk_roi_band_mask: the coefficient mask (uint8, 1 = region) of one band of a (C, H, W) image
+        of `prec` bits under `params` and the engine's current region, computed by the kernels the
+        encode runs.  band: 0 (LL) at resolution 0; above it 0 HL, 1 LH, 2 HH.  Returns an (h, w)
+        numpy array, or with ``out`` (a torch cuda uint8 tensor) fills it on the device and returns
+        (h, w)."""
+        c, h, w = shape
+        info = ImageInfo(w, h, c, prec, int(signed), 0)
+        if params is None:
+            params = default_params()
+        if origin is not None:
+            info.x0, info.y0 = int(origin[0]), int(origin[1])
+        else:
+            info.x0, info.y0 = params.tx0, params.ty0
+        bw, bh = ctypes.c_uint32(), ctypes.c_uint32()
+        args = (self.ctx, ctypes.byref(info), ctypes.byref(params), comp, tile, resolution, band)
+        if out is not None:
+            if self.lib.gk_roi_band_mask(*args, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(bw),
+                                         ctypes.byref(bh), 1) != 0:
+                self._err("gk_roi_band_mask")
+            return bh.value, bw.value
+        buf = np.zeros(max(w * h, 1), np.uint8)
+        if self.lib.gk_roi_band_mask(*args, buf.ctypes.data, buf.size, ctypes.byref(bw), ctypes.byref(bh), 0) != 0:
+            self._err("gk_roi_band_mask")
+        return buf[:bw.value * bh.value].reshape(bh.value, bw.value).copy()
 
     def encode_pixels(self, pixels, prec, signed=False, params=None, out=None, origin=None):
         """gk_encode_pixels: encode packed pixels.  pixels: an (H, W, C) or (H, W) numpy array (host)

@@ -226,6 +226,9 @@ struct Params {
     // the caller's COM markers (Rcom 0 binary / 1 text, bytes) written instead of the default one
     std::vector<std::pair<uint32_t, std::string>> comments;
     uint32_t roi(uint32_t c) const { return c < roishift.size() ? roishift[c] : 0u; }
+    // encode: roishift belongs to a shaped region (gk_set_encode_roi): T1 scales the coefficients its
+    // masks mark, not the whole component
+    bool region = false;
     bool ht() const { return (cblk_sty & 0x40) != 0; }
     // a code-block side above 64 (128 x 32 ... 1024 x 4): Part-1 blocks take the lane-per-block
     // coders of gk_t1ms.hip, whose state is sized by the block (T1::alloc, T1.cpp:337-398), HT
@@ -866,6 +869,9 @@ static void build_plan(Plan& P) {
     uint64_t off = 0;
     for (auto& G : P.blocks) {
         uint32_t cap = (uint32_t)G.w * G.h * 4 + 64;
+        // TERMALL under an ROI shift: the shift's bit-planes add passes whose every termination
+        // costs bytes a small block's samples do not pay for (up to 5 per pass, PTERM included)
+        if ((G.flags >> 3) && (P.p.c_sty(G.comp) & 0x04)) cap += 5u * 3u * G.band_numbps;
         G.data_off = off;
         G.data_cap = cap;
         off += align_up(cap, 64);
@@ -3079,6 +3085,94 @@ static void enc_convert_grids(const gk_image_info& info, const EncConvert& c, ui
     }
 }
 
+// gk_set_encode_roi: the shaped region of later encodes, copied in (the mask's bytes go to the
+// device at once; the host keeps whether any of them is set).
+struct EncRoi {
+    bool set = false;
+    uint32_t shift = 0;
+    std::vector<uint32_t> comps;         // empty: every component
+    std::vector<gk_rect> rects;
+    bool has_mask = false, mask_any = false;
+    uint32_t mask_w = 0, mask_h = 0;
+};
+// What no image can make valid.  scan: look at a host mask's bytes.
+static void enc_roi_read(EncRoi& R, const gk_encode_roi& s, bool scan) {
+    R = EncRoi();
+    if (s.num_comps && !s.comps) throw GkError("roi: num_comps without comps");
+    if (s.num_rects && !s.rects) throw GkError("roi: num_rects without rects");
+    if (s.num_rects > 4096) throw GkError("roi: more than 4096 rectangles (use a mask)");
+    if (s.shift >= 32) throw GkError("ROI shift must be below 32");
+    R.shift = s.shift;
+    R.comps.assign(s.comps, s.comps + s.num_comps);
+    R.rects.assign(s.rects, s.rects + s.num_rects);
+    for (const gk_rect& q : R.rects)
+        if (q.x1 <= q.x0 || q.y1 <= q.y0) throw GkError("roi: empty rectangle");
+    if (s.mask) {
+        if (!s.mask_w || !s.mask_h) throw GkError("roi: a mask without a size");
+        if (s.mask_row_bytes < s.mask_w) throw GkError("roi: mask_row_bytes is below mask_w");
+        R.has_mask = true; R.mask_w = s.mask_w; R.mask_h = s.mask_h;
+        R.mask_any = true;
+        if (scan && !s.mask_on_device) {
+            R.mask_any = false;
+            for (uint32_t y = 0; y < s.mask_h && !R.mask_any; ++y) {
+                const uint8_t* row = s.mask + (size_t)y * s.mask_row_bytes;
+                R.mask_any = std::any_of(row, row + s.mask_w, [](uint8_t v) { return v != 0; });
+            }
+        }
+    }
+    if (R.rects.empty() && !(R.has_mask && R.mask_any)) throw GkError("roi: empty region (no rectangle and no non-zero mask byte)");
+    R.set = true;
+}
+// What depends on the image and the coding: the refusals, and the shift of every component
+// (want.p.roishift; want.p.region).  want: the encode's request after set_params and the MCT rules.
+static void enc_roi_apply(const EncRoi& R, Plan& want) {
+    char msg[256];
+    if (!want.p.roishift.empty())
+        throw GkError("roi: a region together with roi_compno / roi_shift (the whole component as the region): give one of them");
+    if (want.subsampled()) throw GkError("roi: subsampled components (the region is given on the image's grid, which every component must share)");
+    for (const gk_rect& q : R.rects)
+        if (q.x1 > want.w || q.y1 > want.h) {
+            snprintf(msg, sizeof msg, "roi: rectangle [%u, %u) x [%u, %u) outside the %u x %u image", q.x0, q.x1, q.y0, q.y1,
+                     want.w, want.h);
+            throw GkError(msg);
+        }
+    if (R.has_mask && (R.mask_w != want.w || R.mask_h != want.h)) {
+        snprintf(msg, sizeof msg, "roi: the mask is %u x %u, the image %u x %u", R.mask_w, R.mask_h, want.w, want.h);
+        throw GkError(msg);
+    }
+    for (uint32_t c : R.comps)
+        if (c >= want.nc) {
+            snprintf(msg, sizeof msg, "roi: component index %u past the last (%u components)", c, want.nc);
+            throw GkError(msg);
+        }
+    std::vector<uint8_t> rs(want.nc, 0);
+    for (uint32_t c = 0; c < want.nc; ++c) {
+        if (!R.comps.empty() && std::find(R.comps.begin(), R.comps.end(), c) == R.comps.end()) continue;
+        // the nominal Mb: the largest band bit-plane count without ROI (the same for every tile)
+        uint32_t mb = 0;
+        const uint32_t nres = want.p.c_numres(c);
+        for (uint32_t r = 0; r < nres; ++r)
+            for (uint32_t orient = r ? 1 : 0; orient < (r ? 4u : 1u); ++orient) {
+                BandG B{};
+                B.orient = orient;
+                band_quant(want, c, nres, r, B);
+                mb = std::max(mb, B.numbps);
+            }
+        const uint32_t shift = R.shift ? R.shift : mb;
+        if (shift < mb) {
+            snprintf(msg, sizeof msg, "roi: shift %u is below the smallest legal shift %u of component %u (a background "
+                     "magnitude must stay below 2^shift)", shift, mb, c);
+            throw GkError(msg);
+        }
+        if (shift == 0) continue;   // (a component without bit-planes)
+        if (shift >= 32) throw GkError("ROI shift must be below 32");
+        if (mb + shift > 25) throw GkError("ROI shift too large for this precision");
+        rs[c] = (uint8_t)shift;
+    }
+    want.p.roishift = rs;
+    want.p.region = true;
+}
+
 // What the display flags (gk_set_decode_display) make of the output channels: the CLI's
 // GrkDecompress::postProcess (grk_decompress.cpp:1335-1389, 1495) resolved from the header alone.
 struct DisplayOut {
@@ -3439,6 +3533,10 @@ struct gk_ctx {
     EncColour enc_col;                     // gk_set_encode_colour: the next encodes' colour description
     EncConvert enc_conv;                   // gk_set_encode_convert: sticky, read by the encode entry points, never written by an encode
     std::vector<uint8_t> enc_jp2h;         // the jp2h contents of the JP2 encode in progress (setup_plan)
+    EncRoi enc_roi;                        // gk_set_encode_roi: sticky, read by setup_plan, never written by an encode
+    DevBuf droi_rects, droi_mask;          // its rectangles (4 u32 each) and its mask (mask_w bytes per row), uploaded when set
+    DevBuf droi;                           // the coefficient masks of the encode in progress: two byte planes
+    hipEvent_t roi_ev[2] = {nullptr, nullptr};
     std::vector<uint32_t> hdr_dx, hdr_dy, hdr_prec, hdr_sgnd;   // the last gk_decode_header's components
     bool enc_rc = false;                // its rate-control flag (GkBlock::flags bit 1)
     // band quantisation held by the cached plan's bands: the plan's own (encoder, native_qcd)
@@ -3567,6 +3665,7 @@ static std::string plan_key(const Plan& P) {
     k += " o" + std::to_string(P.x0) + "," + std::to_string(P.y0) + "," + std::to_string(P.gx0) + "," + std::to_string(P.gy0);
     for (size_t c = 0; c < P.p.roishift.size(); ++c)   // non-zero (component, shift) pairs only
         if (P.p.roishift[c]) k += " roi" + std::to_string(c) + ":" + std::to_string(P.p.roishift[c]);
+    if (P.p.region) k += " region";   // (the region's shape is not part of the plan: the masks are per call)
     for (uint32_t r = 0; r < P.p.numres; ++r) k += " " + std::to_string(P.p.prcw[r]) + "," + std::to_string(P.p.prch[r]);
     for (const Params::CompCod& q : P.p.cc) {   // COC: every component's coding
         k += " coc" + std::to_string(q.numres) + "," + std::to_string(q.cbw) + "," + std::to_string(q.cbh) + "," +
@@ -3738,16 +3837,10 @@ static float ev_ms(gk_ctx* ctx, int a, int b) {
 // ---------------------------------------------------------------------------
 // Encode
 // ---------------------------------------------------------------------------
-// Encode tiles [tb, te) (te = 0: all).  with_header: SOC..main header + tile parts + EOC
-// (a complete codestream); otherwise only the tile parts, back to back, with their
-// lengths in part_lens (tile sharding across devices, SURVEY.md §8(e)).
-// cv: the call converts R, G, B to sYCC first (gk_set_encode_convert): its component grids and
-// colour description stand for the engine's.
-static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* cp, const EncConvCall* cv = nullptr) {
-    const std::vector<uint8_t>& enc_dx = cv ? cv->cdx : ctx->enc_dx;
-    const std::vector<uint8_t>& enc_dy = cv ? cv->cdy : ctx->enc_dy;
-    const EncColour& enc_col = cv ? cv->col : ctx->enc_col;
-    Plan want;
+// The request of an encode: the image, the coding and the sticky encode settings as a Plan to be
+// built, with every refusal that needs no device (also what gk_probe_encode_roi answers from).
+static void encode_request(Plan& want, const gk_image_info* info, const gk_cparameters* cp, const std::vector<uint8_t>& enc_dx,
+                           const std::vector<uint8_t>& enc_dy, bool clears_mct) {
     want.w = info->w; want.h = info->h; want.nc = info->numcomps; want.prec = info->prec; want.sgnd = info->sgnd;
     set_params(want.p, cp, want.nc);
     // canvas offsets: image origin (grk_image::x0 / y0) and tile grid origin (grk_cparameters::tx0 / ty0);
@@ -3766,7 +3859,7 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     if (want.p.tw && ((uint64_t)want.gx0 + want.p.tw <= want.x0 || (uint64_t)want.gy0 + want.p.th <= want.y0))
         throw GkError("the first tile must overlap the image area");
     if (want.nc < 3) want.p.mct = 0;
-    if (enc_col.clears_mct()) want.p.mct = 0;   // sYCC / e-sYCC (CodeStreamCompress.cpp:494-500)
+    if (clears_mct) want.p.mct = 0;   // sYCC / e-sYCC (CodeStreamCompress.cpp:494-500)
     // CodeStreamCompress.cpp:501-512: no MCT unless the first three components share a grid
     if (want.p.mct && !want.mct3()) want.p.mct = 0;
     check_poc_coverage(want.p, want.nc);
@@ -3777,11 +3870,27 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     if (want.prec == 0 || want.prec > 31) throw GkError("component precision must be 1..31 bits");
     check_precision(want);
     if (want.w == 0 || want.h == 0) throw GkError("empty image");
-    // the jp2h contents of this call, built (and a colour description refused) once, here
-    if (want.p.jp2) ctx->enc_jp2h = jp2h_content(want, &enc_col);
+}
+static void encode_request_tail(Plan& want, const EncRoi* roi) {
     // grk_compress.cpp:981-988 (and A.6.1's xcb, ycb): 4 <= side <= 1024, at most 4096 samples
     if (want.p.cbw < 2 || want.p.cbh < 2 || want.p.cbw > 10 || want.p.cbh > 10 || want.p.cbw + want.p.cbh > 12)
         throw GkError("code-block size must be 4..1024 per side with at most 4096 samples");
+    if (roi && roi->set) enc_roi_apply(*roi, want);
+}
+// Encode tiles [tb, te) (te = 0: all).  with_header: SOC..main header + tile parts + EOC
+// (a complete codestream); otherwise only the tile parts, back to back, with their
+// lengths in part_lens (tile sharding across devices, SURVEY.md §8(e)).
+// cv: the call converts R, G, B to sYCC first (gk_set_encode_convert): its component grids and
+// colour description stand for the engine's.
+static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* cp, const EncConvCall* cv = nullptr) {
+    const std::vector<uint8_t>& enc_dx = cv ? cv->cdx : ctx->enc_dx;
+    const std::vector<uint8_t>& enc_dy = cv ? cv->cdy : ctx->enc_dy;
+    const EncColour& enc_col = cv ? cv->col : ctx->enc_col;
+    Plan want;
+    encode_request(want, info, cp, enc_dx, enc_dy, enc_col.clears_mct());
+    // the jp2h contents of this call, built (and a colour description refused) once, here
+    if (want.p.jp2) ctx->enc_jp2h = jp2h_content(want, &enc_col);
+    encode_request_tail(want, &ctx->enc_roi);
     ensure_plan(ctx, want);
     restore_native_qcd(ctx);
     // encode: ROI-scaled indices keep 6 fractional bits below them in a 31-bit magnitude
@@ -3792,6 +3901,33 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
             for (const ResG& R : T.comps[ci].res)
                 for (const auto& B : R.bands)
                     if (ctx->plan.p.roi(ci) && B.numbps > 25) throw GkError("ROI shift too large for this precision");
+}
+
+// The coefficient masks of the engine's region for the current plan (whole image): the level-0
+// mask from the rectangles and the mask uploaded by gk_set_encode_roi, then one launch per
+// decomposition level and tile class, ping-ponging between the two mask planes as the DWT does
+// between a component's work planes.  Stream-ordered; nothing returns to the host.
+static uint8_t* run_roi_masks(gk_ctx* ctx) {
+    const Plan& P = ctx->plan;
+    const EncRoi& R = ctx->enc_roi;
+    hipStream_t st = ctx->st;
+    uint8_t* m = (uint8_t*)ctx->droi.get(2 * P.plane_elems);
+    HIPCHK(hipEventRecord(ctx->roi_ev[0], st));
+    gk_launch_roi_fill(st, m, P.stride, P.w, P.h, (const uint32_t*)ctx->droi_rects.p, (uint32_t)R.rects.size(),
+                       R.has_mask ? (const uint8_t*)ctx->droi_mask.p : nullptr, R.mask_w);
+    const SGroup& G = P.groups[0];   // one grid, one transform (no subsampling; COC is never written)
+    for (uint32_t l = 1; l < G.numres; ++l)
+        for (const ShapeG& S0 : G.shapes) {
+            GkTiles tb = S0.tb;
+            tb.ox = 0u - S0.px0; tb.oy = 0u - S0.py0;
+            uint8_t* A = m;
+            uint8_t* B = m + P.plane_elems;
+            gk_launch_roi_level(st, !G.irrev, (l & 1) ? A : B, (l & 1) ? B : A, P.stride, S0.resw[l - 1], S0.resh[l - 1],
+                                S0.parx[l - 1], S0.pary[l - 1], tb);
+        }
+    HIPCHK(hipEventRecord(ctx->roi_ev[1], st));
+    launch_check(__LINE__);
+    return m;
 }
 
 // gk_encode_blocks: the T1 results of the (single) tile in canonical order, the block bytes
@@ -4107,6 +4243,10 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     }
     launch_check(__LINE__);
     HIPCHK(hipEventRecord(ctx->ev[3], st));
+    // a shaped region: its coefficient masks, which the T1 front ends index like the coefficients
+    const bool region = !xc && P.p.region;
+    const uint8_t* roi = region ? run_roi_masks(ctx) : nullptr;
+    const uint64_t roi_mod = 2 * (uint64_t)RG.plane;
     // T1 over the block range [b0, b1): every per-block device array is range-local
     const bool do_rc = P.p.rate_control();
     const uint64_t slot0 = P.blocks[b0].data_off;
@@ -4172,17 +4312,17 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
         uint8_t* mel = (uint8_t*)ctx->dsym.get((size_t)nbx * GK_HT_MEL_CAP + 256);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[8], st));
-        gk_launch_ht_enc(st, arena, dblk, dbytes, mel, GK_HT_MEL_CAP, dinfo, nbr, derr, P.p.wide(), xc != nullptr);
+        gk_launch_ht_enc(st, arena, dblk, dbytes, mel, GK_HT_MEL_CAP, dinfo, nbr, derr, P.p.wide(), xc != nullptr, roi, roi_mod);
     } else if (P.p.t1_generic()) {
         // mode switches: lane-per-block coder with per-pass termination rules (gk_t1ms.hip)
         uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(nbx));
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[8], st));
         gk_launch_t1_enc_ms(st, arena, dblk, dbytes, dps, dinfo, nbr, derr, ctx->nmse_tab, dpcount, mst, P.p.cblk_sty & 0x3f,
-                            xc != nullptr);
+                            xc != nullptr, roi, roi_mod);
     } else if (nbr < 8192 || getenv("GK_T1ENC_SERIAL")) {
         gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse, nullptr, 0, 0xffffffffu,
-                        xc != nullptr);
+                        xc != nullptr, roi, roi_mod);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[8], st));
         gk_launch_t1_mq(st, dsym, dsymoff, dpe, dcm, dblk, dbytes, dps, dinfo, nbr, derr, dnmse, dpcount, nullptr, 0,
@@ -4195,7 +4335,7 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
         // share a SIMD with an MQ chain (sharing one slowed the chains more than the overlap
         // gained).  Each block is coded exactly as in one pass; only the launch order changes.
         uint32_t* dw = (uint32_t*)ctx->dweight.get(4 * (size_t)nbr);
-        gk_launch_t1_weight(st, arena, dblk, dw, nbr);
+        gk_launch_t1_weight(st, arena, dblk, dw, nbr, roi, roi_mod);
         uint32_t* hw = (uint32_t*)ctx->hweight.get(4 * (size_t)nbr);
         HIPCHK(hipMemcpyAsync(hw, dw, 4 * (size_t)nbr, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -4239,7 +4379,7 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
         for (int k = 0; k < nch; ++k) {
             const uint32_t base = cut[k], cnt = cut[k + 1] - cut[k];
             gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse, dord, base, cnt,
-                            xc != nullptr);
+                            xc != nullptr, roi, roi_mod);
             if (k + 1 < nch) {
                 HIPCHK(hipEventRecord(ctx->xev[k], st));
                 HIPCHK(hipStreamWaitEvent(ctx->aux[k], ctx->xev[k], 0));
@@ -4680,6 +4820,8 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     ctx->tm.t1_ms = ev_ms(ctx, 3, 4);
     ctx->tm.t1_cm_ms = ev_ms(ctx, 3, 8);
     ctx->tm.t1_coder_ms = ev_ms(ctx, 8, 4);
+    ctx->tm.roi_ms = 0.f;
+    if (region) (void)hipEventElapsedTime(&ctx->tm.roi_ms, ctx->roi_ev[0], ctx->roi_ev[1]);
     ctx->tm.cs_bytes = total;
     {
         uint64_t tbytes = 0;
@@ -7045,6 +7187,7 @@ gk_ctx* gk_create(int device_id) {
         if (hipStreamCreateWithFlags(&a, hipStreamNonBlocking) != hipSuccess) { gk_destroy(ctx); return nullptr; }
     for (auto& e : ctx->ev) (void)hipEventCreate(&e);
     for (auto& e : ctx->xev) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    for (auto& e : ctx->roi_ev) (void)hipEventCreate(&e);
     // nmsedec lookup tables (t1_generate_luts.cpp:338-362): sig, sig0, ref, ref0
     int16_t tab[4][128];
     for (int i = 0; i < 128; ++i) {
@@ -7082,6 +7225,7 @@ void gk_destroy(gk_ctx* ctx) {
         if (a) { (void)hipStreamSynchronize(a); (void)hipStreamDestroy(a); }
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->xev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->roi_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->nmse_tab) (void)hipFree(ctx->nmse_tab);
     if (ctx->st) (void)hipStreamDestroy(ctx->st);
     delete ctx;
@@ -7187,6 +7331,8 @@ int gk_encode_tiles(gk_ctx* ctx, const gk_image_info* info, const void* const* c
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
         refuse_under_convert(ctx, "gk_encode_tiles");
+        if (ctx->enc_roi.set)
+            throw GkError("roi: gk_encode_tiles while gk_set_encode_roi is set (whole images only: use gk_encode / gk_encode_pixels, or clear it)");
         int rc = 0;
         size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc,
                                tile_begin, tile_end, false, part_lens);
@@ -7239,6 +7385,8 @@ int gk_main_header(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters*
     if (!ctx || !info || !out) return -1;
     try {
         refuse_under_convert(ctx, "gk_main_header");
+        if (ctx->enc_roi.set)
+            throw GkError("roi: gk_main_header while gk_set_encode_roi is set (whole images only: use gk_encode / gk_encode_pixels, or clear it)");
         setup_plan(ctx, info, p);
         std::vector<uint8_t> H;
         size_t tlm = 0;
@@ -7446,6 +7594,97 @@ int gk_set_encode_convert(gk_ctx* ctx, const gk_encode_convert* spec) {
         if (!spec || spec->space == 0) return 0;
         enc_convert_check(*spec);
         ctx->enc_conv.space = spec->space; ctx->enc_conv.dx = spec->chroma_dx; ctx->enc_conv.dy = spec->chroma_dy;
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_set_encode_roi(gk_ctx* ctx, const gk_encode_roi* roi) {
+    if (!ctx) return -1;
+    ctx->enc_roi = EncRoi();
+    if (!roi) return 0;
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        EncRoi R;
+        enc_roi_read(R, *roi, true);
+        if (!R.rects.empty()) {
+            std::vector<uint32_t> q;
+            for (const gk_rect& r : R.rects) { q.push_back(r.x0); q.push_back(r.y0); q.push_back(r.x1); q.push_back(r.y1); }
+            HIPCHK(hipMemcpy(ctx->droi_rects.get(q.size() * 4), q.data(), q.size() * 4, hipMemcpyHostToDevice));
+        }
+        if (R.has_mask) {
+            HIPCHK(hipStreamSynchronize(ctx->st));
+            void* d = ctx->droi_mask.get((size_t)R.mask_w * R.mask_h);
+            HIPCHK(hipMemcpy2D(d, R.mask_w, roi->mask, roi->mask_row_bytes, R.mask_w, R.mask_h,
+                               roi->mask_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+            if (roi->mask_on_device) {   // is any byte set?  (once, here: an encode never asks)
+                uint32_t* flag = (uint32_t*)ctx->derr.get(64);
+                uint32_t any = 0;
+                HIPCHK(hipMemsetAsync(flag, 0, 4, ctx->st));
+                gk_launch_roi_any(ctx->st, (const uint8_t*)d, (size_t)R.mask_w * R.mask_h, flag);
+                HIPCHK(hipMemcpyAsync(&any, flag, 4, hipMemcpyDeviceToHost, ctx->st));
+                HIPCHK(hipStreamSynchronize(ctx->st));
+                R.mask_any = any != 0;
+                if (R.rects.empty() && !R.mask_any) throw GkError("roi: empty region (no rectangle and no non-zero mask byte)");
+            }
+        }
+        ctx->enc_roi = R;
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_probe_encode_roi(const gk_image_info* info, const gk_cparameters* params, const gk_encode_roi* roi,
+                        uint32_t* shift_out, char* msg, size_t msg_cap) {
+    if (msg && msg_cap) msg[0] = 0;
+    try {
+        if (!info || !roi) throw GkError("roi: no image or region description");
+        EncRoi R;
+        enc_roi_read(R, *roi, true);
+        Plan want;
+        const std::vector<uint8_t> none;
+        encode_request(want, info, params, none, none, false);
+        encode_request_tail(want, &R);
+        if (shift_out)
+            for (uint32_t c = 0; c < want.nc; ++c) shift_out[c] = want.p.roi(c);
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
+        return -1;
+    }
+}
+
+int gk_roi_band_mask(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* params, uint32_t comp, uint32_t tile,
+                     uint32_t resolution, uint32_t band, uint8_t* out, size_t cap, uint32_t* w, uint32_t* h,
+                     int out_on_device) {
+    if (!ctx || !info || !w || !h) return -1;
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        if (!ctx->enc_roi.set) throw GkError("roi: no region is set");
+        refuse_under_convert(ctx, "gk_roi_band_mask");
+        setup_plan(ctx, info, params);
+        const Plan& P = ctx->plan;
+        if (comp >= P.nc || tile >= P.tiles.size() || resolution >= P.p.numres ||
+            band >= P.tiles[tile].comps[comp].res[resolution].bands.size())
+            throw GkError("roi: component, tile, resolution or band out of range");
+        const TileG& T = P.tiles[tile];
+        const BandG& B = T.comps[comp].res[resolution].bands[band];
+        *w = B.x1 - B.x0; *h = B.y1 - B.y0;   // (either may be 0: an empty band)
+        const size_t need = (size_t)*w * *h;
+        if (need > cap) { ctx->err = "output capacity too small"; return -2; }
+        if (!need) return 0;
+        if (!out) return -1;
+        const uint8_t* m = run_roi_masks(ctx);
+        const uint8_t* src = m + (size_t)B.plane * P.plane_elems + (size_t)(T.y0 - P.y0 + B.offy) * P.stride + (T.x0 - P.x0 + B.offx);
+        HIPCHK(hipMemcpy2DAsync(out, *w, src, P.stride, *w, *h, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                ctx->st));
+        HIPCHK(hipStreamSynchronize(ctx->st));
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;

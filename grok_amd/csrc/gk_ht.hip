@@ -57,12 +57,17 @@ __device__ __forceinline__ void uvlc_code(int u, uint32_t& pre, int& plen, uint3
 // =============================================================================
 // INDEX (transcode): the coefficients are signed quantisation indices (ROI shift included), coded
 // as they are: no quantisation, no ROI up-shift.
-template <int HT_WG, int HT_LINE, bool INDEX = false>
+// REGION (a shaped region of interest; never with INDEX): roi holds a byte per coefficient, laid out
+// like a component's plane pair (gk_roi.hip); only the marked indices take the ROI up-shift.
+template <int HT_WG, int HT_LINE, bool INDEX = false, bool REGION = false>
 __global__ __launch_bounds__(HT_WG) void k_ht_enc(const int32_t* __restrict__ coef, const GkBlock* __restrict__ blocks,
                                                   uint8_t* __restrict__ bytes, uint8_t* __restrict__ mel_scratch,
                                                   uint32_t mel_cap, uint32_t* __restrict__ info, uint32_t nblocks,
-                                                  int* __restrict__ err, uint32_t nl) {
+                                                  int* __restrict__ err, uint32_t nl, const uint8_t* __restrict__ roi,
+                                                  uint64_t roi_mod) {
     __shared__ uint16_t s_tab[2][2048];
+    // REGION: the region bits of the staged columns, one byte per staged row
+    __shared__ uint8_t s_roi[REGION ? 2 : 1][REGION ? HT_WG : 1];
     __shared__ uint8_t s_e[HT_LINE][HT_WG];
     __shared__ uint8_t s_cx[HT_LINE][HT_WG];
     // Input staging: a lane's 8 columns x 2 rows, loaded as two 16-byte pieces per row when its
@@ -189,11 +194,32 @@ __global__ __launch_bounds__(HT_WG) void k_ht_enc(const int32_t* __restrict__ co
     // ROI maxshift (the component is the region): every index magnitude scaled up by 2^shift, the
     // band's bit-plane count raised by it (standard-correct; Grok's encoder only raises the count)
     const uint32_t rshift = G.flags >> 3;
+    // REGION: the block's mask, staged eight columns at a time beside the samples (no pass of its
+    // own over the block: a lane would read w * h scattered bytes to learn what the staging
+    // tells it anyway); NULL for a component without a shift
+    const uint8_t* rmask = nullptr;
+    if constexpr (REGION) {
+        if (rshift) rmask = roi + G.band_off % roi_mod;
+    }
     // columns [x8, x8 + 8) of rows y, y + 1 into the staging (zeros outside the block)
     auto stage = [&](uint32_t x8, uint32_t y) {
         const uint32_t nc = x8 < w ? min(8u, w - x8) : 0u;
         for (uint32_t r = 0; r < 2; ++r) {
             const int32_t* row = src + (size_t)(y + r) * stride + x8;
+            if constexpr (REGION) {
+                uint32_t bits = 0;
+                if (rmask && y + r < h) {
+                    const uint8_t* mrow = rmask + (size_t)(y + r) * stride + x8;
+                    if (nc == 8 && ((uintptr_t)mrow & 7) == 0) {   // eight mask bytes (0 / 1) in one load
+                        const uint2 q = *reinterpret_cast<const uint2*>(mrow);
+                        const uint32_t lo = (q.x * 0x01020408u) >> 24, hi = (q.y * 0x01020408u) >> 24;
+                        bits = (lo & 15u) | ((hi & 15u) << 4);
+                    } else {
+                        for (uint32_t k = 0; k < nc; ++k) bits |= (mrow[k] != 0 ? 1u : 0u) << k;
+                    }
+                }
+                s_roi[r][tid] = (uint8_t)bits;
+            }
             if (y + r < h && nc == 8 && ((uintptr_t)row & 15) == 0) {
                 const uint4 a = reinterpret_cast<const uint4*>(row)[0], c = reinterpret_cast<const uint4*>(row)[1];
                 s_in[r][0][tid] = (int32_t)a.x; s_in[r][1][tid] = (int32_t)a.y; s_in[r][2][tid] = (int32_t)a.z;
@@ -208,6 +234,10 @@ __global__ __launch_bounds__(HT_WG) void k_ht_enc(const int32_t* __restrict__ co
         const int32_t raw = s_in[y & 1][x & 7][tid];
         if constexpr (INDEX) return raw;
         const int32_t v = irrev ? (int32_t)(__int_as_float(raw) * inv_step) : raw;
+        if constexpr (REGION) {
+            const uint32_t rs = ((s_roi[y & 1][tid] >> (x & 7)) & 1u) ? rshift : 0u;
+            return v < 0 ? -(int32_t)((uint32_t)-v << rs) : (int32_t)((uint32_t)v << rs);
+        }
         return v < 0 ? -(int32_t)((uint32_t)-v << rshift) : (int32_t)((uint32_t)v << rshift);
     };
     // one quad: samples (x,y) (x,y+1) (x+1,y) (x+1,y+1) -> rho, exponents, MagSgn values
@@ -658,30 +688,45 @@ static uint32_t ht_lanes(const char* var) {
     return (uint32_t)(n < 1 ? 1 : (n > 64 ? 64 : n));
 }
 void gk_launch_ht_enc(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, uint8_t* mel_scratch,
-                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide, bool index) {
+                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide, bool index, const uint8_t* roi,
+                      uint64_t roi_mod) {
     if (!nblocks) return;
     static const uint32_t nl = ht_lanes("GK_HT_ENC_LANES");
+    if (roi && !index) {
+        if (wide) {
+            const uint32_t per = (HT_WG_WIDE / 64) * nl;
+            hipLaunchKernelGGL((k_ht_enc<HT_WG_WIDE, HT_LINE_WIDE, false, true>), dim3((nblocks + per - 1) / per),
+                               dim3(HT_WG_WIDE), 0, st, coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl, roi,
+                               roi_mod);
+        } else {
+            const uint32_t per = (HT_WG_STD / 64) * nl;
+            hipLaunchKernelGGL((k_ht_enc<HT_WG_STD, HT_LINE_STD, false, true>), dim3((nblocks + per - 1) / per),
+                               dim3(HT_WG_STD), 0, st, coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl, roi,
+                               roi_mod);
+        }
+        return;
+    }
     if (index) {
         if (wide) {
             const uint32_t per = (HT_WG_WIDE / 64) * nl;
             hipLaunchKernelGGL((k_ht_enc<HT_WG_WIDE, HT_LINE_WIDE, true>), dim3((nblocks + per - 1) / per), dim3(HT_WG_WIDE), 0,
-                               st, coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl);
+                               st, coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl, nullptr, 0);
         } else {
             const uint32_t per = (HT_WG_STD / 64) * nl;
             hipLaunchKernelGGL((k_ht_enc<HT_WG_STD, HT_LINE_STD, true>), dim3((nblocks + per - 1) / per), dim3(HT_WG_STD), 0, st,
-                               coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl);
+                               coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl, nullptr, 0);
         }
         return;
     }
     if (wide) {
         const uint32_t per = (HT_WG_WIDE / 64) * nl;
         hipLaunchKernelGGL((k_ht_enc<HT_WG_WIDE, HT_LINE_WIDE>), dim3((nblocks + per - 1) / per), dim3(HT_WG_WIDE), 0, st,
-                           coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl);
+                           coef, blocks, bytes, mel_scratch, mel_cap, info, nblocks, err, nl, nullptr, 0);
         return;
     }
     const uint32_t per = (HT_WG_STD / 64) * nl;
     hipLaunchKernelGGL((k_ht_enc<HT_WG_STD, HT_LINE_STD>), dim3((nblocks + per - 1) / per), dim3(HT_WG_STD), 0, st, coef, blocks, bytes,
-                       mel_scratch, mel_cap, info, nblocks, err, nl);
+                       mel_scratch, mel_cap, info, nblocks, err, nl, nullptr, 0);
 }
 
 void gk_launch_ht_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* ids, int32_t* coef,

@@ -43,14 +43,20 @@ void gk_launch_gather(hipStream_t st, const uint8_t* src, uint8_t* dst, const ui
 void gk_launch_t1_cm(hipStream_t st, const int32_t* coef, const GkBlock* blocks, const uint64_t* sym_off, uint8_t* sym,
                      uint32_t* pass_end, uint32_t* cm_info, uint32_t nblocks, int* err, const int16_t* nmse_tab,
                      int32_t* pass_nmse, const uint32_t* order = nullptr, uint32_t base = 0, uint32_t count = 0xffffffffu,
-                     bool index = false);
+                     bool index = false, const uint8_t* roi = nullptr, uint64_t roi_mod = 0);
 void gk_launch_t1_mq(hipStream_t st, const uint8_t* sym, const uint64_t* sym_off, const uint32_t* pass_end,
                      const uint32_t* cm_info, const GkBlock* blocks, uint8_t* bytes, GkPass* passes, uint32_t* info,
                      uint32_t nblocks, int* err, const int32_t* pass_nmse, uint32_t* pass_counter,
                      const uint32_t* order = nullptr, uint32_t base = 0, uint32_t count = 0xffffffffu,
                      uint32_t nsolo = 0);   // nsolo: the first positions coded by solo waves, one block each
+// roi (the three T1 encode front ends; never with index): the coefficient masks of a shaped region of
+// interest (gk_roi.hip), a byte per coefficient in two planes laid out like a component's work
+// planes: block B's mask lies at roi + B.band_off % roi_mod (roi_mod: the elements of one
+// component's plane pair), row stride B.stride.  Only the marked coefficients of a component
+// with an ROI shift are scaled up; without roi every coefficient of such a component is.
 // per-block coded bit-plane count (weight of the chunked CM / MQ overlap)
-void gk_launch_t1_weight(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint32_t* weight, uint32_t nblocks);
+void gk_launch_t1_weight(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint32_t* weight, uint32_t nblocks,
+                         const uint8_t* roi = nullptr, uint64_t roi_mod = 0);
 uint32_t gk_t1dec_lanes();
 // counters of the last k_t1_dec2 launch made with GK_T1_STATS set: max steps per wave, steps,
 // symbols (lane-parallel waves), decisions of the solo waves and of the busiest one
@@ -75,7 +81,8 @@ void gk_launch_dwt_any(hipStream_t st, bool irrev, bool forward, int32_t* in, in
 // code-blocks with mode switches (gk_t1ms.hip)
 void gk_launch_t1_enc_ms(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, GkPass* passes,
                          uint32_t* info, uint32_t nblocks, int* err, const int16_t* nmse_tab, uint32_t* pass_counter,
-                         uint8_t* state, uint32_t sty, bool index = false);
+                         uint8_t* state, uint32_t sty, bool index = false, const uint8_t* roi = nullptr,
+                         uint64_t roi_mod = 0);
 void gk_launch_t1_dec_ms(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* seglen, int32_t* coef,
                          uint32_t nblocks, uint8_t* state, uint32_t sty, bool index = false);
 size_t gk_t1ms_state_bytes(uint32_t nblocks);
@@ -100,7 +107,8 @@ void gk_launch_dwt97_inv_l1(hipStream_t st, int stype, int nc, const float* src,
                             int32_t mn, int32_t mx);
 // HTJ2K cleanup-pass block coder (gk_ht.hip); wide: some block is wider than 64 samples
 void gk_launch_ht_enc(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, uint8_t* mel_scratch,
-                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide = false, bool index = false);
+                      uint32_t mel_cap, uint32_t* info, uint32_t nblocks, int* err, bool wide = false, bool index = false,
+                      const uint8_t* roi = nullptr, uint64_t roi_mod = 0);
 void gk_launch_ht_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* ids, int32_t* coef,
                       uint32_t nblocks, int* err, bool wide = false, bool index = false);
 // JP2 palette expansion (gk_colour.hip).  One output channel: palette column `col` of the launch's
@@ -276,3 +284,16 @@ struct GkLabArgs {
     uint32_t rows;
 };
 void gk_launch_lab_rgb(hipStream_t st, int stype, int dtype, const GkLabArgs& args);
+// Coefficient masks of a shaped region of interest (gk_roi.hip).  Masks are bytes (0 / 1) in two
+// planes of the work planes' geometry (row stride `stride`, a multiple of 64).
+// level-0 mask of the w x h image: the union of nrects rectangles (device memory: x0, y0, x1, y1
+// each, half-open, image samples) and the non-zero bytes of mask (device memory or NULL, row
+// stride mask_stride)
+void gk_launch_roi_fill(hipStream_t st, uint8_t* dst, uint32_t stride, uint32_t w, uint32_t h, const uint32_t* rects,
+                        uint32_t nrects, const uint8_t* mask, uint32_t mask_stride);
+// one decomposition level of every tile of tb: the w x h sample mask at each tile's corner of src
+// (origin parities px, py) becomes the four band masks in Mallat placement at the same corner of dst
+// *flag |= 1 when any of the n bytes at m is non-zero (flag cleared by the caller)
+void gk_launch_roi_any(hipStream_t st, const uint8_t* m, size_t n, uint32_t* flag);
+void gk_launch_roi_level(hipStream_t st, bool reversible, const uint8_t* src, uint8_t* dst, uint32_t stride, uint32_t w,
+                         uint32_t h, uint32_t px, uint32_t py, GkTiles tb);

@@ -104,13 +104,16 @@ __device__ __forceinline__ int32_t wave_sum(int32_t v) {
 // into pass_nmse[b * GK_MAX_PASSES + pass].
 // INDEX (transcode; never with RC): the coefficients are signed quantisation indices (ROI shift
 // included), taken as the magnitudes: no quantisation, no ROI up-shift.
-template <bool RC, bool INDEX = false>
+// REGION (a shaped region of interest; never with INDEX): roi holds a byte per coefficient, laid out
+// like a component's plane pair (gk_roi.hip); only the marked magnitudes take the ROI up-shift.
+template <bool RC, bool INDEX = false, bool REGION = false>
 __global__ __launch_bounds__(64) void k_t1_cm(const int32_t* __restrict__ coef, const GkBlock* __restrict__ blocks,
                                               const uint64_t* __restrict__ sym_off, uint8_t* __restrict__ sym,
                                               uint32_t* __restrict__ pass_end, uint32_t* __restrict__ cm_info,
                                               uint32_t nblocks, int* err, const int16_t* __restrict__ nmse_tab,
                                               int32_t* __restrict__ pass_nmse, const uint32_t* __restrict__ order,
-                                              uint32_t base, uint32_t count) {
+                                              uint32_t base, uint32_t count, const uint8_t* __restrict__ roi,
+                                              uint64_t roi_mod) {
     __shared__ CmLds L;
     __shared__ typename std::conditional<RC, CmRcLds, char>::type R;
     // workgroup j codes block order[base + j] (all blocks in index order without an order)
@@ -126,6 +129,17 @@ __global__ __launch_bounds__(64) void k_t1_cm(const int32_t* __restrict__ coef, 
     const bool irrev = B.flags & 1;
     uint32_t m[64];
     uint64_t negcol = 0;
+    uint64_t regcol = 0;   // REGION: the rows of this column that lie in the region
+    const uint8_t* rmask = nullptr;
+    if constexpr (REGION) {
+        // (gathered before the coefficients are loaded: its loads would otherwise stay in flight
+        // beside the 64 magnitudes and cost the wave half its registers' worth of occupancy)
+        if ((B.flags >> 3) && lane < (int)w) {
+            rmask = roi + B.band_off % roi_mod + lane;
+#pragma unroll 4
+            for (uint32_t y = 0; y < h; ++y) regcol |= (uint64_t)(rmask[(size_t)y * B.stride] != 0) << y;
+        }
+    }
     uint32_t mx = 0;
 #pragma unroll
     for (int y = 0; y < 64; ++y) {
@@ -143,11 +157,23 @@ __global__ __launch_bounds__(64) void k_t1_cm(const int32_t* __restrict__ coef, 
         mx = a > mx ? a : mx;
         negcol |= (uint64_t)(raw < 0) << y;
     }
-    if (const uint32_t rs = INDEX ? 0u : B.flags >> 3) {   // ROI maxshift (the component is the region): index integer part up
+    // a block with no region coefficient stays as it is, one with nothing else takes the
+    // whole-component path below (decided per wave: the mask columns are in registers)
+    bool mixed = false;
+    if constexpr (REGION) {
+        const uint64_t vc = (lane < (int)w) ? ((h >= 64) ? ~0ull : ((1ull << h) - 1)) : 0ull;
+        mixed = __any(regcol != 0) && !__all(regcol == vc);
+    }
+    if (const uint32_t rs = (INDEX || (REGION && !mixed && !__any(regcol != 0))) ? 0u : B.flags >> 3) {
+        // ROI maxshift: index integer part up (every magnitude when the component is the region)
         mx = 0;
+        uint64_t sel = ~0ull;   // the rows scaled: all of them unless the block is mixed
+        if constexpr (REGION) sel = mixed ? regcol : ~0ull;
 #pragma unroll
         for (int y = 0; y < 64; ++y) {
-            m[y] = ((m[y] >> 6) << (6 + rs)) | (m[y] & 63u);
+            const uint32_t up = ((m[y] >> 6) << (6 + rs)) | (m[y] & 63u);
+            if constexpr (REGION) m[y] = ((sel >> y) & 1) ? up : m[y];
+            else m[y] = up;
             mx = m[y] > mx ? m[y] : mx;
         }
     }
@@ -838,19 +864,26 @@ __global__ __launch_bounds__(256) void k_t1_mq(const uint8_t* __restrict__ sym, 
 #include "gk_launch.h"
 void gk_launch_t1_cm(hipStream_t st, const int32_t* coef, const GkBlock* blocks, const uint64_t* sym_off, uint8_t* sym,
                      uint32_t* pass_end, uint32_t* cm_info, uint32_t nblocks, int* err, const int16_t* nmse_tab,
-                     int32_t* pass_nmse, const uint32_t* order, uint32_t base, uint32_t count, bool index) {
+                     int32_t* pass_nmse, const uint32_t* order, uint32_t base, uint32_t count, bool index,
+                     const uint8_t* roi, uint64_t roi_mod) {
     if (!nblocks) return;
     if (count == 0xffffffffu) count = nblocks;
     if (!count) return;
     if (index)
         hipLaunchKernelGGL((k_t1_cm<false, true>), dim3(count), dim3(64), 0, st, coef, blocks, sym_off, sym, pass_end,
-                           cm_info, nblocks, err, nmse_tab, nullptr, order, base, count);
+                           cm_info, nblocks, err, nmse_tab, nullptr, order, base, count, nullptr, 0);
+    else if (roi && pass_nmse)
+        hipLaunchKernelGGL((k_t1_cm<true, false, true>), dim3(count), dim3(64), 0, st, coef, blocks, sym_off, sym, pass_end,
+                           cm_info, nblocks, err, nmse_tab, pass_nmse, order, base, count, roi, roi_mod);
+    else if (roi)
+        hipLaunchKernelGGL((k_t1_cm<false, false, true>), dim3(count), dim3(64), 0, st, coef, blocks, sym_off, sym, pass_end,
+                           cm_info, nblocks, err, nmse_tab, pass_nmse, order, base, count, roi, roi_mod);
     else if (pass_nmse)
         hipLaunchKernelGGL(k_t1_cm<true>, dim3(count), dim3(64), 0, st, coef, blocks, sym_off, sym, pass_end, cm_info,
-                           nblocks, err, nmse_tab, pass_nmse, order, base, count);
+                           nblocks, err, nmse_tab, pass_nmse, order, base, count, nullptr, 0);
     else
         hipLaunchKernelGGL(k_t1_cm<false>, dim3(count), dim3(64), 0, st, coef, blocks, sym_off, sym, pass_end,
-                           cm_info, nblocks, err, nmse_tab, pass_nmse, order, base, count);
+                           cm_info, nblocks, err, nmse_tab, pass_nmse, order, base, count, nullptr, 0);
 }
 
 // Per block an estimate of the MQ decisions T1 will code, as the weight that orders the chunked
@@ -863,8 +896,11 @@ void gk_launch_t1_cm(hipStream_t st, const int32_t* coef, const GkBlock* blocks,
 // blocks (each is coded the same whatever the order), so it is taken over every fourth row - a
 // quarter of the coefficient lines - with the bit count scaled back (a full pass was 0.28 ms of
 // C2's encode, `profiles/r04z_C2_kernel_stats.txt`).
+// REGION: only the coefficients the region's masks mark take the ROI shift, as in k_t1_cm.
+template <bool REGION>
 __global__ __launch_bounds__(64) void k_t1_weight(const int32_t* __restrict__ coef, const GkBlock* __restrict__ blocks,
-                                                  uint32_t* __restrict__ weight, uint32_t nblocks) {
+                                                  uint32_t* __restrict__ weight, uint32_t nblocks,
+                                                  const uint8_t* __restrict__ roi, uint64_t roi_mod) {
     const uint32_t b = blockIdx.x;
     if (b >= nblocks) return;
     const int lane = threadIdx.x;
@@ -877,7 +913,11 @@ __global__ __launch_bounds__(64) void k_t1_weight(const int32_t* __restrict__ co
             const int32_t raw = coef[B.band_off + (size_t)y * B.stride + lane];
             const uint32_t a0 = irrev ? (uint32_t)fabsf(rintf((__int_as_float(raw) / B.step) * 64.0f))
                                       : (uint32_t)(raw < 0 ? -raw : raw) * 64u;
-            const uint32_t a = ((a0 >> 6) << (6 + (B.flags >> 3))) | (a0 & 63u);   // ROI maxshift
+            uint32_t rs = B.flags >> 3;   // ROI maxshift
+            if constexpr (REGION) {
+                if (rs && !roi[B.band_off % roi_mod + (size_t)y * B.stride + lane]) rs = 0;
+            }
+            const uint32_t a = ((a0 >> 6) << (6 + rs)) | (a0 & 63u);
             mx = a > mx ? a : mx;
             nbits += (a >> 6) ? 32u - __clz(a >> 6) : 0u;
         }
@@ -893,9 +933,11 @@ __global__ __launch_bounds__(64) void k_t1_weight(const int32_t* __restrict__ co
         weight[b] = planes * B.w * B.h * 5u + (uint32_t)((3ull * nbits * B.h) / (rows ? rows : 1));
     }
 }
-void gk_launch_t1_weight(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint32_t* weight, uint32_t nblocks) {
+void gk_launch_t1_weight(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint32_t* weight, uint32_t nblocks,
+                         const uint8_t* roi, uint64_t roi_mod) {
     if (!nblocks) return;
-    hipLaunchKernelGGL(k_t1_weight, dim3(nblocks), dim3(64), 0, st, coef, blocks, weight, nblocks);
+    if (roi) hipLaunchKernelGGL(k_t1_weight<true>, dim3(nblocks), dim3(64), 0, st, coef, blocks, weight, nblocks, roi, roi_mod);
+    else hipLaunchKernelGGL(k_t1_weight<false>, dim3(nblocks), dim3(64), 0, st, coef, blocks, weight, nblocks, nullptr, 0);
 }
 void gk_launch_t1_mq(hipStream_t st, const uint8_t* sym, const uint64_t* sym_off, const uint32_t* pass_end,
                      const uint32_t* cm_info, const GkBlock* blocks, uint8_t* bytes, GkPass* passes, uint32_t* info,

@@ -164,22 +164,41 @@ __device__ __forceinline__ bool ms_term_pass(uint32_t sty, int numbps, int bpno,
 // Lane = code-block.  state: MS_STATE_BYTES per block slot of this launch (lane index).
 // INDEX (transcode): the coefficients are signed quantisation indices (ROI shift included), taken
 // as the magnitudes: no quantisation, no ROI up-shift.
-template <bool INDEX>
+// REGION (a shaped region of interest; never with INDEX): roi holds a byte per coefficient, laid out
+// like a component's plane pair (gk_roi.hip); only the marked indices take the ROI up-shift.
+template <bool INDEX, bool REGION = false>
 __global__ __launch_bounds__(64) void k_t1_enc_ms(const int32_t* __restrict__ coef, const GkBlock* __restrict__ blocks,
                                                   uint8_t* __restrict__ bytes, GkPass* __restrict__ passes,
                                                   uint32_t* __restrict__ info, uint32_t nblocks, int* err,
                                                   const int16_t* __restrict__ nmse_tab, uint32_t* __restrict__ pass_counter,
-                                                  uint8_t* __restrict__ state, uint32_t sty) {
+                                                  uint8_t* __restrict__ state, uint32_t sty,
+                                                  const uint8_t* __restrict__ roi, uint64_t roi_mod) {
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= nblocks) return;
     const GkBlock G = blocks[b];
     const int w = G.w, h = G.h;
     const bool irrev = G.flags & 1, rc = (G.flags & 2) != 0;
+    // REGION: 0 no coefficient of the block is scaled, 1 every one (as without a region), 2 the marked ones
+    int rmode = 1;
+    const uint8_t* rmask = nullptr;
+    if constexpr (REGION) {
+        rmode = 0;
+        if (G.flags >> 3) {
+            rmask = roi + G.band_off % roi_mod;
+            uint32_t n = 0;
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) n += rmask[(size_t)y * G.stride + x] != 0;
+            rmode = n == 0 ? 0 : n == (uint32_t)(w * h) ? 1 : 2;
+        }
+    }
     auto smr = [&](int x, int y) -> int32_t {   // T1Part1::preCompress (T1Part1.cpp:36-87)
         const int32_t raw = coef[G.band_off + (size_t)y * G.stride + x];
         if constexpr (INDEX) return raw * 64;
         const int32_t v = irrev ? (int32_t)rintf((__int_as_float(raw) / G.step) * 64.0f) : raw * 64;
         if (!(G.flags >> 3)) return v;
+        if constexpr (REGION) {
+            if (rmode == 0 || (rmode == 2 && !rmask[(size_t)y * G.stride + x])) return v;
+        }
         // ROI maxshift (the component is the region): the index's integer part scaled up
         const uint32_t a0 = (uint32_t)(v < 0 ? -v : v), a1 = ((a0 >> 6) << (6 + (G.flags >> 3))) | (a0 & 63u);
         return v < 0 ? -(int32_t)a1 : (int32_t)a1;
@@ -541,15 +560,20 @@ __global__ __launch_bounds__(64) void k_t1_dec_ms(const uint8_t* __restrict__ by
 #include "gk_launch.h"
 void gk_launch_t1_enc_ms(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint8_t* bytes, GkPass* passes,
                          uint32_t* info, uint32_t nblocks, int* err, const int16_t* nmse_tab, uint32_t* pass_counter,
-                         uint8_t* state, uint32_t sty, bool index) {
+                         uint8_t* state, uint32_t sty, bool index, const uint8_t* roi, uint64_t roi_mod) {
     if (!nblocks) return;
     if (index) {
         hipLaunchKernelGGL(k_t1_enc_ms<true>, dim3((nblocks + 63) / 64), dim3(64), 0, st, coef, blocks, bytes, passes, info,
-                           nblocks, err, nmse_tab, pass_counter, state, sty);
+                           nblocks, err, nmse_tab, pass_counter, state, sty, nullptr, 0);
+        return;
+    }
+    if (roi) {
+        hipLaunchKernelGGL((k_t1_enc_ms<false, true>), dim3((nblocks + 63) / 64), dim3(64), 0, st, coef, blocks, bytes, passes,
+                           info, nblocks, err, nmse_tab, pass_counter, state, sty, roi, roi_mod);
         return;
     }
     hipLaunchKernelGGL(k_t1_enc_ms<false>, dim3((nblocks + 63) / 64), dim3(64), 0, st, coef, blocks, bytes, passes, info, nblocks,
-                       err, nmse_tab, pass_counter, state, sty);
+                       err, nmse_tab, pass_counter, state, sty, nullptr, 0);
 }
 void gk_launch_t1_dec_ms(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* seglen, int32_t* coef,
                          uint32_t nblocks, uint8_t* state, uint32_t sty, bool index) {

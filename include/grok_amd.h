@@ -113,6 +113,9 @@ typedef struct gk_timings {
     /* Part-1 decode: decoder classes of the last call whose solo / lane-parallel split was chosen
        by the rule for a device shared with another engine's call in progress (0 on encode) */
     uint64_t t1_shared;
+    /* encode under gk_set_encode_roi: the region's mask kernels (k_roi_fill, k_roi_level), part of
+       t1_ms (0 without a region and on decode) */
+    float roi_ms;
 } gk_timings;
 
 typedef struct gk_ctx gk_ctx;
@@ -259,6 +262,66 @@ int gk_set_encode_convert(gk_ctx* ctx, const gk_encode_convert* spec);
  * sizes cw x ch (any may be NULL); 0, or -1 with the refusal in msg. */
 int gk_probe_encode_convert(const gk_image_info* info, const gk_encode_convert* spec, uint32_t dx[3], uint32_t dy[3],
                             uint32_t cw[3], uint32_t ch[3], char* msg, size_t msg_cap);
+
+/* A shaped region of interest (ISO 15444-1 Annex H, maxshift): the samples of a region, given as
+ * rectangles and / or a mask, are coded ahead of the background.  Grok's -ROI (roi_compno /
+ * roi_shift above) makes a whole component the region; it has no counterpart to this, so the
+ * region's arithmetic is the standard's (H.3): per tile-component and decomposition level, in that
+ * level's interleaved canvas coordinates k (even low-pass, odd high-pass), a region sample at k
+ * needs the coefficients at k + d, |d| <= 1 (k even) or 2 (k odd) for 5/3, 3 or 4 for 9/7, indices
+ * outside the tile-component reflected whole-sample symmetrically (an interval of one sample needs
+ * itself); two dimensions are the product; the low/low positions are the next level's samples.  The
+ * T1 encoders scale exactly those coefficients of the listed components up by 2^shift; the band
+ * bit-plane counts rise by the shift for the whole component and one RGN marker (Srgn 0) is
+ * written per listed component, so the stream is a plain Part-1 / Part-15 maxshift stream and any
+ * decoder separates region from background by magnitude.  The masks are computed on the device
+ * inside the encode (k_roi_fill, k_roi_level).
+ * shift = 0 takes, per component, the smallest legal shift: the largest band bit-plane count of
+ * the component without ROI (a background magnitude then stays below 2^shift).
+ * Refused, each by name, by the encode (before anything is allocated or launched) and by
+ * gk_probe_encode_roi alike: a region together with roi_compno / roi_shift; an empty rectangle or
+ * one that leaves the image; a mask whose size is not the image's; a component index past the
+ * last; an empty region (no rectangle and no non-zero mask byte); subsampled components
+ * (gk_set_subsampling, gk_set_encode_convert with subsampled chroma); an explicit shift below the
+ * smallest legal one; "ROI shift too large for this precision" (a band of more than 25 bit-planes,
+ * shift included); gk_encode_tiles and gk_main_header while a region is set (sharded encodes are
+ * out of scope).  TERMALL: the code-block slots of a component with an ROI shift are enlarged by
+ * the terminations its extra passes can cost. */
+typedef struct gk_rect {
+    uint32_t x0, y0, x1, y1;   /* half-open, in samples from the image's top-left sample (not canvas coordinates) */
+} gk_rect;
+typedef struct gk_encode_roi {
+    uint32_t shift;            /* RGN SPrgn of the listed components; 0: the smallest legal shift of each */
+    uint32_t num_comps;        /* entries of comps; 0: every component carries the region */
+    const uint32_t* comps;
+    uint32_t num_rects;
+    const gk_rect* rects;
+    const uint8_t* mask;       /* NULL, or mask_h rows of mask_w bytes, mask_row_bytes apart: non-zero = region */
+    uint32_t mask_w, mask_h;   /* must be the image's w / h */
+    size_t mask_row_bytes;
+    int mask_on_device;
+} gk_encode_roi;
+/* Sticky, like gk_set_encode_colour: later gk_encode / gk_encode_pixels calls (host or device
+ * input and output, .j2k and .jp2) code the region, the union of the rectangles and the mask.
+ * Everything is copied (the mask to the device).  roi = NULL clears it: every byte as before.  What
+ * depends on the image is checked by the encode.  A refused description leaves the engine with
+ * none. */
+int gk_set_encode_roi(gk_ctx* ctx, const gk_encode_roi* roi);
+/* What an encode of `info` under `params` and `roi` would answer, no engine or device needed: 0
+ * and, in shift_out[c] (NULL, or info->numcomps entries), the shift each component gets (0: the
+ * component does not carry the region); -1 with the refusal in msg.  A mask in device memory is
+ * judged by its size alone (its bytes cannot be read without a device). */
+int gk_probe_encode_roi(const gk_image_info* info, const gk_cparameters* params, const gk_encode_roi* roi,
+                        uint32_t* shift_out, char* msg, size_t msg_cap);
+/* The coefficient mask of one band under the engine's current region, computed by the kernels the
+ * encode runs: band `band` (resolution 0: 0 = LL; above: 0 HL, 1 LH, 2 HH) of resolution
+ * `resolution` of tile `tile` (raster index) of component `comp`, as *w x *h bytes (1 = region),
+ * rows *w apart, in out (device memory if out_on_device).  Returns 0, -2 when cap is below
+ * *w * *h (both still set), -1 on error (no region set; an index out of range; whatever the encode
+ * refuses).  A diagnostic: what a region costs in coefficients. */
+int gk_roi_band_mask(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* params, uint32_t comp, uint32_t tile,
+                     uint32_t resolution, uint32_t band, uint8_t* out, size_t cap, uint32_t* w, uint32_t* h,
+                     int out_on_device);
 
 /* grk_decompress_read_header (grok.cpp:287-297, CodeStreamDecompress::readHeader) of a raw
  * codestream or a JP2 file (its jp2c box; FileFormatDecompress::read_box_hdr :632-672). */
