@@ -30,7 +30,10 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_probe_output", "gk_decode_pixels", "gk_decode_window_pixels", "gk_encode_pixels",
            "gk_set_encode_colour", "gk_jp2_boxes", "gk_header_cielab", "gk_probe_cielab",
            "gk_set_encode_convert", "gk_probe_encode_convert", "gk_set_default_transcode", "gk_transcode",
-           "gk_probe_transcode", "gk_set_encode_roi", "gk_probe_encode_roi", "gk_roi_band_mask")
+           "gk_probe_transcode", "gk_set_encode_roi", "gk_probe_encode_roi", "gk_roi_band_mask",
+           "gk_set_encode_quant", "gk_probe_encode_quant", "gk_get_encode_quant")
+GK_QUANT_STEP, GK_QUANT_BYTES, GK_QUANT_PSNR = 1, 2, 3   # gk_encode_quant::mode
+GK_QUANT_FOR_TILES, GK_QUANT_FOR_BLOCKS = 0x100, 0x200   # gk_probe_encode_quant: the call asked about
 GK_TRANSCODE_HT, GK_TRANSCODE_PART1 = 1, 2   # gk_transcode_params::target
 GK_MAX_CHANNELS = 256
 GK_DISPLAY_RGB, GK_DISPLAY_UPSAMPLE, GK_DISPLAY_FORCE_RGB, GK_DISPLAY_ICC = 1, 2, 4, 8   # gk_set_decode_display flags
@@ -256,6 +259,54 @@ def probe_encode_roi(shape, prec, params=None, rects=None, mask=None, shift=0, c
     return [out[k] for k in range(c)]
 
 
+class EncodeQuant(ctypes.Structure):
+    """gk_encode_quant"""
+    _fields_ = [("mode", ctypes.c_uint32), ("value", ctypes.c_double)]
+
+
+class QuantResult(ctypes.Structure):
+    """gk_quant_result"""
+    _fields_ = [("mode", ctypes.c_uint32), ("notch", ctypes.c_uint32), ("t1_passes", ctypes.c_uint32),
+                ("stats_passes", ctypes.c_uint32), ("base_step", ctypes.c_double), ("est_mse", ctypes.c_double),
+                ("est_psnr", ctypes.c_double), ("est_psnr_next", ctypes.c_double), ("bytes", ctypes.c_uint64)]
+
+
+def _encode_quant(step=None, max_bytes=None, psnr=None):
+    """gk_encode_quant of the Python arguments: exactly one of step (base step, nominal-range units),
+    max_bytes and psnr (dB); None when all are None."""
+    given = [(m, v) for m, v in ((GK_QUANT_STEP, step), (GK_QUANT_BYTES, max_bytes), (GK_QUANT_PSNR, psnr)) if v is not None]
+    if not given:
+        return None
+    if len(given) > 1:
+        raise ValueError("quant: give exactly one of step, max_bytes and psnr")
+    return EncodeQuant(given[0][0], float(given[0][1]))
+
+
+def probe_encode_quant(shape, prec, params=None, step=None, max_bytes=None, psnr=None, signed=False, call="encode"):
+    """gk_probe_encode_quant: what an encode of a (C, H, W) image of `prec` bits under `params` and
+    Engine.set_encode_quant(step, max_bytes, psnr) would answer, no engine or GPU needed: the
+    ladder's (step_min, step_max, notches).  call: "encode" (Engine.encode / encode_pixels),
+    "encode_tiles" or "encode_blocks".  A refusal raises ValueError with the engine's message."""
+    lib = load_library()
+    c, h, w = shape
+    info = ImageInfo(w, h, c, prec, int(signed), 0)
+    if params is None:
+        params = default_params()
+    info.x0, info.y0 = params.tx0, params.ty0
+    flags = {"encode": 0, "encode_tiles": GK_QUANT_FOR_TILES, "encode_blocks": GK_QUANT_FOR_BLOCKS}
+    if call not in flags:
+        raise ValueError("quant: call is 'encode', 'encode_tiles' or 'encode_blocks'")
+    q = _encode_quant(step, max_bytes, psnr)
+    if q is not None:
+        q.mode |= flags[call]
+    lo, hi, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint32()
+    msg = ctypes.create_string_buffer(512)
+    if lib.gk_probe_encode_quant(ctypes.byref(info), ctypes.byref(params), ctypes.byref(q) if q is not None else None,
+                                 ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(n), msg, len(msg)) != 0:
+        raise ValueError("gk_probe_encode_quant: " + msg.value.decode())
+    return lo.value, hi.value, n.value
+
+
 # GRK_COLOR_SPACE by name (gk_encode_colour::colour_space)
 COLOUR_SPACES = {"srgb": 2, "grey": 3, "gray": 3, "sycc": 4, "esycc": 5, "eycc": 5, "cmyk": 6, "cie": 7, "icc": 9}
 
@@ -458,6 +509,16 @@ def load_library(build_if_missing=True):
     lib.gk_probe_encode_roi.restype = ctypes.c_int
     lib.gk_probe_encode_roi.argtypes = [P(ImageInfo), P(CParameters), P(EncodeRoi), P(ctypes.c_uint32), ctypes.c_char_p,
                                         ctypes.c_size_t]
+    # (another build named by GROK_AMD_LIB, the A side of a measurement, may predate these three: its
+    # plain calls still run and set_encode_quant fails on the missing symbol; the tree's own must have them)
+    if hasattr(lib, "gk_set_encode_quant") or not os.environ.get("GROK_AMD_LIB"):
+        lib.gk_set_encode_quant.restype = ctypes.c_int
+        lib.gk_set_encode_quant.argtypes = [ctypes.c_void_p, P(EncodeQuant)]
+        lib.gk_probe_encode_quant.restype = ctypes.c_int
+        lib.gk_probe_encode_quant.argtypes = [P(ImageInfo), P(CParameters), P(EncodeQuant), P(ctypes.c_double),
+                                              P(ctypes.c_double), P(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_size_t]
+        lib.gk_get_encode_quant.restype = ctypes.c_int
+        lib.gk_get_encode_quant.argtypes = [ctypes.c_void_p, P(QuantResult)]
     lib.gk_roi_band_mask.restype = ctypes.c_int
     lib.gk_roi_band_mask.argtypes = [ctypes.c_void_p, P(ImageInfo), P(CParameters)] + [ctypes.c_uint32] * 4 + \
         [ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_uint32), P(ctypes.c_uint32), ctypes.c_int]
@@ -858,6 +919,23 @@ class Engine:
         r = _encode_roi(rects, mask, shift, components)
         if self.lib.gk_set_encode_roi(self.ctx, ctypes.byref(r) if r is not None else None) != 0:
             raise ValueError("gk_set_encode_roi: " + self.lib.gk_last_error(self.ctx).decode())
+
+    def set_encode_quant(self, step=None, max_bytes=None, psnr=None):
+        """gk_set_encode_quant (sticky): later HTJ2K 9/7 encodes quantise with the base step `step`
+        (nominal-range units; the default is 2^-(prec + signed)), or with the finest ladder notch
+        whose output is at most `max_bytes` long, or with the coarsest one whose estimated PSNR
+        reaches `psnr` dB.  Exactly one argument; none clears the setting.  encode_quant() reports
+        what an encode did."""
+        q = _encode_quant(step, max_bytes, psnr)
+        if self.lib.gk_set_encode_quant(self.ctx, ctypes.byref(q) if q is not None else None) != 0:
+            raise ValueError("gk_set_encode_quant: " + self.lib.gk_last_error(self.ctx).decode())
+
+    def encode_quant(self):
+        """gk_get_encode_quant: the gk_quant_result of the last encode as a dict."""
+        r = QuantResult()
+        if self.lib.gk_get_encode_quant(self.ctx, ctypes.byref(r)) != 0:
+            self._err("gk_get_encode_quant")
+        return {k: getattr(r, k) for k, _ in QuantResult._fields_}
 
     def roi_band_mask(self, shape, prec, params=None, comp=0, tile=0, resolution=0, band=0, signed=False, origin=None,
                       out=None):

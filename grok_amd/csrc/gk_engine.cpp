@@ -229,6 +229,10 @@ struct Params {
     // encode: roishift belongs to a shaped region (gk_set_encode_roi): T1 scales the coefficients its
     // masks mark, not the whole component
     bool region = false;
+    // encode: the HT 9/7 base step in nominal-range units (gk_set_encode_quant); 0: the default,
+    // 2^-(precision + signed).  It shapes no geometry: the cached plan's bands and blocks are
+    // re-stepped when it changes (sync_qstep)
+    double qstep = 0.0;
     bool ht() const { return (cblk_sty & 0x40) != 0; }
     // a code-block side above 64 (128 x 32 ... 1024 x 4): Part-1 blocks take the lane-per-block
     // coders of gk_t1ms.hip, whose state is sized by the block (T1::alloc, T1.cpp:337-398), HT
@@ -447,11 +451,9 @@ static uint32_t ht_rev_expn(uint32_t B, uint32_t ndecomp, uint32_t r, uint32_t o
     return (uint32_t)((int)B + (orient == 3 ? X(H(d) * H(d)) : X(H(d) * L(d + 1))));
 }
 
-// HT irreversible QCD: param_qcd::set_irrev_quant (HTParams.cpp:273-317), base_delta =
-// 2^-(bit depth + signed) (:211-212), 9/7 synthesis energy gains (sqrt_energy_gains,
-// HTParams.cpp:75-86: constant data of the 9/7 filter bank).
-static void ht_irrev_quant(uint32_t prec, bool sgnd, uint32_t nd, uint32_t r, uint32_t orient, uint32_t& expn,
-                           uint32_t& mant) {
+// 9/7 synthesis gain gl * gh of a band (sqrt_energy_gains, HTParams.cpp:75-86: constant data of
+// the 9/7 filter bank); its square is the band's energy gain.
+static float ht97_gain(uint32_t nd, uint32_t r, uint32_t orient) {
     static const float L97[34] = {
         1.0000e+00f, 1.4021e+00f, 2.0304e+00f, 2.9012e+00f, 4.1153e+00f, 5.8245e+00f, 8.2388e+00f, 1.1652e+01f, 1.6479e+01f,
         2.3304e+01f, 3.2957e+01f, 4.6609e+01f, 6.5915e+01f, 9.3217e+01f, 1.3183e+02f, 1.8643e+02f, 2.6366e+02f, 3.7287e+02f,
@@ -462,11 +464,19 @@ static void ht_irrev_quant(uint32_t prec, bool sgnd, uint32_t nd, uint32_t r, ui
         3.3403e+01f, 4.7240e+01f, 6.6807e+01f, 9.4479e+01f, 1.3361e+02f, 1.8896e+02f, 2.6723e+02f, 3.7792e+02f, 5.3446e+02f,
         7.5583e+02f, 1.0689e+03f, 1.5117e+03f, 2.1378e+03f, 3.0233e+03f, 4.2756e+03f, 6.0467e+03f, 8.5513e+03f, 1.2093e+04f,
         1.7103e+04f, 2.4187e+04f, 3.4205e+04f, 4.8373e+04f, 6.8410e+04f, 9.6747e+04f, 1.3682e+05f};
-    const float base_delta = 1.0f / (float)(1u << (prec + (sgnd ? 1 : 0)));
     float gl, gh;
     if (r == 0) { gl = L97[nd]; gh = gl; }
     else { const uint32_t d = nd - r; gl = orient == 3 ? H97[d] : L97[d + 1]; gh = H97[d]; }
-    float delta_b = base_delta / (gl * gh);
+    return gl * gh;
+}
+
+// HT irreversible QCD: param_qcd::set_irrev_quant (HTParams.cpp:273-317), base_delta =
+// 2^-(bit depth + signed) (:211-212) unless the caller chose a base step (qstep > 0,
+// gk_set_encode_quant), divided by the band's synthesis gain.
+static void ht_irrev_quant(uint32_t prec, bool sgnd, uint32_t nd, uint32_t r, uint32_t orient, double qstep,
+                           uint32_t& expn, uint32_t& mant) {
+    const float base_delta = qstep > 0.0 ? (float)qstep : 1.0f / (float)(1u << (prec + (sgnd ? 1 : 0)));
+    float delta_b = base_delta / ht97_gain(nd, r, orient);
     uint32_t e = 0;
     while (delta_b < 1.0f) { e++; delta_b *= 2.0f; }
     const uint32_t m = (uint32_t)round(delta_b * (float)(1 << 11)) - (1 << 11);
@@ -489,7 +499,7 @@ static void band_quant(const Plan& P, uint32_t ci, uint32_t nres, uint32_t r, Ba
     }
     uint32_t gain = irrev ? 0 : (B.orient == 0 ? 0 : (B.orient == 3 ? 2 : 1));
     if (ht) {
-        ht_irrev_quant(P.prec, P.sgnd != 0, nres - 1, r, B.orient, B.expn, B.mant);
+        ht_irrev_quant(P.prec, P.sgnd != 0, nres - 1, r, B.orient, P.p.qstep, B.expn, B.mant);
     } else {
         // Part-1 QCD generation (HTParams.cpp:216-251)
         double stepsize = 1.0;
@@ -506,6 +516,16 @@ static void band_quant(const Plan& P, uint32_t ci, uint32_t nres, uint32_t r, Ba
     B.step_dec = (float)((1.0 + B.mant / 2048.0) * pow(2.0, (int)(P.prec + lg_dec) - (int)B.expn));
     int v = (int)B.expn + (int)P.p.numgbits - 1;
     B.numbps = P.p.roi(ci) + (uint32_t)std::max(0, v);   // Quantizer.cpp:47: roishift + ...
+}
+
+// The notch ladder of gk_set_encode_quant: notch n has the base step 2^-(prec + sgnd) * 2^(n / 8),
+// n = 0 .. 8 * (prec - 1).  At the top every band's step is still below 1 before normalisation
+// (gains are >= 1), so every exponent stays >= 1 and no band loses its last bit-plane.
+static uint32_t quant_notches(uint32_t prec) { return 8 * (prec - 1) + 1; }
+static double quant_ladder(uint32_t prec, bool sgnd, uint32_t n) {
+    static const double frac[8] = {1.0, 1.0905077326652577, 1.189207115002721, 1.2968395546510096,
+                                   1.4142135623730951, 1.5422108254079407, 1.681792830507429, 1.8340080864093424};
+    return ldexp(frac[n & 7], (int)(n >> 3) - (int)(prec + (sgnd ? 1 : 0)));
 }
 
 static void assign_steps_tile(Plan& P, TileG& T) {
@@ -648,6 +668,16 @@ static void parse_quant(const std::vector<uint8_t>& b, uint32_t numres, QuantLis
     }
 }
 
+// T1::getwmsedec weight w1 * w2 * stepsize of a band's blocks (T1.cpp:418-436): w1 = MCT basis norm
+// (mct.cpp:689-704) when the MCT is on, w2 = DWT band norm (T1.cpp:264-277)
+static double block_wmse(const Plan& P, uint32_t c, uint32_t nres, uint32_t r, const BandG& B) {
+    static const double norms_irrev[3] = {1.732, 1.805, 1.573};
+    static const double norms_rev[3] = {1.732, .8292, .8292};
+    const uint32_t irrev = P.p.c_irrev(c);
+    const double w1 = (P.mct3() && c < 3) ? (irrev ? norms_irrev[c] : norms_rev[c]) : 1.0;
+    return w1 * band_norm(nres - 1 - r, B.orient, !irrev) * (double)B.step_enc;
+}
+
 static void build_tile(Plan& P, TileG& T, uint32_t t) {
     T.comps.assign(P.nc, CompG());
     T.b0 = (uint32_t)P.blocks.size();
@@ -749,13 +779,7 @@ static void build_tile(Plan& P, TileG& T, uint32_t t) {
                         G.step = B.step_enc;
                         // T1::getwmsedec weight w1 * w2 * stepsize (T1.cpp:418-436): w1 = MCT basis norm
                         // (mct.cpp:689-704) when the MCT is on, w2 = DWT band norm (T1.cpp:264-277)
-                        {
-                            static const double norms_irrev[3] = {1.732, 1.805, 1.573};
-                            static const double norms_rev[3] = {1.732, .8292, .8292};
-                            const bool mct = P.mct3();
-                            double w1 = (mct && c < 3) ? (irrev ? norms_irrev[c] : norms_rev[c]) : 1.0;
-                            G.wmse = w1 * band_norm(nres - 1 - r, B.orient, !irrev) * (double)B.step_enc;
-                        }
+                        G.wmse = block_wmse(P, c, nres, r, B);
                         P.blocks.push_back(G);
                         P.bxy.push_back(x0); P.bxy.push_back(y0);
                     }
@@ -3482,6 +3506,9 @@ struct HostBuf {
     ~HostBuf() { if (p) (void)hipHostFree(p); }
 };
 
+// gk_set_encode_quant's setting, copied in (mode 0: none)
+struct EncQuant { uint32_t mode = 0; double value = 0.0; };
+
 struct gk_ctx {
     uint32_t dec_layers = 0;   // quality layers to decode (0 = all; grk_dparameters::cp_layer)
     bool dec_colour = true;    // JP2 colour boxes (pclr + cmap, cdef): applied on decode (gk_set_decode_colour)
@@ -3537,6 +3564,11 @@ struct gk_ctx {
     DevBuf droi_rects, droi_mask;          // its rectangles (4 u32 each) and its mask (mask_w bytes per row), uploaded when set
     DevBuf droi;                           // the coefficient masks of the encode in progress: two byte planes
     hipEvent_t roi_ev[2] = {nullptr, nullptr};
+    EncQuant enc_quant;                    // gk_set_encode_quant: sticky, read by the encode entry points, never written by an encode
+    gk_quant_result quant_res{};           // gk_get_encode_quant: the last encode's
+    double plan_qstep = 0.0;               // the base step the cached plan's bands and blocks carry (Params::qstep)
+    DevBuf dq_tab, dq_partial, dq_out;     // k_htq_dist / k_htq_len: work lists and step tables, partials, results
+    HostBuf hq_out;
     std::vector<uint32_t> hdr_dx, hdr_dy, hdr_prec, hdr_sgnd;   // the last gk_decode_header's components
     bool enc_rc = false;                // its rate-control flag (GkBlock::flags bit 1)
     // band quantisation held by the cached plan's bands: the plan's own (encoder, native_qcd)
@@ -3694,12 +3726,49 @@ static void ensure_plan(gk_ctx* ctx, const Plan& want) {
             for (const BandG& B : R.bands) ctx->native_qcd.push_back({B.expn, B.mant});
     }
     ctx->band_qcd = ctx->native_qcd;
+    ctx->plan_qstep = ctx->plan.p.qstep;
 }
 // Encode uses the plan's own quantisation: undo a decoded stream's QCD if one was applied.
 static void restore_native_qcd(gk_ctx* ctx) {
     if (ctx->band_qcd == ctx->native_qcd) return;
+    const double q = ctx->plan.p.qstep;
+    ctx->plan.p.qstep = ctx->plan_qstep;   // (native_qcd is that of the step the plan carries)
     for (TileG& T : ctx->plan.tiles) assign_steps_tile(ctx->plan, T);
+    ctx->plan.p.qstep = q;
     ctx->band_qcd = ctx->native_qcd;
+}
+// Re-step the cached plan when the call's base step (Params::qstep, gk_set_encode_quant) is not
+// the one it carries: the bands' QCD values, steps and bit-plane counts, the blocks' copies of
+// them and the plan's own QCD list.  Geometry, slots and offsets do not depend on the step.
+static void sync_qstep(gk_ctx* ctx) {
+    Plan& P = ctx->plan;
+    if (ctx->plan_qstep == P.p.qstep) return;
+    for (TileG& T : P.tiles) {
+        assign_steps_tile(P, T);
+        for (uint32_t c = 0; c < P.nc; ++c) {
+            const uint32_t nres = P.p.c_numres(c);
+            for (uint32_t r = 0; r < nres; ++r) {
+                const ResG& R = T.comps[c].res[r];
+                for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
+                    for (const PrecG& PG : R.prc[bi])
+                        for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
+                            GkBlock& G = P.blocks[PG.first_block + k];
+                            G.band_numbps = (uint8_t)R.bands[bi].numbps;
+                            G.step = R.bands[bi].step_enc;
+                            G.wmse = block_wmse(P, c, nres, r, R.bands[bi]);
+                        }
+            }
+        }
+    }
+    ctx->native_qcd.clear();
+    for (const CompG& C : P.tiles[0].comps) {
+        ctx->native_qcd.push_back({P.p.numgbits, ~0u});
+        for (const ResG& R : C.res)
+            for (const BandG& B : R.bands) ctx->native_qcd.push_back({B.expn, B.mant});
+    }
+    ctx->band_qcd = ctx->native_qcd;
+    ctx->plan_qstep = P.p.qstep;
+    ctx->blocks_uploaded = false;
 }
 
 // Level 1 fused with the sample stage: the caller's planes (sample type stype) are read by the
@@ -3871,6 +3940,49 @@ static void encode_request(Plan& want, const gk_image_info* info, const gk_cpara
     check_precision(want);
     if (want.w == 0 || want.h == 0) throw GkError("empty image");
 }
+// gk_set_encode_quant's refusals that need no device, and the request's base step.  call: what is
+// asked for (QC_ENCODE: gk_encode / gk_encode_pixels).
+enum QuantCall { QC_ENCODE = 0, QC_TILES, QC_BLOCKS, QC_HEADER };
+static void enc_quant_check(const EncQuant& q) {
+    if (q.mode < GK_QUANT_STEP || q.mode > GK_QUANT_PSNR)
+        throw GkError("quant: unknown mode " + std::to_string(q.mode) + " (GK_QUANT_STEP 1, GK_QUANT_BYTES 2, GK_QUANT_PSNR 3)");
+    if (!(q.value > 0.0) || !std::isfinite(q.value)) throw GkError("quant: the value must be finite and positive");
+}
+static void enc_quant_apply(const EncQuant& q, Plan& want, QuantCall call) {
+    want.p.qstep = 0.0;
+    if (!q.mode) return;
+    enc_quant_check(q);
+    if (!want.p.ht() || !want.p.irrev)
+        throw GkError(std::string("quant: gk_set_encode_quant steers HTJ2K 9/7 encodes only, this one is ") +
+                      (want.p.ht() ? "reversible" : "Part-1") + " (clear the setting for it)");
+    if (want.p.nlayers > 1) throw GkError("quant: numlayers > 1 (an HT block has one pass, so the stream has one layer)");
+    if (want.p.quality) throw GkError("quant: allocationByQuality (the step is the quality knob: use GK_QUANT_PSNR)");
+    for (uint32_t l = 0; l < GK_MAX_LAYERS; ++l)
+        if (want.p.rates[l] > 0.0) throw GkError("quant: layer_rate (it cannot cut an HT block: use GK_QUANT_BYTES)");
+    if (call == QC_BLOCKS) throw GkError("quant: gk_encode_blocks while gk_set_encode_quant is set (clear it)");
+    if (q.mode != GK_QUANT_STEP && call != QC_ENCODE)
+        throw GkError(std::string("quant: GK_QUANT_BYTES / GK_QUANT_PSNR with ") + (call == QC_TILES ? "gk_encode_tiles" : "gk_main_header") +
+                      " (a shard cannot know the other shards' bytes or errors; GK_QUANT_STEP works there)");
+    if (q.mode == GK_QUANT_STEP) {
+        const double lo = quant_ladder(want.prec, want.sgnd != 0, 0);
+        const double hi = quant_ladder(want.prec, want.sgnd != 0, quant_notches(want.prec) - 1);
+        if (q.value < lo * (1.0 - 1e-12) || q.value > hi * (1.0 + 1e-12)) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "quant: step %.9g outside [%.9g, %.9g] (finer than the default 2^-(prec + sgnd) is out of "
+                     "scope; the coarsest notch keeps every band a bit-plane)", q.value, lo, hi);
+            throw GkError(msg);
+        }
+        // (the default step is the constant's own float: the plan without a setting)
+        want.p.qstep = (float)q.value == (float)lo ? 0.0 : std::min(std::max(q.value, lo), hi);
+    }
+}
+// The notch of a base step: the last notch that is not coarser.
+static uint32_t quant_notch_of(uint32_t prec, bool sgnd, double step) {
+    uint32_t n = 0;
+    while (n + 1 < quant_notches(prec) && quant_ladder(prec, sgnd, n + 1) <= step * (1.0 + 1e-12)) ++n;
+    return n;
+}
+
 static void encode_request_tail(Plan& want, const EncRoi* roi) {
     // grk_compress.cpp:981-988 (and A.6.1's xcb, ycb): 4 <= side <= 1024, at most 4096 samples
     if (want.p.cbw < 2 || want.p.cbh < 2 || want.p.cbw > 10 || want.p.cbh > 10 || want.p.cbw + want.p.cbh > 12)
@@ -3882,7 +3994,8 @@ static void encode_request_tail(Plan& want, const EncRoi* roi) {
 // lengths in part_lens (tile sharding across devices).
 // cv: the call converts R, G, B to sYCC first (gk_set_encode_convert): its component grids and
 // colour description stand for the engine's.
-static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* cp, const EncConvCall* cv = nullptr) {
+static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* cp, const EncConvCall* cv = nullptr,
+                       QuantCall qc = QC_ENCODE) {
     const std::vector<uint8_t>& enc_dx = cv ? cv->cdx : ctx->enc_dx;
     const std::vector<uint8_t>& enc_dy = cv ? cv->cdy : ctx->enc_dy;
     const EncColour& enc_col = cv ? cv->col : ctx->enc_col;
@@ -3890,9 +4003,12 @@ static void setup_plan(gk_ctx* ctx, const gk_image_info* info, const gk_cparamet
     encode_request(want, info, cp, enc_dx, enc_dy, enc_col.clears_mct());
     // the jp2h contents of this call, built (and a colour description refused) once, here
     if (want.p.jp2) ctx->enc_jp2h = jp2h_content(want, &enc_col);
+    // (the search modes start from the default step: the finest, whose bit-plane counts bound the others')
+    enc_quant_apply(ctx->enc_quant, want, qc);
     encode_request_tail(want, &ctx->enc_roi);
     ensure_plan(ctx, want);
     restore_native_qcd(ctx);
+    sync_qstep(ctx);
     // encode: ROI-scaled indices keep 6 fractional bits below them in a 31-bit magnitude
     // (the decoders take up to 30 band bit-planes, checked where a stream's QCD is applied)
     if (!ctx->plan.p.roishift.empty())
@@ -3928,6 +4044,106 @@ static uint8_t* run_roi_masks(gk_ctx* ctx) {
     HIPCHK(hipEventRecord(ctx->roi_ev[1], st));
     launch_check(__LINE__);
     return m;
+}
+
+// gk_set_encode_quant's distortion estimate: the image-domain MSE an HT 9/7 encode of the float
+// coefficients in the work planes would leave at each of the given base steps (k_htq_dist: the
+// squared quantisation error of every band class at its step for each base step, one pass over
+// the coefficients of tiles [tb, te), blocks [b0, b1) of the uploaded table dblk).  A band's error
+// reaches the image through the 9/7 synthesis, whose energy gain is (gl gh)^2 (ht_irrev_quant's
+// tables), and, for the first three components under the ICT, through the inverse ICT, whose
+// squared column norms weigh Y, Cb and Cr; the decoder's rounding to integers adds 1/12.
+static std::vector<double> quant_estimate(gk_ctx* ctx, const int32_t* arena, const GkBlock* dblk, uint32_t tb, uint32_t te,
+                                          uint32_t b0, uint32_t b1, const std::vector<double>& base_steps) {
+    const Plan& P = ctx->plan;
+    hipStream_t st = ctx->st;
+    const uint32_t nbr = b1 - b0, M = (uint32_t)base_steps.size();
+    // band classes: per component (its own resolution count), the bands in QCD order
+    std::vector<uint32_t> cls0(P.nc + 1, 0);
+    for (uint32_t c = 0; c < P.nc; ++c) cls0[c + 1] = cls0[c] + 3 * P.p.c_numres(c) - 2;
+    const uint32_t ncls = cls0[P.nc];
+    std::vector<uint32_t> cls(nbr, 0), cnt(ncls + 1, 0);
+    uint64_t nsamples = 0;
+    for (uint32_t t = tb; t < te; ++t) {
+        const TileG& T = P.tiles[t];
+        for (uint32_t c = 0; c < P.nc; ++c) {
+            const uint32_t nres = P.p.c_numres(c);
+            nsamples += (uint64_t)T.comps[c].res[nres - 1].w * T.comps[c].res[nres - 1].h;
+            for (uint32_t r = 0; r < nres; ++r) {
+                const ResG& R = T.comps[c].res[r];
+                for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
+                    for (const PrecG& PG : R.prc[bi])
+                        for (uint32_t k = 0; k < PG.cw * PG.ch; ++k)
+                            cls[PG.first_block + k - b0] = cls0[c] + (r ? 3 * (r - 1) + 1 + bi : 0);
+            }
+        }
+    }
+    // blocks by class (in block order within one), cut into work items
+    for (uint32_t i = 0; i < nbr; ++i) cnt[cls[i] + 1]++;
+    for (uint32_t k = 0; k < ncls; ++k) cnt[k + 1] += cnt[k];
+    std::vector<uint32_t> order(nbr), at(cnt.begin(), cnt.end() - 1), cls_first(ncls + 1, 0);
+    for (uint32_t i = 0; i < nbr; ++i) order[at[cls[i]]++] = i;
+    std::vector<GkHtqItem> items;
+    for (uint32_t k = 0; k < ncls; ++k) {
+        cls_first[k] = (uint32_t)items.size();
+        for (uint32_t f = cnt[k]; f < cnt[k + 1]; f += GK_HTQ_ITEM_BLOCKS)
+            items.push_back({f, std::min((uint32_t)GK_HTQ_ITEM_BLOCKS, cnt[k + 1] - f), k, 0});
+    }
+    cls_first[ncls] = (uint32_t)items.size();
+    // each class's quantiser step at each base step (what band_quant gives the encoder), and its weight
+    std::vector<float> steps((size_t)ncls * M);
+    std::vector<double> weight(ncls);
+    Plan Q;
+    Q.prec = P.prec; Q.sgnd = P.sgnd; Q.nc = P.nc; Q.p = P.p; Q.p.roishift.clear();
+    static const double ict[3] = {3.0, 0.34413 * 0.34413 + 1.772 * 1.772, 1.402 * 1.402 + 0.71414 * 0.71414};
+    for (uint32_t c = 0; c < P.nc; ++c)
+        for (uint32_t r = 0, nres = P.p.c_numres(c); r < nres; ++r)
+            for (uint32_t bi = 0; bi < (r ? 3u : 1u); ++bi) {
+                const uint32_t k = cls0[c] + (r ? 3 * (r - 1) + 1 + bi : 0);
+                BandG B{};
+                B.orient = r ? bi + 1 : 0;
+                for (uint32_t m = 0; m < M; ++m) {
+                    Q.p.qstep = base_steps[m];
+                    band_quant(Q, c, nres, r, B);
+                    steps[(size_t)k * M + m] = B.step_enc;
+                }
+                // (the encoder's coefficients carry their band's nominal gain, step_enc = 2^gain *
+                // step_dec in Quantizer::setBandStepSizeAndBps: an error there is that much smaller
+                // in the coefficients the synthesis starts from)
+                const double g = (double)ht97_gain(nres - 1, r, B.orient) * ((double)B.step_dec / (double)B.step_enc);
+                weight[k] = g * g * ((P.mct3() && c < 3) ? ict[c] : 1.0);
+            }
+    const uint32_t nitems = (uint32_t)items.size();
+    const size_t o_items = align_up((size_t)nbr * 4, 16), o_first = o_items + sizeof(GkHtqItem) * nitems,
+                 o_steps = o_first + 4 * ((size_t)ncls + 1), tab_bytes = o_steps + 4 * steps.size();
+    std::vector<uint8_t> blob(tab_bytes);
+    memcpy(blob.data(), order.data(), (size_t)nbr * 4);
+    memcpy(blob.data() + o_items, items.data(), sizeof(GkHtqItem) * nitems);
+    memcpy(blob.data() + o_first, cls_first.data(), 4 * ((size_t)ncls + 1));
+    memcpy(blob.data() + o_steps, steps.data(), 4 * steps.size());
+    uint8_t* tab = (uint8_t*)ctx->dq_tab.get(tab_bytes);
+    float* partial = (float*)ctx->dq_partial.get(4 * (size_t)nitems * M);
+    double* dsum = (double*)ctx->dq_out.get(8 * (size_t)ncls * M + 64);
+    double* hsum = (double*)ctx->hq_out.get(8 * (size_t)ncls * M + 64);
+    HIPCHK(hipMemcpyAsync(tab, blob.data(), tab_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // (blob is pageable memory of this frame)
+    gk_launch_htq_dist(st, reinterpret_cast<const float*>(arena), dblk, (const uint32_t*)tab, (const GkHtqItem*)(tab + o_items),
+                       nitems, (const float*)(tab + o_steps), M, (const uint32_t*)(tab + o_first), ncls, partial, dsum);
+    launch_check(__LINE__);
+    HIPCHK(hipMemcpyAsync(hsum, dsum, 8 * (size_t)ncls * M, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<double> mse(M);
+    for (uint32_t m = 0; m < M; ++m) {
+        double e = 0.0;
+        for (uint32_t k = 0; k < ncls; ++k) e += weight[k] * hsum[(size_t)k * M + m];
+        mse[m] = e / (double)std::max<uint64_t>(nsamples, 1) + 1.0 / 12.0;
+    }
+    ctx->quant_res.stats_passes++;
+    return mse;
+}
+static double quant_psnr(uint32_t prec, double mse) {
+    const double peak = ldexp(1.0, (int)prec) - 1.0;
+    return 10.0 * log10(peak * peak / mse);
 }
 
 // gk_encode_blocks: the T1 results of the (single) tile in canonical order, the block bytes
@@ -4094,8 +4310,13 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
                           const EncConvCall* cv = nullptr, const Xcode* xc = nullptr) {
     // xc (a transcode): the plan is the target's and work plane A holds the source's quantisation
     // indices; the call starts at T1 and writes the header the transcode keeps
-    if (!xc) setup_plan(ctx, info, cp, cv);
+    if (!xc) setup_plan(ctx, info, cp, cv, blocks_only ? QC_BLOCKS : part_lens ? QC_TILES : QC_ENCODE);
     Plan& P = ctx->plan;
+    // gk_set_encode_quant (a transcode keeps its source's QCD): STEP is in the plan already
+    const EncQuant quant = xc ? EncQuant() : ctx->enc_quant;
+    gk_quant_result& qres = ctx->quant_res;
+    qres = gk_quant_result();
+    qres.mode = quant.mode;
     const uint32_t ntiles = (uint32_t)P.tiles.size();
     if (te == 0) { tb = 0; te = ntiles; }
     if (tb >= te || te > ntiles) throw GkError("bad tile range");
@@ -4285,7 +4506,8 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
     uint32_t* dpe = (uint32_t*)ctx->dpassend.get(4 * GK_MAX_PASSES * (size_t)nbx);
     uint32_t* dcm = (uint32_t*)ctx->dcminfo.get(8 * (size_t)nbx);
     int32_t* dnmse = do_rc ? (int32_t*)ctx->dnmse.get(4 * GK_MAX_PASSES * (size_t)nbx) : nullptr;
-    if (xc || !ctx->blocks_uploaded || ctx->enc_b0 != b0 || ctx->enc_b1 != b1 || ctx->enc_rc != do_rc) {
+    auto upload_blocks = [&]() {
+        if (!xc && ctx->blocks_uploaded && ctx->enc_b0 == b0 && ctx->enc_b1 == b1 && ctx->enc_rc == do_rc) return;
         // the range's blocks with offsets into this call's planes and slots
         GkBlock* hb = (GkBlock*)ctx->hpasses.get(sizeof(GkBlock) * nbx + 8 * ((size_t)nbr + 1));
         uint64_t* hso = (uint64_t*)(hb + nbx);
@@ -4302,17 +4524,93 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
         HIPCHK(hipMemcpyAsync(dsymoff, hso, 8 * ((size_t)nbr + 1), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));   // the staging buffer is reused below
         ctx->blocks_uploaded = !xc; ctx->enc_b0 = b0; ctx->enc_b1 = b1; ctx->enc_rc = do_rc;
-    }
+    };
+    upload_blocks();
     HIPCHK(hipMemsetAsync(derr, 0, 64, st));
     // solo MQ waves (gk_t1enc.hip mq_solo_block): GK_T1ENC_SOLO = how many of the heaviest blocks
     // of the first chunk they code (without chunks: the first blocks in index order; tests)
     const uint32_t nsolo_env = []() { const char* v = getenv("GK_T1ENC_SOLO"); return v ? (uint32_t)atoi(v) : 0u; }();
-    if (P.p.ht()) {
-        // HT cleanup pass (T1HT::compress, T1HT.cpp:109-133); MEL bytes staged in the symbol buffer
-        uint8_t* mel = (uint8_t*)ctx->dsym.get((size_t)nbx * GK_HT_MEL_CAP + 256);
+    // HT cleanup pass (T1HT::compress, T1HT.cpp:109-133); MEL bytes staged in the symbol buffer
+    uint8_t* const mel = P.p.ht() ? (uint8_t*)ctx->dsym.get((size_t)nbx * GK_HT_MEL_CAP + 256) : nullptr;
+    auto ht_pass = [&]() {
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[8], st));
         gk_launch_ht_enc(st, arena, dblk, dbytes, mel, GK_HT_MEL_CAP, dinfo, nbr, derr, P.p.wide(), xc != nullptr, roi, roi_mod);
+        qres.t1_passes++;
+    };
+    // ---- gk_set_encode_quant's search modes: the coefficients stay in the work planes, only the
+    // step of the quantise-and-code pass moves.  Notch 0 is the default step (Params::qstep 0).
+    const uint32_t q_top = quant_notches(P.prec) - 1;
+    uint32_t q_notch = 0;
+    uint64_t q_target = 0;
+    bool q_have_pass = false;   // the pass of q_notch has run already (the search's last probe)
+    auto q_step_to = [&](uint32_t n) {
+        P.p.qstep = n ? quant_ladder(P.prec, P.sgnd != 0, n) : 0.0;
+        sync_qstep(ctx);
+        upload_blocks();
+    };
+    std::vector<double> q_mse;   // the estimated MSE of every notch (PSNR mode) or of the step in use and the next notch
+    if (quant.mode == GK_QUANT_PSNR) {
+        // one statistics pass over the whole ladder, then the coarsest notch that reaches the target
+        std::vector<double> ladder(q_top + 1);
+        for (uint32_t n = 0; n <= q_top; ++n) ladder[n] = quant_ladder(P.prec, P.sgnd != 0, n);
+        q_mse = quant_estimate(ctx, arena, dblk, tb, te, b0, b1, ladder);
+        for (q_notch = q_top; q_notch > 0 && quant_psnr(P.prec, q_mse[q_notch]) < quant.value;) --q_notch;
+        q_step_to(q_notch);
+    } else if (quant.mode == GK_QUANT_BYTES) {
+        // Bisect the ladder on the stream length.  A probe's length is the pass's bytes and a lower
+        // bound of its packet-header bits, summed on the device (k_htq_len: the host reads two
+        // numbers), plus the bytes every stream of this plan has: "overshoots" is therefore always
+        // true of the real stream, "fits" is confirmed on the exact length after T2 below.  The
+        // invariant: notch lo overshoots, notch hi fits; lo = -1 and hi = top + 1 stand for "finer
+        // than the ladder" and "refused", so the search ends on an adjacent pair after at most
+        // ceil(log2(notches + 1)) passes whether or not the length is monotone in the step.
+        q_target = quant.value >= 1.8e19 ? ~0ull : (uint64_t)quant.value;
+        std::vector<uint8_t> H0;
+        write_main_header(H0, P);
+        uint64_t fixed = H0.size() + (P.p.jp2 ? jp2_prefix_size(P, ctx->enc_jp2h) : 0) + 2 + 14ull * (te - tb);
+        if (P.p.plt)   // a PLT per tile: its 5 bytes and at least one per packet
+            for (uint32_t t = tb; t < te; ++t) {
+                fixed += 5;
+                for (uint32_t c = 0; c < P.nc; ++c)
+                    for (const ResG& R : P.tiles[t].comps[c].res) fixed += (uint64_t)R.pw * R.ph;
+            }
+        uint64_t* dpart = (uint64_t*)ctx->dq_partial.get(16 * (size_t)gk_htq_len_partials(nbr) + 16);
+        uint64_t* dlen = (uint64_t*)ctx->dq_out.get(64);
+        uint64_t* hlen = (uint64_t*)ctx->hq_out.get(64);
+        uint64_t over = 0;   // the coarsest overshooting probe's length
+        int64_t lo = -1, hi = (int64_t)q_top + 1, last = -1;
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            q_step_to((uint32_t)mid);
+            ht_pass();
+            gk_launch_htq_len(st, dinfo, nbr, dpart, dlen);
+            HIPCHK(hipMemcpyAsync(hlen, dlen, 16, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            const uint64_t est = fixed + hlen[0] + hlen[1] / 8;
+            last = mid;
+            if (est > q_target) { lo = mid; over = est; } else hi = mid;
+        }
+        if (hi > (int64_t)q_top)
+            throw GkError("quant: max_bytes " + std::to_string(q_target) + " is below what the coarsest notch (" +
+                          std::to_string(q_top) + ") still needs, at least " + std::to_string(over) + " bytes");
+        q_notch = (uint32_t)hi;
+        q_have_pass = last == hi;
+        if (!q_have_pass) q_step_to(q_notch);
+    }
+quant_retry:
+    if (P.p.ht()) {
+        if (!q_have_pass) ht_pass();
+        if (quant.mode == GK_QUANT_STEP || quant.mode == GK_QUANT_BYTES) {
+            // the estimates of the step in use and of the next coarser notch, for the result: queued
+            // behind the pass, so their read-back is the wait for the pass the T2 fetch below needs anyway
+            const bool sg = P.sgnd != 0;
+            const double step = P.p.qstep > 0.0 ? P.p.qstep : quant_ladder(P.prec, sg, 0);
+            if (quant.mode == GK_QUANT_STEP) q_notch = quant_notch_of(P.prec, sg, step);
+            std::vector<double> two(1, step);
+            if (q_notch < q_top) two.push_back(quant_ladder(P.prec, sg, q_notch + 1));
+            q_mse = quant_estimate(ctx, arena, dblk, tb, te, b0, b1, two);
+        }
     } else if (P.p.t1_generic()) {
         // mode switches: lane-per-block coder with per-pass termination rules (gk_t1ms.hip)
         uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(nbx));
@@ -4786,6 +5084,27 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
         add_host(xc->suffix.data(), xc->suffix.size());
     }
     const size_t total = pos;
+    if (quant.mode == GK_QUANT_BYTES && total > q_target) {
+        // the exact length is over the target (the probe's header bits were a lower bound): this
+        // notch overshoots too, so the next coarser one is coded and measured the same way
+        if (q_notch >= q_top)
+            throw GkError("quant: max_bytes " + std::to_string(q_target) + " is below what the coarsest notch (" +
+                          std::to_string(q_top) + ") still needs, " + std::to_string(total) + " bytes");
+        q_step_to(++q_notch);
+        q_have_pass = false;
+        goto quant_retry;
+    }
+    if (quant.mode) {
+        // the result: the step used and the estimates for it and for the next coarser notch (PSNR
+        // mode holds the whole ladder's, the other modes the two steps')
+        const size_t at = quant.mode == GK_QUANT_PSNR ? q_notch : 0;
+        qres.notch = q_notch;
+        qres.base_step = P.p.qstep > 0.0 ? P.p.qstep : quant_ladder(P.prec, P.sgnd != 0, 0);
+        qres.est_mse = q_mse[at];
+        qres.est_psnr = quant_psnr(P.prec, q_mse[at]);
+        qres.est_psnr_next = at + 1 < q_mse.size() ? quant_psnr(P.prec, q_mse[at + 1]) : 0.0;
+        qres.bytes = total;
+    }
     if (jp2) {
         const size_t prefix = J.size();
         J.clear();
@@ -7387,7 +7706,7 @@ int gk_main_header(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters*
         refuse_under_convert(ctx, "gk_main_header");
         if (ctx->enc_roi.set)
             throw GkError("roi: gk_main_header while gk_set_encode_roi is set (whole images only: use gk_encode / gk_encode_pixels, or clear it)");
-        setup_plan(ctx, info, p);
+        setup_plan(ctx, info, p, nullptr, QC_HEADER);
         std::vector<uint8_t> H;
         size_t tlm = 0;
         write_main_header(H, ctx->plan, &tlm);
@@ -7652,6 +7971,72 @@ int gk_probe_encode_roi(const gk_image_info* info, const gk_cparameters* params,
         encode_request_tail(want, &R);
         if (shift_out)
             for (uint32_t c = 0; c < want.nc; ++c) shift_out[c] = want.p.roi(c);
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
+        return -1;
+    }
+}
+
+int gk_set_encode_quant(gk_ctx* ctx, const gk_encode_quant* quant) {
+    if (!ctx) return -1;
+    ctx->enc_quant = EncQuant();   // (cleared first: a refused setting leaves none)
+    if (!quant) return 0;
+    try {
+        EncQuant q;
+        q.mode = quant->mode; q.value = quant->value;
+        enc_quant_check(q);
+        ctx->enc_quant = q;
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_get_encode_quant(gk_ctx* ctx, gk_quant_result* result) {
+    if (!ctx || !result) return -1;
+    *result = ctx->quant_res;
+    return 0;
+}
+
+int gk_probe_encode_quant(const gk_image_info* info, const gk_cparameters* params, const gk_encode_quant* quant,
+                          double* step_min, double* step_max, uint32_t* notches, char* msg, size_t msg_cap) {
+    if (msg && msg_cap) msg[0] = 0;
+    try {
+        if (!info) throw GkError("quant: no image description");
+        Plan want;
+        const std::vector<uint8_t> none;
+        encode_request(want, info, params, none, none, false);
+        if (quant) {
+            EncQuant q;
+            q.mode = quant->mode & 0xffu; q.value = quant->value;
+            const uint32_t f = quant->mode & ~0xffu;
+            if (f & ~(GK_QUANT_FOR_TILES | GK_QUANT_FOR_BLOCKS)) throw GkError("quant: unknown mode " + std::to_string(quant->mode));
+            enc_quant_check(q);
+            enc_quant_apply(q, want, (f & GK_QUANT_FOR_BLOCKS) ? QC_BLOCKS : (f & GK_QUANT_FOR_TILES) ? QC_TILES : QC_ENCODE);
+            encode_request_tail(want, nullptr);
+            if (q.mode == GK_QUANT_BYTES) {
+                // what every stream of this request holds whatever its step: the main header, the
+                // JP2 boxes, SOT + SOD per tile, a byte per packet, EOC
+                EncColour col;
+                const std::vector<uint8_t> jp2h = want.p.jp2 ? jp2h_content(want, &col) : std::vector<uint8_t>();
+                build_plan(want);
+                std::vector<uint8_t> H;
+                write_main_header(H, want);
+                uint64_t need = H.size() + (want.p.jp2 ? jp2_prefix_size(want, jp2h) : 0) + 2 + 14ull * want.tiles.size();
+                for (const TileG& T : want.tiles)
+                    for (uint32_t c = 0; c < want.nc; ++c)
+                        for (const ResG& R : T.comps[c].res) need += (uint64_t)R.pw * R.ph * (want.p.plt ? 2 : 1);
+                if (q.value < (double)need)
+                    throw GkError("quant: max_bytes " + std::to_string((uint64_t)q.value) + " is below what the coarsest notch (" +
+                                  std::to_string(quant_notches(want.prec) - 1) + ") still needs, at least " + std::to_string(need) +
+                                  " bytes of headers");
+            }
+        }
+        if (step_min) *step_min = quant_ladder(want.prec, want.sgnd != 0, 0);
+        if (step_max) *step_max = quant_ladder(want.prec, want.sgnd != 0, quant_notches(want.prec) - 1);
+        if (notches) *notches = quant_notches(want.prec);
         return 0;
     } catch (const GkError& e) {
         if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());

@@ -111,6 +111,22 @@ void gk_launch_ht_enc(hipStream_t st, const int32_t* coef, const GkBlock* blocks
                       const uint8_t* roi = nullptr, uint64_t roi_mod = 0);
 void gk_launch_ht_dec(hipStream_t st, const uint8_t* bytes, const GkBlock* blocks, const uint32_t* ids, int32_t* coef,
                       uint32_t nblocks, int* err, bool wide = false, bool index = false);
+// HT 9/7 quantisation control (gk_htq.hip).  k_htq_dist: for every work item (count blocks of one
+// band class, order[first ..)) and each of the class's nsteps steps (steps[cls * nsteps + n]) the
+// squared quantisation error of its float coefficients, GK_HTQ_RUNGS steps per launch; one float
+// partial per item and step, added per class in item order into out[cls * nsteps + n] (double).
+// cls_first[cls] .. cls_first[cls + 1]: the class's items.
+#define GK_HTQ_RUNGS 32
+#define GK_HTQ_ITEM_BLOCKS 8   // blocks per work item at most (the host's split)
+struct GkHtqItem { uint32_t first, count, cls, pad; };
+void gk_launch_htq_dist(hipStream_t st, const float* coef, const GkBlock* blocks, const uint32_t* order,
+                        const GkHtqItem* items, uint32_t nitems, const float* steps, uint32_t nsteps,
+                        const uint32_t* cls_first, uint32_t ncls, float* partial, double* out);
+// k_htq_len: out[0] = the bytes of the nblocks code-blocks of an HT pass (info[4 i + 2]), out[1] = a
+// lower bound of their packet-header bits; partial: 2 * gk_htq_len_partials(nblocks) words
+#define GK_HTQ_LEN_PER 4
+uint32_t gk_htq_len_partials(uint32_t nblocks);
+void gk_launch_htq_len(hipStream_t st, const uint32_t* info, uint32_t nblocks, uint64_t* partial, uint64_t* out);
 // JP2 palette expansion (gk_colour.hip).  One output channel: palette column `col` of the launch's
 // index plane, or (direct) a copy of the component plane `src`.
 struct GkPalChan {

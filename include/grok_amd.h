@@ -323,6 +323,66 @@ int gk_roi_band_mask(gk_ctx* ctx, const gk_image_info* info, const gk_cparameter
                      uint32_t resolution, uint32_t band, uint8_t* out, size_t cap, uint32_t* w, uint32_t* h,
                      int out_on_device);
 
+/* The quantisation step of HTJ2K 9/7 encodes: to a chosen step, size or PSNR.  An HT block has one
+ * pass, so its step is the only rate knob (layer_rate cannot cut a block); Grok's encoder has one
+ * operating point, base step 2^-(prec + sgnd) (HTParams.cpp:211-212), and no option to move it
+ * (OpenJPH has -qstep, Kakadu Qstep and -rate).  Band b is quantised with base_step / (gl gh), its
+ * 9/7 synthesis gain, exactly as Grok derives its own steps; the QCD is scalar expounded and holds
+ * the (exponent, mantissa) pair of every band, and the encoder quantises with the step that pair
+ * represents, so any decoder reconstructs on the encoder's grid.
+ * The ladder: notch n has base_step = 2^-(prec + sgnd) * 2^(n / 8), n = 0 .. 8 (prec - 1); at its top
+ * every band still has an exponent >= 1, i.e. a bit-plane.
+ * GK_QUANT_STEP: a plain encode with that base step, anywhere in [step(0), step(top)] (at step(0)
+ * the stream is byte for byte the one without a setting).
+ * GK_QUANT_BYTES: the finest notch whose stream (the .jp2 file when one is written) is at most
+ * value bytes: MCT and DWT run once, the HT pass alone repeats, bisecting the ladder with the
+ * pass's length summed on the device (k_htq_len).  Passes: ceil(log2(notches + 1)) probes, one
+ * more when the last probe was not the chosen notch, and one per exact-length correction (the
+ * probes count a lower bound of the packet headers; the final length is checked exactly and a
+ * notch that is over moves one coarser).  That is 2 + ceil(log2(notches)) with at most one
+ * correction, what the tests hold it to; 6 to 8 were measured, gk_quant_result says how many.
+ * GK_QUANT_PSNR: one pass over the float coefficients (k_htq_dist) gives the squared quantisation
+ * error of every band at every notch; weighted by the bands' energy gains (and the inverse ICT's
+ * column norms), plus 1/12 for the decoder's rounding, it estimates the image-domain MSE; the
+ * coarsest notch whose estimate reaches value dB against the source samples is encoded, once.
+ * Refused, each by name, by the encode (before anything is allocated or launched) and by
+ * gk_probe_encode_quant alike: a mode other than the three, a value that is not finite and
+ * positive; a Part-1 or a reversible encode while a setting is held; numlayers > 1, layer_rate or
+ * allocationByQuality with it; a step outside the ladder's range (finer than the default is out of
+ * scope: DESIGN.md §7); GK_QUANT_BYTES / GK_QUANT_PSNR with gk_encode_tiles or gk_main_header (a
+ * shard cannot know the other shards' bytes; GK_QUANT_STEP works there); gk_encode_blocks; a byte
+ * target that the coarsest notch still exceeds (the probe knows the headers' share alone).
+ * Composes with tiles, TLM / PLT, JP2 and its colour boxes, gk_encode_pixels,
+ * gk_set_encode_convert and gk_set_encode_roi.  gk_transcode keeps a QCD as it is. */
+#define GK_QUANT_STEP  1u  /* value = base step, nominal-range units (the default is 2^-(prec+sgnd)) */
+#define GK_QUANT_BYTES 2u  /* value = largest output length in bytes (codestream, or the whole .jp2 file) */
+#define GK_QUANT_PSNR  3u  /* value = PSNR in dB against the source samples */
+/* gk_probe_encode_quant only, or-ed into mode: answer for gk_encode_tiles / gk_encode_blocks */
+#define GK_QUANT_FOR_TILES  0x100u
+#define GK_QUANT_FOR_BLOCKS 0x200u
+typedef struct gk_encode_quant { uint32_t mode; double value; } gk_encode_quant;
+/* Sticky; quant = NULL clears it: every call is then byte for byte as without.  A refused setting
+ * leaves none.  No encode changes it, and no result depends on what the engine encoded before. */
+int gk_set_encode_quant(gk_ctx* ctx, const gk_encode_quant* quant);
+/* What an encode of `info` under `params` and `quant` would answer, no engine or device needed:
+ * 0 and the ladder's ends *step_min = step(0), *step_max = step(top) and its length *notches (any
+ * may be NULL; quant may be NULL to ask for the ladder alone); -1 with the refusal in msg. */
+int gk_probe_encode_quant(const gk_image_info* info, const gk_cparameters* params, const gk_encode_quant* quant,
+                          double* step_min, double* step_max, uint32_t* notches, char* msg, size_t msg_cap);
+typedef struct gk_quant_result {
+    uint32_t mode, notch;    /* the setting's mode (0: none was set); the notch used (STEP: the last one not coarser) */
+    uint32_t t1_passes;      /* HT encode passes the call ran (1 in STEP mode) */
+    uint32_t stats_passes;   /* k_htq_dist passes over the coefficients (ladder launches counted once); with the
+                                search's passes they are part of gk_timings::t1_ms */
+    double base_step;        /* the step used */
+    double est_mse;          /* estimate for the chosen step */
+    double est_psnr;         /* estimate for the chosen step */
+    double est_psnr_next;    /* estimate for the next coarser notch (0 at the top of the ladder) */
+    uint64_t bytes;          /* output length */
+} gk_quant_result;
+/* Of the last gk_encode / gk_encode_pixels / gk_encode_tiles (zeros after one without a setting). */
+int gk_get_encode_quant(gk_ctx* ctx, gk_quant_result* result);
+
 /* grk_decompress_read_header (grok.cpp:287-297, CodeStreamDecompress::readHeader) of a raw
  * codestream or a JP2 file (its jp2c box; FileFormatDecompress::read_box_hdr :632-672). */
 int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, gk_image_info* info);
