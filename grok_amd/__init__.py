@@ -31,7 +31,8 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_set_encode_colour", "gk_jp2_boxes", "gk_header_cielab", "gk_probe_cielab",
            "gk_set_encode_convert", "gk_probe_encode_convert", "gk_set_default_transcode", "gk_transcode",
            "gk_probe_transcode", "gk_set_encode_roi", "gk_probe_encode_roi", "gk_roi_band_mask",
-           "gk_set_encode_quant", "gk_probe_encode_quant", "gk_get_encode_quant")
+           "gk_set_encode_quant", "gk_probe_encode_quant", "gk_get_encode_quant", "gk_probe_view",
+           "gk_decode_view_pixels")
 GK_QUANT_STEP, GK_QUANT_BYTES, GK_QUANT_PSNR = 1, 2, 3   # gk_encode_quant::mode
 GK_QUANT_FOR_TILES, GK_QUANT_FOR_BLOCKS = 0x100, 0x200   # gk_probe_encode_quant: the call asked about
 GK_TRANSCODE_HT, GK_TRANSCODE_PART1 = 1, 2   # gk_transcode_params::target
@@ -70,6 +71,132 @@ def parse_precision(spec):
             raise ValueError("precision entry (%r, %r): expected (prec, 'C' | 'S')" % (prec, mode))
         out.append((int(prec), mode))
     return out
+
+
+class View(ctypes.Structure):
+    """gk_view (include/grok_amd.h): a region, its output size and its orientation."""
+    _fields_ = [("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32), ("x1", ctypes.c_uint32), ("y1", ctypes.c_uint32),
+                ("out_w", ctypes.c_uint32), ("out_h", ctypes.c_uint32), ("fit", ctypes.c_uint32),
+                ("rotate", ctypes.c_uint32), ("mirror", ctypes.c_uint32)]
+
+
+class ViewResult(ctypes.Structure):
+    """gk_view_result: what a view resolved to."""
+    _fields_ = [("reduce", ctypes.c_uint32), ("rx0", ctypes.c_uint32), ("ry0", ctypes.c_uint32),
+                ("rx1", ctypes.c_uint32), ("ry1", ctypes.c_uint32), ("out_w", ctypes.c_uint32),
+                ("out_h", ctypes.c_uint32), ("pix_w", ctypes.c_uint32), ("pix_h", ctypes.c_uint32),
+                ("channels", ctypes.c_uint32), ("prec", ctypes.c_uint32), ("sgnd", ctypes.c_uint32)]
+
+    def __repr__(self):
+        return "ViewResult(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+def _view(region, size, width, height, fit, rotate, mirror):
+    """The gk_view of decode_view's / probe_view's keyword arguments."""
+    if size is not None:
+        if width is not None or height is not None:
+            raise ValueError("view: give size=(w, h) or width= / height=, not both")
+        width, height = size
+    x0, y0, x1, y1 = region if region is not None else (0, 0, 0, 0)
+    vals = [x0, y0, x1, y1, width or 0, height or 0, int(fit), rotate, int(mirror)]
+    if any(int(v) != v or not 0 <= v < 2 ** 32 for v in vals):
+        raise ValueError("view: every field is an integer in 0 .. 2^32 - 1")
+    return View(*[int(v) for v in vals])
+
+
+def _view_size(w, h, width=None, height=None, fit=False):
+    """gk_view's size rule for a region of w x h: (out_w, out_h) before rotation.  Both given: as
+    they are; one of them: the other keeps the aspect, max(1, (2 a h + w) // (2 w)); fit: the
+    largest size of the region's aspect inside width x height.  The engine's own resolution,
+    which also refuses upscaling, is gk_probe_view's, and Engine.decode_view sizes its array from
+    that; this restatement serves only a codestream in device memory, which cannot be probed."""
+    ow, oh = int(width or 0), int(height or 0)
+    if not ow and not oh:
+        raise ValueError("view: out_w and out_h are both 0")
+    if not oh:
+        oh = max(1, (2 * ow * h + w) // (2 * w))
+    elif not ow:
+        ow = max(1, (2 * oh * w + h) // (2 * h))
+    elif fit:
+        if ow * h <= oh * w:
+            oh = max(1, (2 * ow * h + w) // (2 * w))
+        else:
+            ow = max(1, (2 * oh * w + h) // (2 * h))
+    return ow, oh
+
+
+def parse_iiif(w, h, region="full", size="max", rotation="0"):
+    """IIIF Image API 3.0 region / size / rotation strings for an image of w x h, as the keyword
+    arguments of Engine.decode_view / probe_view (region, width, height, fit, rotate, mirror).
+    region: full | square (centred) | x,y,w,h | pct:x,y,w,h (cut at the image's edges, as the API
+    asks); size: max | w, | ,h | pct:n | w,h | !w,h (!w,h is held to the region's size, as the API
+    asks; every other form above the region's size is upscaling); rotation: 0 | 90 | 180 | 270
+    with an optional leading ! (mirror).  Upscaling (^) and other angles raise ValueError."""
+    from fractions import Fraction
+
+    def numbers(text, n, what, whole):
+        parts = text.split(",")
+        if len(parts) != n:
+            raise ValueError("iiif %s %r: expected %d comma-separated numbers" % (what, text, n))
+        try:
+            vals = [Fraction(p) for p in parts]
+        except (ValueError, ZeroDivisionError):
+            raise ValueError("iiif %s %r: not a number" % (what, text)) from None
+        if any(v < 0 for v in vals) or (whole and any(v.denominator != 1 for v in vals)):
+            raise ValueError("iiif %s %r: expected %s" % (what, text, "whole numbers" if whole else "numbers >= 0"))
+        return vals
+
+    half_up = lambda q: int((2 * q + 1) // 2)
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0:
+        raise ValueError("iiif: an image of %d x %d" % (w, h))
+    if region == "full":
+        box = None
+    elif region == "square":
+        side = min(w, h)
+        box = ((w - side) // 2, (h - side) // 2, (w - side) // 2 + side, (h - side) // 2 + side)
+    else:
+        pct = region.startswith("pct:")
+        x, y, rw, rh = numbers(region[4:] if pct else region, 4, "region", not pct)
+        if pct:
+            x, y, rw, rh = x * w / 100, y * h / 100, rw * w / 100, rh * h / 100
+        box = (half_up(x), half_up(y), min(w, half_up(x + rw)), min(h, half_up(y + rh)))
+        if rw == 0 or rh == 0 or box[0] >= box[2] or box[1] >= box[3]:
+            raise ValueError("iiif region %r: empty, or outside the image of %d x %d" % (region, w, h))
+    bw, bh = (box[2] - box[0], box[3] - box[1]) if box else (w, h)
+    if box == (0, 0, w, h):
+        box = None
+    if "^" in size:
+        raise ValueError("iiif size %r: upscaling (^) is out of scope" % size)
+    fit = False
+    if size == "max":
+        width, height = bw, bh
+    elif size.startswith("pct:"):
+        n, = numbers(size[4:], 1, "size", False)
+        if n > 100:
+            raise ValueError("iiif size %r: upscaling is out of scope" % size)
+        width, height = max(1, half_up(bw * n / 100)), max(1, half_up(bh * n / 100))
+    elif size.startswith("!"):
+        width, height = (int(v) for v in numbers(size[1:], 2, "size", True))
+        width, height, fit = min(width, bw), min(height, bh), True
+    elif size.endswith(",") and size.count(",") == 1:
+        (width,), height = (int(v) for v in numbers(size[:-1], 1, "size", True)), None
+    elif size.startswith(",") and size.count(",") == 1:
+        width, (height,) = None, (int(v) for v in numbers(size[1:], 1, "size", True))
+    else:
+        width, height = (int(v) for v in numbers(size, 2, "size", True))
+    if width == 0 or height == 0:
+        raise ValueError("iiif size %r: a size of 0" % size)
+    if (width or 0) > bw or (height or 0) > bh:
+        raise ValueError("iiif size %r: upscaling of a region of %d x %d is out of scope" % (size, bw, bh))
+    mirror = rotation.startswith("!")
+    try:
+        angle = Fraction(rotation[1:] if mirror else rotation)
+    except (ValueError, ZeroDivisionError):
+        raise ValueError("iiif rotation %r: not a number" % rotation) from None
+    if angle not in (0, 90, 180, 270):
+        raise ValueError("iiif rotation %r: only 0, 90, 180 and 270 are supported" % rotation)
+    return dict(region=box, width=width, height=height, fit=fit, rotate=int(angle), mirror=mirror)
 
 
 def _precision_array(spec):
@@ -529,6 +656,13 @@ def load_library(build_if_missing=True):
     lib.gk_probe_transcode.restype = ctypes.c_int
     lib.gk_probe_transcode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, P(TranscodeParams), ctypes.c_char_p,
                                        ctypes.c_size_t]
+    if hasattr(lib, "gk_probe_view") or not os.environ.get("GROK_AMD_LIB"):   # (as above: an older A side)
+        lib.gk_probe_view.restype = ctypes.c_int
+        lib.gk_probe_view.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, P(Precision), ctypes.c_uint32,
+                                      P(View), P(ViewResult), ctypes.c_char_p, ctypes.c_size_t]
+        lib.gk_decode_view_pixels.restype = ctypes.c_int
+        lib.gk_decode_view_pixels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(View),
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, P(ViewResult)]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -721,6 +855,24 @@ def probe_output(cs, rgb=False, upsample=False, force_rgb=False, precision=None,
     return DisplayInfo(info, colour, [(dx[c], dy[c], pr[c], sg[c]) for c in range(n)], int(reduce))
 
 
+def probe_view(cs, region=None, size=None, width=None, height=None, fit=False, rotate=0, mirror=False, rgb=False,
+               upsample=False, force_rgb=False, icc=False, precision=None):
+    """gk_probe_view: what Engine.decode_view would resolve for host codestream / JP2 bytes under
+    set_decode_display(rgb, upsample, force_rgb, icc) and set_decode_precision(precision), no engine
+    or GPU needed: a ViewResult (reduce, the region on the reduced canvas, out_w x out_h, the written
+    pix_w x pix_h, channels, prec, sgnd).  Raises ValueError with the engine's refusal."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0) | \
+        (GK_DISPLAY_FORCE_RGB if force_rgb else 0) | (GK_DISPLAY_ICC if icc else 0)
+    arr, n = _precision_array(precision)
+    v, res = _view(region, size, width, height, fit, rotate, mirror), ViewResult()
+    msg = ctypes.create_string_buffer(512)
+    if lib.gk_probe_view(b.ctypes.data, len(b), flags, arr, n, ctypes.byref(v), ctypes.byref(res), msg, 512) != 0:
+        raise ValueError(msg.value.decode())
+    return res
+
+
 def probe_components(cs, precision=False):
     """gk_probe_components: [(dx, dy)] per output channel of host codestream / JP2 bytes (SIZ XRsiz /
     YRsiz; the channels a JP2 palette / channel definition makes of the components); with
@@ -788,6 +940,7 @@ class Engine:
         self.ctx = self.lib.gk_create(device)
         if not self.ctx:
             raise RuntimeError("gk_create failed: no HIP device %d" % device)
+        self._display_flags, self._precision = 0, None   # as set_decode_display / set_decode_precision left them
 
     def close(self):
         if self.ctx:
@@ -1238,6 +1391,7 @@ class Engine:
             (GK_DISPLAY_FORCE_RGB if force_rgb else 0) | (GK_DISPLAY_ICC if icc else 0)
         if self.lib.gk_set_decode_display(self.ctx, flags) != 0:
             self._err("gk_set_decode_display")
+        self._display_flags = flags
 
     def set_decode_precision(self, spec):
         """gk_set_decode_precision: force the output channels' precision (grk_decompress -p).
@@ -1248,6 +1402,7 @@ class Engine:
         arr, n = _precision_array(spec)
         if self.lib.gk_set_decode_precision(self.ctx, arr, n) != 0:
             self._err("gk_set_decode_precision")
+        self._precision = parse_precision(spec)
 
     def precisions(self):
         """[(prec, signed)] per output channel of the stream the last read_header / decode read."""
@@ -1294,6 +1449,75 @@ class Engine:
                                                   out_dev)
         if rc != 0:
             self._err("gk_decode_pixels")
+        return res
+
+    def decode_view(self, cs, region=None, size=None, width=None, height=None, fit=False, rotate=0, mirror=False,
+                    out=None, sample_bytes=0, length=None):
+        """gk_decode_view_pixels: region = (x0, y0, x1, y1) of the image (None: all of it) at exactly
+        size = (w, h) pixels, or width= / height= alone (the other keeps the aspect), or both with
+        fit=True (the largest size of the region's aspect inside them); then mirrored left-right
+        and rotated clockwise by rotate = 0 / 90 / 180 / 270 (parse_iiif makes these arguments of
+        IIIF strings).  The engine picks the reduce level, decodes the region there and area-averages
+        it on the GPU (include/grok_amd.h has the exact rule).  Returns a (pix_h, pix_w, C) numpy
+        array (int32, or 8 / 16-bit with sample_bytes 1 / 2), or fills ``out``: a torch cuda tensor of
+        that shape under decode_pixels' stride rules.  Every sticky decode setting is honoured,
+        except that set_decode_reduce must be 0.  The resolved view is kept as self.view_result."""
+        v = _view(region, size, width, height, fit, rotate, mirror)
+        info = self.read_header(cs, length)
+        c = info.numcomps
+        if _is_torch_cuda(cs):
+            src, n, on_dev = ctypes.c_void_p(cs.data_ptr()), length, 1
+        else:
+            b = np.frombuffer(cs, np.uint8)
+            src, n, on_dev = ctypes.c_void_p(b.ctypes.data), len(cs), 0
+        vr = ViewResult()
+        # The size of the written image.  Host bytes: the engine's own answer (gk_probe_view under this
+        # engine's display flags and precision list).  Device bytes cannot be probed: the size rule
+        # restated (_view_size; an all-0 region is the image, as in the C ABI).
+        why = None
+        if not on_dev:
+            arr, np_ = _precision_array(self._precision)
+            msg = ctypes.create_string_buffer(512)
+            pr = ViewResult()
+            if self.lib.gk_probe_view(src, n, self._display_flags, arr, np_, ctypes.byref(v), ctypes.byref(pr), msg, 512) == 0:
+                w, h = pr.pix_w, pr.pix_h
+            else:
+                why = msg.value.decode()
+        else:
+            whole = not (v.x0 or v.y0 or v.x1 or v.y1)
+            bw, bh = (info.w, info.h) if whole else (v.x1 - v.x0, v.y1 - v.y0)
+            try:
+                ow, oh = _view_size(bw, bh, v.out_w, v.out_h, fit) if bw > 0 and bh > 0 else (0, 0)
+            except ValueError:
+                ow = oh = 0
+            if 0 < ow <= bw and 0 < oh <= bh:
+                w, h = (oh, ow) if v.rotate in (90, 270) else (ow, oh)
+            else:
+                why = "the view has no size here"
+        if why is not None:
+            # The engine names its refusal itself.  It is asked with row_bytes 0, which is below any row
+            # and so is refused, after the refusals that concern the view, before a byte is written.
+            one = np.zeros(1, np.int64)
+            self.lib.gk_decode_view_pixels(self.ctx, src, n, on_dev, ctypes.byref(v), ctypes.c_void_p(one.ctypes.data), 0,
+                                           sample_bytes if out is None else _sample_bytes(out), 0, ctypes.byref(vr))
+            err = self.lib.gk_last_error(self.ctx).decode()
+            raise RuntimeError("gk_decode_view_pixels failed: %s" % (why if "row_bytes 0 " in err else err))
+        if out is not None:
+            assert tuple(out.shape) == (h, w, c) and out.stride(2) == 1 and (w == 1 or out.stride(1) == c)
+            sample_bytes = _sample_bytes(out)
+            es = sample_bytes or 4
+            dst, row_bytes, res, out_dev = ctypes.c_void_p(out.data_ptr()), (out.stride(0) if h > 1 else w * c) * es, out, 1
+        else:
+            es = sample_bytes or 4
+            res = np.empty((h, w, c), _np_sample_dtype(sample_bytes, info))
+            dst, row_bytes, out_dev = ctypes.c_void_p(res.ctypes.data), w * c * es, 0
+        if self.lib.gk_decode_view_pixels(self.ctx, src, n, on_dev, ctypes.byref(v), dst, row_bytes, sample_bytes,
+                                          out_dev, ctypes.byref(vr)) != 0:
+            self._err("gk_decode_view_pixels")
+        if (vr.pix_h, vr.pix_w, vr.channels) != (h, w, c):
+            raise RuntimeError("gk_decode_view_pixels wrote %d x %d x %d pixels into an array of %d x %d x %d"
+                               % (vr.pix_h, vr.pix_w, vr.channels, h, w, c))
+        self.view_result = vr
         return res
 
     def decode_window(self, cs, window, length=None, out=None, sample_bytes=0):

@@ -3551,6 +3551,7 @@ struct gk_ctx {
     DevBuf dicc_tab;                       // ICC stage: the launch's curve tables (icc_blob as uploaded)
     std::vector<uint8_t> icc_blob;
     DevBuf dpix_in;                        // encode from pixels: the host's packed rows
+    DevBuf dview;                          // view: the reduced region as packed int32 pixels, k_view's input
     HostBuf hstage1, hstage2;
     int16_t* nmse_tab = nullptr;   // device copy of the nmsedec tables (4 x 128)
     hipEvent_t ev[32];
@@ -5717,7 +5718,8 @@ static void merge_tile_parts(Header& Hd) {
 }
 
 // ---- One decode call.  The entry points fill these once; the stages pass them down by reference
-// and the chain only goes down: decode_call -> decode_output -> decode_planes -> decode_display or
+// and the chain only goes down: decode_call (or view_call, which resolves a view first and runs
+// k_view last) -> decode_opened -> decode_output -> decode_planes -> decode_display or
 // decode_colour -> decode_components -> decode_core.
 using HostClock = std::chrono::steady_clock;
 namespace {
@@ -6086,6 +6088,21 @@ static void decode_planes(gk_ctx* ctx, DecStream& o, const DecDst& dst, const De
     }
     decode_components(ctx, o, dst, rq, stg.whole);
 }
+// the sample type of sample_bytes for the output channels D, or the refusal
+static int output_sample_type(const DisplayOut& D, uint32_t sample_bytes) {
+    bool any_signed = false, all_signed = true;
+    for (const auto& h : D.ch) { any_signed = any_signed || h.sgnd; all_signed = all_signed && h.sgnd; }
+    const uint32_t oprec = D.max_prec();
+    if (sample_bytes == 1 || sample_bytes == 2) {
+        if (sample_bytes != (oprec + 7) / 8)
+            throw GkError("output: sample_bytes " + std::to_string(sample_bytes) + " for an output precision of " + std::to_string(oprec) +
+                          " bits: use (precision + 7) / 8-byte or int32 samples");
+        if (any_signed && !all_signed) throw GkError("output: 8 / 16-bit samples need one sign (sample_bytes): use int32 samples");
+    } else if (sample_bytes != 0 && sample_bytes != 4) {
+        throw GkError("output: sample_bytes must be 4 or (prec + 7) / 8");
+    }
+    return sample_bytes == 1 ? GK_U8 : sample_bytes == 2 ? GK_U16 : GK_S32;
+}
 // The output stage (DisplayOut::out_active, and every pixel call): the image is decoded as the
 // display flags and colour boxes make it (GK_DISPLAY_FORCE_RGB and the precision list set aside)
 // into engine-owned planes of the narrowest sample type, and k_pixels (gk_pixels.hip) reads them
@@ -6102,18 +6119,7 @@ static void decode_output(gk_ctx* ctx, DecStream& o, const DecDst& dst, const De
     const uint32_t red = D.upsampled ? 0 : ctx->dec_reduce;
     // every refusal first: nothing is allocated or launched before the call is known to be sound
     if (win && (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h)) throw GkError("bad decode window");
-    bool any_signed = false, all_signed = true;
-    for (const auto& h : D.ch) { any_signed = any_signed || h.sgnd; all_signed = all_signed && h.sgnd; }
-    const uint32_t oprec = D.max_prec();
-    if (sample_bytes == 1 || sample_bytes == 2) {
-        if (sample_bytes != (oprec + 7) / 8)
-            throw GkError("output: sample_bytes " + std::to_string(sample_bytes) + " for an output precision of " + std::to_string(oprec) +
-                          " bits: use (precision + 7) / 8-byte or int32 samples");
-        if (any_signed && !all_signed) throw GkError("output: 8 / 16-bit samples need one sign (sample_bytes): use int32 samples");
-    } else if (sample_bytes != 0 && sample_bytes != 4) {
-        throw GkError("output: sample_bytes must be 4 or (prec + 7) / 8");
-    }
-    const int dtype = sample_bytes == 1 ? GK_U8 : sample_bytes == 2 ? GK_U16 : GK_S32;
+    const int dtype = output_sample_type(D, sample_bytes);
     const size_t es_out = gk_sample_size(dtype);
     // the stage's channels (those the inner decode writes) and their planes
     std::vector<uint32_t> sw(nst), sh(nst), sprec(nst, 0);
@@ -6211,16 +6217,11 @@ static void decode_output(gk_ctx* ctx, DecStream& o, const DecDst& dst, const De
 }
 // A public decode call: the stream is opened once, and the output stage applies to a pixel call,
 // a forced precision and grey to RGB; everything else goes to decode_planes.
-static void decode_call(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const uint32_t* win) {
-    hipStream_t st = ctx->st;
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[0], st));
+static void decode_opened(gk_ctx* ctx, DecStream& o, const DecDst& dst, const uint32_t* win) {
     // Grok's partial-tile inverse (its single odd 5/3 sample shifted, not halved) follows a window
     // set with setDecompressWindow; decompressTile without one keeps the whole-tile rule
     const DecReq rq{win, win != nullptr && !ctx->win_whole_tile};
     const bool out_stage = dst.pixels || !ctx->dec_prec.empty();
-    DecStream o;
-    open_stream(o, src, st, ctx->dec_colour || ctx->dec_display || out_stage);
     DecStages stg;
     DisplayOut D;
     if (ctx->dec_display || out_stage) {   // display flags, a precision list, a pixel call
@@ -6232,6 +6233,143 @@ static void decode_call(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const
         stg.display = &D;
     }
     decode_planes(ctx, o, dst, rq, stg);
+}
+static void decode_call(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const uint32_t* win) {
+    hipStream_t st = ctx->st;
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    DecStream o;
+    open_stream(o, src, st, ctx->dec_colour || ctx->dec_display || dst.pixels || !ctx->dec_prec.empty());
+    decode_opened(ctx, o, dst, win);
+}
+
+// ---- A view (gk_probe_view, gk_decode_view_pixels): a region of the image at exactly out_w x
+// out_h pixels, mirrored and rotated.  resolve_view is the one place where the size and the reduce
+// level are worked out and where every refusal that needs no device is made; the probe and the
+// decode share it.
+namespace {
+struct ViewPlan {
+    gk_view_result res{};
+    uint32_t win[4] = {0, 0, 0, 0};   // the region, image relative
+    bool whole = false;               // the region was given as all 0: the image, decoded without a window
+    DisplayOut D;                     // the output channels at the chosen reduce level
+};
+}  // namespace
+// max(1, (2 a num + den) / (2 den)): side `a` scaled by num / den, rounded half up
+static uint64_t view_scaled(uint64_t a, uint64_t num, uint64_t den) {
+    const unsigned __int128 q = ((unsigned __int128)2 * a * num + den) / ((unsigned __int128)2 * den);
+    return std::max<uint64_t>(1, (uint64_t)std::min<unsigned __int128>(q, UINT64_MAX));
+}
+static ViewPlan resolve_view(const DecStream& o, bool apply_colour, uint32_t flags, const std::vector<gk_precision>& list,
+                             const gk_view& v) {
+    const Plan& W = o.Hd.want;
+    ViewPlan V;
+    if (v.rotate != 0 && v.rotate != 90 && v.rotate != 180 && v.rotate != 270)
+        throw GkError("view: rotate " + std::to_string(v.rotate) + " (it must be 0, 90, 180 or 270)");
+    if (v.mirror > 1) throw GkError("view: mirror must be 0 or 1");
+    if (v.fit > 1) throw GkError("view: fit must be 0 or 1");
+    V.whole = !v.x0 && !v.y0 && !v.x1 && !v.y1;
+    const uint32_t win[4] = {v.x0, v.y0, V.whole ? W.w : v.x1, V.whole ? W.h : v.y1};
+    if (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h)
+        throw GkError("view: the region is empty or leaves the image");
+    std::copy(win, win + 4, V.win);
+    const uint64_t RW = win[2] - win[0], RH = win[3] - win[1];
+    // the size
+    uint64_t ow = v.out_w, oh = v.out_h;
+    if (!ow && !oh) throw GkError("view: out_w and out_h are both 0");
+    if (!oh) oh = view_scaled(ow, RH, RW);
+    else if (!ow) ow = view_scaled(oh, RW, RH);
+    else if (v.fit) {
+        if ((unsigned __int128)ow * RH <= (unsigned __int128)oh * RW) oh = view_scaled(ow, RH, RW);
+        else ow = view_scaled(oh, RW, RH);
+    }
+    if (ow > RW || oh > RH)
+        throw GkError("view: upscaling (" + std::to_string(ow) + " x " + std::to_string(oh) + " from a region of " + std::to_string(RW) +
+                      " x " + std::to_string(RH) + ") is out of scope");
+    // the reduce level: the largest one gk_set_decode_reduce accepts for this stream at which the
+    // reduced region (every edge of its canvas rectangle ceil(x / 2^r)) still covers the size
+    uint32_t cap = GK_MAXRLVLS - 1;
+    for (uint32_t c = 0; c < W.nc; ++c) cap = std::min<uint32_t>(cap, W.p.c_numres(c) - 1);
+    if (flags & GK_DISPLAY_UPSAMPLE) cap = 0;   // (refused together with a reduction)
+    const uint64_t cx[4] = {(uint64_t)W.x0 + win[0], (uint64_t)W.y0 + win[1], (uint64_t)W.x0 + win[2], (uint64_t)W.y0 + win[3]};
+    auto edge = [&](int e, uint32_t r) { return (uint32_t)((cx[e] + ((1ull << r) - 1)) >> r); };
+    uint32_t r = 0;
+    while (r < cap && edge(2, r + 1) - edge(0, r + 1) >= ow && edge(3, r + 1) - edge(1, r + 1) >= oh) ++r;
+    const uint32_t rw = edge(2, r) - edge(0, r), rh = edge(3, r) - edge(1, r);
+    // the output channels, and what the pixel calls refuse
+    V.D = resolve_display(o.col, stream_channels(o, apply_colour), W, flags, r, V.whole ? nullptr : V.win, &list);
+    const DisplayOut& D = V.D;
+    const uint32_t nout = (uint32_t)D.ch.size();
+    if (nout > GK_PIX_MAX_CH)
+        throw GkError("pixels: " + std::to_string(nout) + " output channels (at most " + std::to_string(GK_PIX_MAX_CH) +
+                      "): use the planar calls gk_decode / gk_decode_window");
+    for (const auto& h : D.ch) {
+        uint32_t cw, chh;
+        comp_dims(W, h.dx, h.dy, D.upsampled ? 0 : r, V.win, cw, chh);
+        if (cw != rw || chh != rh)
+            throw GkError("pixels: output channels of different sizes (subsampled components): set GK_DISPLAY_UPSAMPLE");
+    }
+    const uint32_t prec = D.max_prec();
+    if ((((unsigned __int128)rw * rh) << prec) >> 62)
+        throw GkError("view: a source of " + std::to_string(rw) + " x " + std::to_string(rh) + " samples of " + std::to_string(prec) +
+                      " bits overflows the 64-bit accumulator");
+    gk_view_result& R = V.res;
+    R.reduce = r;
+    R.rx0 = edge(0, r); R.ry0 = edge(1, r); R.rx1 = edge(2, r); R.ry1 = edge(3, r);
+    R.out_w = (uint32_t)ow; R.out_h = (uint32_t)oh;
+    const bool swap = v.rotate == 90 || v.rotate == 270;
+    R.pix_w = swap ? R.out_h : R.out_w; R.pix_h = swap ? R.out_w : R.out_h;
+    R.channels = nout; R.prec = prec; R.sgnd = D.ch[0].sgnd;
+    return V;
+}
+// The decode: the window path at the chosen reduce level writes the reduced region as packed int32
+// pixels into ctx->dview (what gk_decode_window_pixels returns with sample_bytes 0 under
+// gk_set_decode_reduce(r)), and k_view (gk_view.hip) writes the caller's pixels from it.
+static void view_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, void* pixels, size_t row_bytes, uint32_t sample_bytes,
+                      bool out_on_device, gk_view_result* res) {
+    if (ctx->dec_reduce)
+        throw GkError("view: gk_set_decode_reduce is set (a view chooses the reduce level itself): set it to 0");
+    hipStream_t st = ctx->st;
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    DecStream o;
+    open_stream(o, src, st, true);
+    const ViewPlan V = resolve_view(o, ctx->dec_colour, ctx->dec_display, ctx->dec_prec, v);
+    const gk_view_result& R = V.res;
+    const int dtype = output_sample_type(V.D, sample_bytes);
+    const size_t es = gk_sample_size(dtype), C = R.channels;
+    const size_t tight = (size_t)R.pix_w * C * es;
+    if (row_bytes < tight) throw GkError("pixels: row_bytes " + std::to_string(row_bytes) + " is below w * C * es = " + std::to_string(tight));
+    if (row_bytes % es) throw GkError("pixels: row_bytes must be a multiple of the sample size");
+    if (out_on_device && ((uintptr_t)pixels % es)) throw GkError("pixels: the buffer is not aligned to its sample size");
+    if ((uint64_t)((R.out_w + 15) / 16) * ((R.out_h + 15) / 16) > GK_VIEW_MAX_TILES) throw GkError("view: an output of 2^24 tiles of 16 x 16 pixels or more is too large for one launch");
+    const uint32_t rw = R.rx1 - R.rx0, rh = R.ry1 - R.ry0;
+    const size_t src_row = (size_t)rw * C * 4;
+    void* region = ctx->dview.get(src_row * rh);
+    {   // the window path at the view's reduce level; the sticky one (0) is back whatever happens
+        struct Reduce {
+            gk_ctx* c;
+            Reduce(gk_ctx* c_, uint32_t r) : c(c_) { c->dec_reduce = r; }
+            ~Reduce() { c->dec_reduce = 0; }
+        } reduce(ctx, R.reduce);
+        decode_opened(ctx, o, DecDst{nullptr, nullptr, region, src_row, 0, true}, V.whole ? nullptr : V.win);
+    }
+    const size_t pitch = (tight + 15) & ~(size_t)15;
+    GkViewArgs a{};
+    a.src = region;
+    a.rw = rw; a.rh = rh; a.ow = R.out_w; a.oh = R.out_h; a.nch = (uint32_t)C;
+    a.mirror = v.mirror; a.rot = v.rotate / 90;
+    if (out_on_device) { a.dst = pixels; a.row_bytes = row_bytes; }
+    else { a.dst = ctx->dpix_out.get(pitch * R.pix_h); a.row_bytes = pitch; }
+    HIPCHK(hipEventRecord(ctx->ev[24], st));
+    if (gk_launch_view(st, dtype, a)) throw GkError("internal: view geometry");
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[25], st));
+    if (!out_on_device) HIPCHK(hipMemcpy2DAsync(pixels, row_bytes, a.dst, pitch, tight, R.pix_h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const float ms = ev_ms(ctx, 24, 25);   // the view pass counts as sample stage, as the output pass does
+    ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+    if (res) *res = R;
 }
 
 // ---- T2 parse of one tile (T2Decompress.cpp:216-570): its packets in progression order into
@@ -8352,6 +8490,38 @@ int gk_decode_window_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_o
                             int out_on_device) {
     const uint32_t win[4] = {x0, y0, x1, y1};
     return decode_pixels(ctx, cs, len, cs_on_device, win, pixels, row_bytes, sample_bytes, out_on_device);
+}
+
+int gk_probe_view(const uint8_t* cs, size_t len, uint32_t display_flags, const gk_precision* list, uint32_t n, const gk_view* v,
+                  gk_view_result* res, char* msg, size_t msg_cap) {
+    if (!cs || !v) return -1;
+    try {
+        if (display_flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB | GK_DISPLAY_ICC)) throw GkError("gk_probe_view: unknown flags");
+        if (n && !list) throw GkError("gk_probe_view: no list");
+        const std::vector<gk_precision> plist(list, list + n);
+        DecStream o;
+        open_stream(o, DecSrc{cs, len, false}, nullptr, true);
+        const ViewPlan V = resolve_view(o, true, display_flags, plist, *v);
+        if (res) *res = V.res;
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
+        return -1;
+    }
+}
+int gk_decode_view_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_view* v, void* pixels,
+                          size_t row_bytes, uint32_t sample_bytes, int out_on_device, gk_view_result* res) {
+    if (!ctx || !cs || !v || !pixels) return -1;
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
+        view_call(ctx, DecSrc{cs, len, cs_on_device != 0}, *v, pixels, row_bytes, sample_bytes, out_on_device != 0, res);
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
 }
 
 int gk_get_timings(gk_ctx* ctx, gk_timings* t) {

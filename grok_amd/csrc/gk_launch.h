@@ -219,6 +219,22 @@ struct GkPixArgs {
 };
 // stype / dtype: GK_U8, GK_U16 or GK_S32 planes in / pixels out
 void gk_launch_pixels(hipStream_t st, int stype, int dtype, const GkPixArgs& args);
+// Last stage of a view (gk_view.hip): src holds rw x rh packed int32 pixels of nch channels, rows
+// rw * nch samples apart (the engine's own buffer); they are area-averaged to ow x oh pixels
+// (ow <= rw, oh <= rh), mirrored left-right, rotated clockwise by rot quarter turns and written as
+// dtype samples: sample k of pixel (x, y) of the written image at dst + y * row_bytes +
+// (x * nch + k) * es.  Returns 0, or -1 without a launch when the arguments break these rules.
+#define GK_VIEW_MAX_TILES 0xffffffull   /* 16 x 16 output tiles on one grid axis: below 2^32 threads a launch */
+struct GkViewArgs {
+    const void* src;
+    void* dst;
+    uint64_t row_bytes;
+    uint32_t rw, rh, ow, oh, nch;
+    uint32_t mirror, rot;
+    uint32_t swap, pix_w, pix_h, tiles_x;   // (set by the launcher)
+};
+// dtype: GK_U8, GK_U16 or GK_S32 pixels out
+int gk_launch_view(hipStream_t st, int dtype, const GkViewArgs& args);
 // Input stage of an encode from packed pixels (gk_unpixels.hip): sample k of pixel (x, y) is read
 // at src + y * row_bytes + (x * nch + k) * es and written to plane k, dst + k * plane samples on,
 // row stride ds samples, in the same sample type.  The planes are the engine's own: dst, ds and

@@ -618,6 +618,66 @@ int gk_decode_window_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_o
                             uint32_t x1, uint32_t y1, void* pixels, size_t row_bytes, uint32_t sample_bytes,
                             int out_on_device);
 
+/* Decode a view: a region of the image at exactly out_w x out_h pixels, mirrored and rotated, as
+ * packed pixels in one call (the IIIF Image API's region / size / rotation; Grok's CLI has the
+ * region, -d, and the power-of-two reduction, -r, only).  The rules are the engine's own:
+ * The size.  W x H: the region at full resolution.  Both sizes given and fit = 0: as given (the
+ * aspect may change).  out_h = 0: out_h = max(1, (2 out_w H + W) / (2 W)); out_w = 0 likewise.
+ * fit = 1 with both given: if out_w H <= out_h W the width is kept and the height derived as above,
+ * otherwise the height is kept and the width derived.
+ * The reduce level.  The largest r that gk_set_decode_reduce accepts for the stream (below its
+ * smallest resolution count; 0 under GK_DISPLAY_UPSAMPLE) at which the reduced region, every edge
+ * of its canvas rectangle ceil(x / 2^r), is still at least out_w wide and out_h high.
+ * The decode.  The window path at r, under every sticky setting (layers, window rule, colour boxes,
+ * display flags, precision list), leaves the reduced region, rw x rh, as packed int32 pixels in an
+ * engine-owned device buffer: the samples gk_decode_window_pixels returns with sample_bytes 0 under
+ * gk_set_decode_reduce(r) (a region given as all 0: gk_decode_pixels').  k_view (gk_view.hip) then
+ * writes the caller's pixels.
+ * The resampling.  An exact area average on the reduced region.  In units of 1 / out_w, output
+ * column i covers [i rw, (i + 1) rw) and source column s covers [s out_w, (s + 1) out_w); the
+ * weight wx(i, s) is the length of their overlap, an integer, and a column's weights sum to rw;
+ * rows alike.  Per channel, in signed 64-bit integers,
+ *   out = floor((2 sum(wy wx v) + rw rh) / (2 rw rh))            (floor division; halves round up)
+ * so equal sizes copy the samples, an integer ratio gives the rounded block mean and a constant
+ * image stays constant.
+ * The orientation.  mirror: column i becomes out_w - 1 - i; the result is then rotated clockwise by
+ * `rotate` degrees (numpy: rot90(fliplr(a), k = -rotate / 90)); 90 and 270 swap the written
+ * image's width and height.
+ * pixels, row_bytes, sample_bytes, out_on_device: as gk_decode_pixels, for the written image of
+ * pix_w x pix_h pixels; row bytes past pix_w * C * es are never written.
+ * Refused, each by name, before anything is allocated or launched, and leaving the engine's state
+ * as it was: a non-zero gk_set_decode_reduce (the view chooses the level); a rotate other than 0,
+ * 90, 180, 270; mirror or fit above 1; a region that is empty or leaves the image; upscaling
+ * (out_w > W or out_h > H); both sizes 0; whatever gk_decode_window_pixels refuses from the
+ * header (subsampled channels without GK_DISPLAY_UPSAMPLE, more than 16 channels, the row_bytes /
+ * sample_bytes rules); a source with (rw rh) << prec >= 2^62 (the accumulator); an output of
+ * 2^24 tiles of 16 x 16 pixels or more.  One refusal comes later, where gk_decode_pixels makes it:
+ * a stream that holds only some of its tiles is found once its tile parts are located, after the
+ * engine's buffers have grown and before any kernel runs; it too changes no setting.  gk_get_timings afterwards: the decode's, with the view pass added to mct_ms and
+ * total_ms as the output pass is. */
+typedef struct gk_view {
+    uint32_t x0, y0, x1, y1;   /* region: gk_decode_window's rectangle convention; all 0 = whole image */
+    uint32_t out_w, out_h;     /* size before rotation; one of them may be 0 (kept aspect) */
+    uint32_t fit;              /* 1: the largest size of the region's aspect inside out_w x out_h (IIIF "!w,h") */
+    uint32_t rotate;           /* 0, 90, 180, 270, clockwise */
+    uint32_t mirror;           /* 1: mirror left-right before rotating (IIIF "!n") */
+} gk_view;
+typedef struct gk_view_result {
+    uint32_t reduce;                 /* resolutions discarded */
+    uint32_t rx0, ry0, rx1, ry1;     /* the region on the reduced canvas (every edge ceil(x / 2^reduce)) */
+    uint32_t out_w, out_h;           /* resolved size before rotation */
+    uint32_t pix_w, pix_h;           /* size of the written image (swapped for 90 / 270) */
+    uint32_t channels, prec, sgnd;   /* as the header calls report under the sticky settings */
+} gk_view_result;
+/* What gk_decode_view_pixels would answer for host bytes under these display flags and this
+ * precision list (n = 0: none), no device needed: 0 and *res, or -1 with the refusal in msg.  (The
+ * sticky reduce and the caller's buffer are the decode's to judge.) */
+int gk_probe_view(const uint8_t* cs, size_t len, uint32_t display_flags, const gk_precision* list, uint32_t n,
+                  const gk_view* v, gk_view_result* res, char* msg, size_t msg_cap);
+int gk_decode_view_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_view* v,
+                          void* pixels, size_t row_bytes, uint32_t sample_bytes, int out_on_device,
+                          gk_view_result* res /* may be NULL */);
+
 /* Inverse 5/3 rule of later gk_decode_window calls.  whole_tile = 0 (default): Grok's partial-tile
  * inverse, which a window set through setDecompressWindow selects for every tile
  * (CodeStreamDecompress.cpp:389; a one-sample-wide resolution on an odd coordinate shifts its
