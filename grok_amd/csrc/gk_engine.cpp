@@ -2365,7 +2365,10 @@ struct T2Enc {
                 bounds_prep(l, prev);
                 t_prep += msd(tp, clk::now());
             }
-            if (P.p.layer_rc(l)) {
+            // layerNeedsRateControl reads the tile's byte budget, not the ratio asked for: where the
+            // tile-part offset exceeds a small tile's budget (left negative above) the layer takes
+            // every remaining pass
+            if (P.p.quality ? P.p.layer_rc(l) : rates[l] > 0.0) {
                 double lower = min_slope, prevthresh = -1, thresh = 0;
                 // pass counts equal to those at an end of the bisection interval give that end's
                 // outcome (the simulation depends on nothing else): the simulation is skipped

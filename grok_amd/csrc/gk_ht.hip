@@ -450,7 +450,8 @@ __global__ __launch_bounds__(HT_WG) void k_ht_dec(const uint8_t* __restrict__ by
     if (G.npasses > 1 && lcup) { atomicOr(err, 4); zero_block(); return; }
     // 9/7: ScaleHTFilter (PostDecompressFilters.h:161-176) on the decoder's 32-bit sample, whose
     // magnitude LSB sits at p = 30 - k_msbs (ojph_block_decoder.cpp:1222); G.step = stepsize /
-    // 2^(31 - band numbps).  k_msbs > 29 does not fit 32 bits (:1028-1030).
+    // 2^(31 - band numbps), so a non-zero index q is rebuilt at (q + 1/2) * step.  k_msbs > 29
+    // does not fit 32 bits (:1028-1030).
     const bool irrev = G.flags & 1;
     const uint32_t kmsbs = (uint32_t)G.band_numbps - (uint32_t)G.numbps;
     if (G.npasses && lcup && kmsbs > 29) { atomicOr(err, 4); zero_block(); return; }
@@ -575,7 +576,8 @@ __global__ __launch_bounds__(HT_WG) void k_ht_dec(const uint8_t* __restrict__ by
             }
             uint32_t bits = (uint32_t)val;
             if (!INDEX && irrev) {
-                const uint32_t mag = ((uint32_t)(val < 0 ? -val : val) << pbit) & 0x7fffffffu;
+                // the centre of the bin rides one bit under the magnitude (v_n |= 1, :1219)
+                const uint32_t mag = val ? ((((uint32_t)(val < 0 ? -val : val) << pbit) | (1u << (pbit - 1))) & 0x7fffffffu) : 0u;
                 const float f = (float)mag * G.step;
                 bits = __float_as_uint(val < 0 ? -f : f);
             }

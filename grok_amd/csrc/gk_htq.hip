@@ -23,7 +23,8 @@ __device__ __forceinline__ uint64_t htq_wave_sum(uint64_t v) {
 // of one work item (blocks of one band class: component, resolution, orientation), for the
 // GK_HTQ_RUNGS steps [n0, n0 + GK_HTQ_RUNGS) of the class's step list.  The index is the
 // encoder's (k_ht_enc: the float coefficient times the reciprocal step, truncated), the
-// reconstruction point the lower edge of the bin (k_ht_dec).
+// reconstruction point the lower edge of the bin: the estimate's, and a cautious one, since
+// k_ht_dec rebuilds a non-zero index at the centre of its bin, as Grok's decoder does.
 //
 // Registers: GK_HTQ_RUNGS float accumulators per lane, and the compiler keeps the rungs' steps and
 // reciprocals (read once from LDS) in registers too: its resource report gives 138 VGPRs at 32

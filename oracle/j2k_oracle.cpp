@@ -2485,7 +2485,10 @@ static void rate_allocate(EncodeState& E) {
                 q += n; if (*q == ',') ++q;
             }
         }
-        if (layer_needs_rc(E.p, l)) {
+        // layerNeedsRateControl reads the tile's byte budget, not the ratio asked for: where the
+        // tile-part offset exceeds a small tile's budget (updateRates leaves it negative) the
+        // layer takes every remaining pass
+        if (E.p.quality ? layer_needs_rc(E.p, l) : rates[l] > 0.0) {
             double lower = min_slope, prevthresh = -1, thresh = 0;
             const double target = E.p.quality ? tile_dist - maxSE / pow(10.0, E.p.dist[l] / 10.0) : 0.0;
             for (uint32_t it = 0; it < 128; ++it) {
@@ -3221,14 +3224,17 @@ t2done:
                             else {
                                 // ScaleHTFilter (PostDecompressFilters.h:161-176): the decoder's 32-bit
                                 // sample (magnitude LSB at p = 30 - k_msbs, ojph_block_decoder.cpp:1222)
-                                // times stepsize / 2^(31 - band numbps) (Quantizer.cpp:52-62)
+                                // times stepsize / 2^(31 - band numbps) (Quantizer.cpp:52-62).  That
+                                // sample carries the centre of the bin, one bit under the magnitude
+                                // (v_n |= 1, :1219): a non-zero index q is rebuilt at (q + 1/2) * step,
+                                // as Grok's grk_decompress shows on these streams
                                 if (B.numbps > 31) { jrc[ji] = -4; return; }
                                 const uint32_t kmsbs = B.numbps - K.numbps, pp = 30 - kmsbs;
                                 const float scale = B.stepsize / (float)(1u << (31 - B.numbps));
                                 for (uint32_t y = 0; y < h; ++y)
                                     for (uint32_t x = 0; x < w; ++x) {
                                         const int32_t v = blk[y * w + x];
-                                        const uint32_t mag = ((uint32_t)(v < 0 ? -v : v) << pp) & 0x7fffffffu;
+                                        const uint32_t mag = v ? ((((uint32_t)(v < 0 ? -v : v) << pp) | (1u << (pp - 1))) & 0x7fffffffu) : 0u;
                                         const float f = (float)mag * scale;
                                         const size_t o = (size_t)(B.offy + K.y0 - B.y0 + y) * TW + (B.offx + K.x0 - B.x0 + x);
                                         fp[c][o] = v < 0 ? -f : f;

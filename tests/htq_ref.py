@@ -7,8 +7,10 @@
   multiplies with);
 * the known answer of a numres = 1 encode without MCT: the only band is LL with gain 1, its
   coefficient is sample - dc, the index trunc(|x| * (1 / step)) in float32 (the encoder multiplies
-  by the reciprocal step) and the decoded sample clip(rint(index * step) + dc): the lower edge of
-  the bin, Grok's ScaleHTFilter rule;
+  by the reciprocal step) and the decoded sample clip(rint((index + 1/2) * step) + dc) for a
+  non-zero index, dc for index 0: the centre of the bin, which the HT block decoder Grok uses puts
+  one bit under the magnitude and Grok's ScaleHTFilter scales with it (grk_decompress on these
+  streams: tests/test_grok_live.py);
 * the squared quantisation error of coefficients at a step (k_htq_dist's sum), in float64.
 """
 import numpy as np
@@ -105,11 +107,18 @@ def indices(x, delta):
     return np.trunc(a * inv).astype(np.float32)
 
 
+def reconstruct(q, delta):
+    """The coefficient magnitude a decoder rebuilds from index magnitude q at step delta: the centre
+    of the bin, (2 q + 1) * (delta / 2) in float32 (one rounding: the halving is exact), 0 for q = 0."""
+    q = np.asarray(q, dtype=np.float32)
+    return np.where(q > 0, (2 * q + 1) * (np.float32(delta) * np.float32(0.5)), np.float32(0)).astype(np.float32)
+
+
 def known_answer(img, prec, signed, delta):
     """Decoded samples of a numres = 1 encode without MCT at LL step delta (sample levels)."""
     dc = 0 if signed else 1 << (prec - 1)
     x = np.asarray(img, dtype=np.int64) - dc
-    rec = np.sign(x).astype(np.float32) * (indices(x, delta) * np.float32(delta))
+    rec = np.sign(x).astype(np.float32) * reconstruct(indices(x, delta), delta)
     lo, hi = (-(1 << (prec - 1)), (1 << (prec - 1)) - 1) if signed else (0, (1 << prec) - 1)
     return np.clip(np.rint(rec).astype(np.int64) + dc, lo, hi).astype(np.int32)
 

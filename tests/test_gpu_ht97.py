@@ -7,7 +7,9 @@ param_qcd::set_irrev_quant, HTParams.cpp:273-317) and decodes with Grok's own
 ScaleHTFilter rule (PostDecompressFilters.h:161-176), so a stream from this encoder decodes
 the same in Grok.  Bar: encode byte-identical to the oracle, decode sample-identical to the
 oracle, and the round trip close to the source (tolerance: PSNR >= 45 dB at the default
-step sizes).  Parity with Grok is unpinned (no reference-held HT 9/7 fixture).
+step sizes).  Grok's encoder writes no sound HT 9/7 stream to compare with; its decoder on these
+streams is held live (tests/test_grok_defects.py R-BUG-2 cases, tests/test_gpu_grok_live.py), which
+is where the reconstruction point, the centre of the bin, comes from.
 """
 import numpy as np
 import pytest

@@ -315,10 +315,9 @@ def test_composition(eng):
 @pytest.mark.skipif(not openjpeg.available(), reason="libopenjp2 not found")
 @pytest.mark.parametrize("name", ["mono12", "rgb", "tiles", "mono16"])
 def test_openjpeg_decodes(eng, name):
-    """OpenJPEG reconstructs at the bin's midpoint, Grok and the oracle at its lower edge, so the
-    samples differ; its PSNR against the source is not more than 1 dB below the oracle decode's.
-    (The shapes have a transform: at numres = 1 the coefficients are integers, a lower edge at an
-    integer step can be exact where a midpoint never is, and the two PSNRs are not comparable.)"""
+    """OpenJPEG is another decoder with its own arithmetic (it rebuilds at the bin's centre, as Grok, the
+    oracle and the engine do; the bar dates from the oracle's earlier lower-edge rule and holds), so the
+    samples may differ; its PSNR against the source is not more than 1 dB below the oracle decode's."""
     img, kw, okw, bits, sg = _case(name)
     for n in (8, 24):
         eng.set_encode_quant(step=R.ladder_step(bits, sg, n))

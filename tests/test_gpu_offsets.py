@@ -4,9 +4,9 @@
 The image area sits at (x0, y0) on the canvas and the tile grid at (tx0, ty0) <= (x0, y0): tile
 rectangles, resolution and band geometry are canvas coordinates (so the lifting parity follows
 the canvas position, WaveletFwd.cpp:486-489), work planes hold the image area.  Bar: codestreams
-byte-identical to the oracle (which restates B.2-B.3 with its odd-parity lifting; Grok fixtures
-with offsets do not exist, so these cases are parity-unpinned against Grok itself beyond the
-oracle's lossless round trips), decodes equal to the oracle's, 5/3 lossless, windows and reduced
+byte-identical to the oracle (which restates B.2-B.3 with its odd-parity lifting; Grok's own
+binaries write the same bytes for five of CASES and get three wrong, tests/test_grok_live.py and
+tests/test_grok_defects.py R-BUG-5..7), decodes equal to the oracle's, 5/3 lossless, windows and reduced
 decodes relative to the image origin.
 """
 import numpy as np

@@ -2,8 +2,9 @@
 
 The interface is declared and exported; the reference rule of tests/htq_ref.py gives the QCD the
 oracle writes at the default step; the decode half of its known answer (the sample a decoder
-returns for index q under the step a QCD's (exponent, mantissa) pair represents is
-rint(q * step) + dc, the lower edge of the bin) holds against the oracle's decoder on oracle-written
+returns for a non-zero index q under the step a QCD's (exponent, mantissa) pair represents is
+rint((q + 1/2) * step) + dc, the centre of the bin, as Grok's decoder rebuilds it) holds against
+the oracle's decoder on oracle-written
 numres = 1 streams whose mantissa is rewritten; the probe reports the ladder and every refusal.
 """
 import os
@@ -52,7 +53,9 @@ def test_default_qcd_is_the_oracles(prec, signed, numres):
 def test_lower_edge_reconstruction(prec, signed, mant):
     """An oracle-written numres = 1 stream codes the indices sample - dc at step 1 (signed: 1/2, the
     indices doubled).  With only the QCD mantissa rewritten, the oracle's decoder must return
-    rint(index * step') + dc for the step' the new pair represents."""
+    rint((index + 1/2) * step') + dc for the step' the new pair represents (dc for index 0): the
+    centre of the bin, where Grok's decoder rebuilds (the test keeps its name from the time the
+    oracle rebuilt at the lower edge, which Grok's own binaries showed to be a misreading)."""
     img = _img(7 + mant, prec, signed)
     cs = bytearray(O.encode(img, prec, signed=signed, numres=1, **HT97))
     i = cs.find(b"\xff\x5c")
@@ -64,7 +67,7 @@ def test_lower_edge_reconstruction(prec, signed, mant):
     x = img.astype(np.int64) - dc
     q = np.sign(x) * R.indices(x, old)
     lo, hi = (-(1 << (prec - 1)), (1 << (prec - 1)) - 1) if signed else (0, (1 << prec) - 1)
-    want = np.clip(np.rint(q.astype(np.float32) * new).astype(np.int64) + dc, lo, hi)
+    want = np.clip(np.rint(np.sign(q) * R.reconstruct(np.abs(q), new)).astype(np.int64) + dc, lo, hi)
     np.testing.assert_array_equal(O.decode(bytes(cs))[0], want)
 
 

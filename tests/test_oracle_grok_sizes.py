@@ -20,8 +20,10 @@ digits); these tests hold the oracle to them byte for byte.  They pin:
   * progression order changes (-P): POC in the main header and in each tile's first part, one
     tile part per entry, the rate-control simulation in the tile's own progression.
 
-Grok is not rebuilt in this repository (its build is cmake with generated config headers:
-DESIGN.md section 4), so the reviews' numbers are the reference.
+These numbers were typed in from the reviews' own Grok builds, on full-size images.  Grok can be
+rebuilt beside this repository (`make -C oracle ref`): tests/test_grok_live.py
+and tests/test_grok_fixtures.py hold the same option families to its binaries and to recordings
+of their output on small images; the numbers here stay as the full-size pin.
 """
 import hashlib
 
