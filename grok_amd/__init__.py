@@ -32,7 +32,9 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_set_encode_convert", "gk_probe_encode_convert", "gk_set_default_transcode", "gk_transcode",
            "gk_probe_transcode", "gk_set_encode_roi", "gk_probe_encode_roi", "gk_roi_band_mask",
            "gk_set_encode_quant", "gk_probe_encode_quant", "gk_get_encode_quant", "gk_probe_view",
-           "gk_decode_view_pixels")
+           "gk_decode_view_pixels", "gk_set_decode_render", "gk_probe_render", "gk_decode_levels")
+GK_RENDER_WINDOW, GK_RENDER_MAP, GK_RENDER_BLEND = 1, 2, 3   # gk_render::mode
+GK_RENDER_MAX_CHANNELS, GK_LEVELS_MAX_BINS = 16, 4096
 GK_QUANT_STEP, GK_QUANT_BYTES, GK_QUANT_PSNR = 1, 2, 3   # gk_encode_quant::mode
 GK_QUANT_FOR_TILES, GK_QUANT_FOR_BLOCKS = 0x100, 0x200   # gk_probe_encode_quant: the call asked about
 GK_TRANSCODE_HT, GK_TRANSCODE_PART1 = 1, 2   # gk_transcode_params::target
@@ -197,6 +199,132 @@ def parse_iiif(w, h, region="full", size="max", rotation="0"):
     if angle not in (0, 90, 180, 270):
         raise ValueError("iiif rotation %r: only 0, 90, 180 and 270 are supported" % rotation)
     return dict(region=box, width=width, height=height, fit=fit, rotate=int(angle), mirror=mirror)
+
+
+class RenderChannel(ctypes.Structure):
+    """gk_render_channel: one channel's window and its BLEND tint."""
+    _fields_ = [("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("tint", ctypes.c_uint8 * 3)]
+
+
+class Render(ctypes.Structure):
+    """gk_render (include/grok_amd.h): how the pixel calls' int32 samples become 8-bit display pixels."""
+    _fields_ = [("mode", ctypes.c_uint32), ("n", ctypes.c_uint32), ("ch", ctypes.POINTER(RenderChannel)),
+                ("curve", ctypes.POINTER(ctypes.c_uint8)), ("map", ctypes.POINTER(ctypes.c_uint8))]
+
+
+class RenderResult(ctypes.Structure):
+    """gk_render_result: the rendered output's channels, precision, sign and colour space."""
+    _fields_ = [("channels", ctypes.c_uint32), ("prec", ctypes.c_uint32), ("sgnd", ctypes.c_uint32),
+                ("colour_space", ctypes.c_uint32)]
+
+    def __repr__(self):
+        return "RenderResult(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+class LevelsBins(ctypes.Structure):
+    """gk_levels_bins: bin b of a channel holds origin + b * 2^shift .. origin + (b + 1) * 2^shift - 1."""
+    _fields_ = [("origin", ctypes.c_int32), ("shift", ctypes.c_uint32)]
+
+
+class ChannelLevels(ctypes.Structure):
+    """gk_channel_levels: one channel's statistics."""
+    _fields_ = [("min", ctypes.c_int32), ("max", ctypes.c_int32), ("sum", ctypes.c_int64), ("count", ctypes.c_uint64)]
+
+
+def gamma_curve(g):
+    """The 256-byte curve round(255 (t / 255)^(1 / g)), built on the host: the kernel never sees a float."""
+    g = float(g)
+    if not g > 0:
+        raise ValueError("render: gamma must be positive")
+    t = np.arange(256, dtype=np.float64) / 255.0
+    return np.floor(255.0 * t ** (1.0 / g) + 0.5).astype(np.uint8)
+
+
+def _render(mode, windows, tints, curve, map, gamma):
+    """(gk_render or None, the arrays it points into) of set_decode_render's / probe_render's arguments."""
+    if mode is None:
+        return None, ()
+    modes = {"window": GK_RENDER_WINDOW, "map": GK_RENDER_MAP, "blend": GK_RENDER_BLEND}
+    if mode not in modes and mode not in modes.values():
+        raise ValueError("render: mode %r (None, 'window', 'map' or 'blend')" % (mode,))
+    windows = [tuple(int(v) for v in w) for w in (windows or [])]
+    if any(len(w) != 2 or not all(-2 ** 31 <= v < 2 ** 31 for v in w) for w in windows):
+        raise ValueError("render: windows are (lo, hi) pairs of int32 values")
+    tints = [tuple(int(v) for v in t) for t in (tints or [])]
+    if any(len(t) != 3 or not all(0 <= v <= 255 for v in t) for t in tints):
+        raise ValueError("render: tints are (r, g, b) in 0 .. 255")
+    if windows and tints and len(tints) != len(windows) and 1 not in (len(tints), len(windows)):
+        raise ValueError("render: %d windows for %d tints" % (len(windows), len(tints)))
+    n = max(len(windows), len(tints))
+    ch = (RenderChannel * max(n, 1))()
+    for k in range(n):
+        lo, hi = windows[min(k, len(windows) - 1)] if windows else (0, 0)
+        tint = tints[min(k, len(tints) - 1)] if tints else (0, 0, 0)
+        ch[k] = RenderChannel(lo, hi, (ctypes.c_uint8 * 3)(*tint))
+    if curve is not None and gamma is not None:
+        raise ValueError("render: give curve= or gamma=, not both")
+    if gamma is not None:
+        curve = gamma_curve(gamma)
+    keep = [ch]
+    r = Render(modes.get(mode, mode), n, ch, None, None)
+    if curve is not None:
+        c = np.ascontiguousarray(curve)
+        if c.dtype != np.uint8 or c.shape != (256,):
+            raise ValueError("render: curve must be 256 uint8 values")
+        keep.append(c)
+        r.curve = c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+    if map is not None:
+        m = np.ascontiguousarray(map)
+        if m.dtype != np.uint8 or m.shape != (256, 3):
+            raise ValueError("render: map must be a (256, 3) uint8 array")
+        keep.append(m)
+        r.map = m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+    return r, keep
+
+
+class Levels:
+    """What Engine.levels reports of a view's int32 pixels, per output channel: min, max, sum (exact), mean
+    (sum / count as a float), count, and with bins the histogram hist[k] (uint64,
+    bin b of channel k holding origin[k] + b * 2^shift[k] and the 2^shift[k] - 1 values after it;
+    values outside the binned range are counted in the end bins)."""
+
+    def __init__(self, stats, hist, origin, shift, view):
+        self.min = [int(s.min) for s in stats]
+        self.max = [int(s.max) for s in stats]
+        self.sum = [int(s.sum) for s in stats]
+        self.count = [int(s.count) for s in stats]
+        self.mean = [s / c for s, c in zip(self.sum, self.count)]
+        self.hist, self.origin, self.shift, self.view = hist, list(origin), list(shift), view
+
+    def window(self, low, high, per=1000):
+        """[(lo, hi)] per channel from the histogram, in integers: with N pixels, lo is the lower edge
+        of the first bin whose cumulative count reaches max(1, ceil(N low / per)), hi the last value
+        of the first bin whose cumulative count reaches ceil(N high / per); hi = lo + 1 if they meet."""
+        if self.hist is None:
+            raise ValueError("levels: no histogram (bins=0)")
+        low, high, per = int(low), int(high), int(per)
+        if not 0 <= low <= high <= per or per <= 0:
+            raise ValueError("levels: 0 <= low <= high <= per")
+        return [_percentile_window(self.hist[k], self.origin[k], self.shift[k], low, high, per) for k in range(len(self.min))]
+
+
+def _percentile_window(hist, origin, shift, low, high, per):
+    cum, n = 0, int(sum(int(v) for v in hist))
+    need_lo, need_hi = max(1, -(-n * low // per)), -(-n * high // per)
+    lo = hi = None
+    for b, c in enumerate(hist):
+        cum += int(c)
+        if lo is None and cum >= need_lo:
+            lo = origin + (b << shift)
+        if hi is None and cum >= need_hi:
+            hi = origin + ((b + 1) << shift) - 1
+        if lo is not None and hi is not None:
+            break
+    if lo is None or hi is None:
+        raise ValueError("levels: an empty histogram")
+    if hi <= lo:
+        hi = lo + 1
+    return lo, hi
 
 
 def _precision_array(spec):
@@ -663,6 +791,16 @@ def load_library(build_if_missing=True):
         lib.gk_decode_view_pixels.restype = ctypes.c_int
         lib.gk_decode_view_pixels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(View),
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, P(ViewResult)]
+    if hasattr(lib, "gk_set_decode_render") or not os.environ.get("GROK_AMD_LIB"):   # (as above: an older A side)
+        lib.gk_set_decode_render.restype = ctypes.c_int
+        lib.gk_set_decode_render.argtypes = [ctypes.c_void_p, P(Render)]
+        lib.gk_probe_render.restype = ctypes.c_int
+        lib.gk_probe_render.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, P(Precision), ctypes.c_uint32,
+                                        P(Render), P(RenderResult), ctypes.c_char_p, ctypes.c_size_t]
+        lib.gk_decode_levels.restype = ctypes.c_int
+        lib.gk_decode_levels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(View),
+                                         P(LevelsBins), ctypes.c_uint32, ctypes.c_uint32, P(ChannelLevels),
+                                         ctypes.c_void_p, ctypes.c_size_t, P(ViewResult)]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -870,6 +1008,27 @@ def probe_view(cs, region=None, size=None, width=None, height=None, fit=False, r
     msg = ctypes.create_string_buffer(512)
     if lib.gk_probe_view(b.ctypes.data, len(b), flags, arr, n, ctypes.byref(v), ctypes.byref(res), msg, 512) != 0:
         raise ValueError(msg.value.decode())
+    return res
+
+
+def probe_render(cs, mode=None, windows=None, tints=None, curve=None, map=None, gamma=None, rgb=False, upsample=False,
+                 force_rgb=False, icc=False, precision=None):
+    """gk_probe_render: what the pixel calls return for host codestream / JP2 bytes under
+    set_decode_display(rgb, upsample, force_rgb, icc), set_decode_precision(precision) and
+    set_decode_render(mode, windows, ...), no engine or GPU needed: a RenderResult (channels, prec,
+    sgnd, colour_space).  Raises ValueError with the engine's refusal."""
+    lib = load_library()
+    b = np.frombuffer(bytes(cs), np.uint8)
+    flags = (GK_DISPLAY_RGB if rgb else 0) | (GK_DISPLAY_UPSAMPLE if upsample else 0) | \
+        (GK_DISPLAY_FORCE_RGB if force_rgb else 0) | (GK_DISPLAY_ICC if icc else 0)
+    arr, n = _precision_array(precision)
+    r, keep = _render(mode, windows, tints, curve, map, gamma)
+    res = RenderResult()
+    msg = ctypes.create_string_buffer(512)
+    if lib.gk_probe_render(b.ctypes.data, len(b), flags, arr, n, ctypes.byref(r) if r is not None else None,
+                           ctypes.byref(res), msg, 512) != 0:
+        raise ValueError(msg.value.decode())
+    del keep
     return res
 
 
@@ -1404,6 +1563,76 @@ class Engine:
             self._err("gk_set_decode_precision")
         self._precision = parse_precision(spec)
 
+    def set_decode_render(self, mode=None, windows=None, tints=None, curve=None, map=None, gamma=None):
+        """gk_set_decode_render: the pixel calls (decode_pixels, decode_view) return unsigned 8-bit
+        display pixels.  mode: None (clears it), "window" (C channels in, C out), "map" (one channel
+        through a (256, 3) uint8 colour map) or "blend" (1..16 tinted channels added into RGB).
+        windows: [(lo, hi)] sample values stretched to 0..255, any int32 pair, lo > hi inverts; tints:
+        [(r, g, b)] for blend; channel k takes entry min(k, n - 1) of each.  curve: 256 uint8 values
+        applied after the window, or gamma=g for round(255 (t / 255)^(1 / g)).  Sticky; read_header
+        then reports the rendered channels at 8 bits, and decode / decode_window refuse."""
+        r, keep = _render(mode, windows, tints, curve, map, gamma)
+        if self.lib.gk_set_decode_render(self.ctx, ctypes.byref(r) if r is not None else None) != 0:
+            self._err("gk_set_decode_render")
+        del keep
+        self._render = r is not None
+
+    def levels(self, cs, region=None, size=None, width=None, height=None, fit=False, bins=4096, length=None,
+               origin=None, shift=None):
+        """gk_decode_levels: min, max, sum, count and a histogram of exactly the int32 pixels
+        decode_view(cs, region, size, ...) returns, per output channel, computed on the GPU without
+        writing the pixels (a render that is set is ignored).  region / size / width / height / fit:
+        as decode_view (none of the sizes: the region's own).  bins: 1..4096 counters a channel, or 0
+        for none.  Without origin= / shift= (one value, or one per channel) the binning is chosen
+        from the data: bin 0 starts at the channel's minimum and the shift is the smallest at which
+        the maximum fits, which takes a second call when max - min >= bins.  Returns a Levels."""
+        bins = int(bins)
+        if _is_torch_cuda(cs):
+            src, n, on_dev = ctypes.c_void_p(cs.data_ptr()), length, 1
+        else:
+            b = np.frombuffer(cs, np.uint8)
+            src, n, on_dev = ctypes.c_void_p(b.ctypes.data), len(cs), 0
+        if size is None and width is None and height is None:
+            if region is not None:
+                size = (region[2] - region[0], region[3] - region[1])
+            else:
+                info = self.read_header(cs, length)
+                size = (info.w, info.h)
+        v = _view(region, size, width, height, fit, 0, False)
+
+        def call(entries):
+            q = (LevelsBins * max(len(entries), 1))(*[LevelsBins(int(o), int(s)) for o, s in entries])
+            stats, vr = (ChannelLevels * GK_RENDER_MAX_CHANNELS)(), ViewResult()
+            hist = np.zeros((GK_RENDER_MAX_CHANNELS, bins), np.uint64) if bins else None
+            if self.lib.gk_decode_levels(self.ctx, src, n, on_dev, ctypes.byref(v), q, len(entries), bins, stats,
+                                         ctypes.c_void_p(hist.ctypes.data) if bins else None, hist.size if bins else 0,
+                                         ctypes.byref(vr)) != 0:
+                self._err("gk_decode_levels")
+            c = vr.channels
+            return [stats[k] for k in range(c)], (hist.reshape(-1)[:c * bins].reshape(c, bins) if bins else None), vr
+
+        if origin is not None or shift is not None:
+            as_list = lambda x: list(x) if isinstance(x, (list, tuple)) else [x or 0]
+            o, sh = as_list(origin), as_list(shift)
+            m = max(len(o), len(sh))
+            entries = [(o[min(k, len(o) - 1)], sh[min(k, len(sh) - 1)]) for k in range(m)]
+            stats, hist, vr = call(entries)
+            c = len(stats)
+            ent = [entries[min(k, m - 1)] for k in range(c)]
+            return Levels(stats, hist, [e[0] for e in ent], [e[1] for e in ent], vr)
+        stats, hist, vr = call([(0, 0)])
+        if not bins:
+            return Levels(stats, None, [0] * len(stats), [0] * len(stats), vr)
+        entries = []
+        for st in stats:
+            sh = 0
+            while ((st.max - st.min) >> sh) >= bins:
+                sh += 1
+            entries.append((st.min, sh))
+        if any(e != (0, 0) for e in entries):
+            stats, hist, vr = call(entries)
+        return Levels(stats, hist, [e[0] for e in entries], [e[1] for e in entries], vr)
+
     def precisions(self):
         """[(prec, signed)] per output channel of the stream the last read_header / decode read."""
         pr, sg = (ctypes.c_uint32 * 16384)(), (ctypes.c_uint32 * 16384)()
@@ -1435,6 +1664,8 @@ class Engine:
             dst, row_bytes, res, out_dev = ctypes.c_void_p(out.data_ptr()), (out.stride(0) if h > 1 else w * c) * es, out, 1
         else:
             es = sample_bytes or 4
+            if getattr(self, "_render", False):   # rendered: unsigned 8-bit whatever was asked
+                sample_bytes = es = 1
             res = np.empty((h, w, c), _np_sample_dtype(sample_bytes, info))
             dst, row_bytes, out_dev = ctypes.c_void_p(res.ctypes.data), w * c * es, 0
         if _is_torch_cuda(cs):
@@ -1509,6 +1740,8 @@ class Engine:
             dst, row_bytes, res, out_dev = ctypes.c_void_p(out.data_ptr()), (out.stride(0) if h > 1 else w * c) * es, out, 1
         else:
             es = sample_bytes or 4
+            if getattr(self, "_render", False):   # rendered: unsigned 8-bit whatever was asked
+                sample_bytes = es = 1
             res = np.empty((h, w, c), _np_sample_dtype(sample_bytes, info))
             dst, row_bytes, out_dev = ctypes.c_void_p(res.ctypes.data), w * c * es, 0
         if self.lib.gk_decode_view_pixels(self.ctx, src, n, on_dev, ctypes.byref(v), dst, row_bytes, sample_bytes,

@@ -3511,6 +3511,13 @@ struct HostBuf {
 
 // gk_set_encode_quant's setting, copied in (mode 0: none)
 struct EncQuant { uint32_t mode = 0; double value = 0.0; };
+// gk_set_decode_render's description, copied in (mode 0: none); tables: the curve (256 bytes), then the map (768)
+struct DecRender {
+    uint32_t mode = 0;
+    std::vector<gk_render_channel> ch;
+    bool has_curve = false;
+    uint8_t tables[GK_RENDER_TABLE_BYTES] = {};
+};
 
 struct gk_ctx {
     uint32_t dec_layers = 0;   // quality layers to decode (0 = all; grk_dparameters::cp_layer)
@@ -3555,6 +3562,11 @@ struct gk_ctx {
     std::vector<uint8_t> icc_blob;
     DevBuf dpix_in;                        // encode from pixels: the host's packed rows
     DevBuf dview;                          // view: the reduced region as packed int32 pixels, k_view's input
+    DecRender dec_render;                  // gk_set_decode_render: sticky, read by the pixel and header calls, never written by a decode
+    uint32_t hdr_render = 0;               // its mode when the last gk_decode_header ran (gk_header_colour)
+    DevBuf drender_tab;                    // k_render's curve and map, uploaded by the call that reads them
+    DevBuf dlevels;                        // gk_decode_levels: stats and uint64 histogram, initialised by the call that reads them
+    std::vector<uint8_t> levels_host;      // ... and their host copy
     HostBuf hstage1, hstage2;
     int16_t* nmse_tab = nullptr;   // device copy of the nmsedec tables (4 x 128)
     hipEvent_t ev[32];
@@ -6325,9 +6337,137 @@ static ViewPlan resolve_view(const DecStream& o, bool apply_colour, uint32_t fla
     R.channels = nout; R.prec = prec; R.sgnd = D.ch[0].sgnd;
     return V;
 }
+// ---- Render (gk_set_decode_render, gk_probe_render): the description checked and copied in, and
+// what it makes of a stream's output channels.  Both refuse by name and touch no device.
+static DecRender checked_render(const gk_render* r) {
+    DecRender R;
+    if (!r || !r->mode) return R;
+    if (r->mode > GK_RENDER_BLEND) throw GkError("render: mode " + std::to_string(r->mode) + " (1 window, 2 map, 3 blend)");
+    if (!r->n || r->n > GK_RENDER_MAX_CHANNELS)
+        throw GkError("render: " + std::to_string(r->n) + " channel entries (1 .. " + std::to_string(GK_RENDER_MAX_CHANNELS) + ")");
+    if (!r->ch) throw GkError("render: no channel entries");
+    bool tinted = false;
+    for (uint32_t k = 0; k < r->n; ++k) {
+        if (r->ch[k].lo == r->ch[k].hi)
+            throw GkError("render: entry " + std::to_string(k) + " has lo == hi (" + std::to_string(r->ch[k].lo) + "): an empty window");
+        tinted = tinted || r->ch[k].tint[0] || r->ch[k].tint[1] || r->ch[k].tint[2];
+    }
+    if (r->mode == GK_RENDER_MAP && !r->map) throw GkError("render: map mode without a 256 x 3 table");
+    if (r->mode == GK_RENDER_BLEND && !tinted) throw GkError("render: blend mode with every tint zero");
+    R.mode = r->mode;
+    R.ch.assign(r->ch, r->ch + r->n);
+    R.has_curve = r->curve != nullptr;
+    if (r->curve) memcpy(R.tables, r->curve, 256);
+    if (r->mode == GK_RENDER_MAP) memcpy(R.tables + 256, r->map, 768);
+    return R;
+}
+// the rendered channel count of nin output channels, or the refusal
+static uint32_t render_channels(const DecRender& R, uint32_t nin) {
+    if (nin > GK_RENDER_MAX_CHANNELS)
+        throw GkError("render: " + std::to_string(nin) + " output channels (at most " + std::to_string(GK_RENDER_MAX_CHANNELS) + ")");
+    if (R.mode == GK_RENDER_MAP && nin != 1)
+        throw GkError("render: map mode on " + std::to_string(nin) + " output channels (it takes exactly one)");
+    if (R.mode == GK_RENDER_BLEND) {
+        bool tinted = false;
+        for (uint32_t k = 0; k < nin; ++k) {
+            const gk_render_channel& c = R.ch[std::min<size_t>(k, R.ch.size() - 1)];
+            tinted = tinted || c.tint[0] || c.tint[1] || c.tint[2];
+        }
+        if (!tinted) throw GkError("render: blend mode with every tint of the image's " + std::to_string(nin) + " channels zero");
+    }
+    return R.mode == GK_RENDER_WINDOW ? nin : 3;
+}
+// what a pixel call's buffer must be under a render: bytes, rows of at least w * C
+static void render_buffer(uint32_t sample_bytes, size_t row_bytes, size_t tight) {
+    if (sample_bytes != 1)
+        throw GkError("render: sample_bytes " + std::to_string(sample_bytes) + " (the rendered output is unsigned 8-bit: sample_bytes must be 1)");
+    if (row_bytes < tight) throw GkError("pixels: row_bytes " + std::to_string(row_bytes) + " is below w * C * es = " + std::to_string(tight));
+}
+// k_render over `region` (rw x rh packed int32 pixels of nin channels) into the caller's bytes
+static void render_launch(gk_ctx* ctx, const DecRender& R, GkViewArgs va, uint32_t cout, void* pixels, size_t row_bytes, bool out_on_device) {
+    hipStream_t st = ctx->st;
+    const bool swap = va.rot & 1;
+    const uint32_t pix_w = swap ? va.oh : va.ow, pix_h = swap ? va.ow : va.oh;
+    const size_t tight = (size_t)pix_w * cout, pitch = (tight + 15) & ~(size_t)15;
+    GkRenderArgs a{};
+    a.v = va;
+    if (out_on_device) { a.v.dst = pixels; a.v.row_bytes = row_bytes; }
+    else { a.v.dst = ctx->dpix_out.get(pitch * pix_h); a.v.row_bytes = pitch; }
+    for (uint32_t k = 0; k < va.nch; ++k) {
+        const gk_render_channel& c = R.ch[std::min<size_t>(k, R.ch.size() - 1)];
+        GkRenderChan& h = a.ch[k];
+        h.inv = c.lo > c.hi;
+        h.lo = std::min(c.lo, c.hi); h.hi = std::max(c.lo, c.hi);
+        memcpy(h.tint, c.tint, 3);
+    }
+    a.mode = R.mode; a.has_curve = R.has_curve ? 1 : 0;
+    if (R.has_curve || R.mode == GK_RENDER_MAP) {
+        uint8_t* dt = (uint8_t*)ctx->drender_tab.get(GK_RENDER_TABLE_BYTES);
+        HIPCHK(hipMemcpyAsync(dt, R.tables, GK_RENDER_TABLE_BYTES, hipMemcpyHostToDevice, st));
+        a.tables = dt;
+    }
+    HIPCHK(hipEventRecord(ctx->ev[24], st));
+    if (gk_launch_render(st, a)) throw GkError("internal: render geometry");
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[25], st));
+    if (!out_on_device) HIPCHK(hipMemcpy2DAsync(pixels, row_bytes, a.v.dst, pitch, tight, pix_h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const float ms = ev_ms(ctx, 24, 25);   // counts as sample stage, as the view pass does
+    ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+}
+// gk_decode_pixels / gk_decode_window_pixels under a render: the call itself with sample_bytes 0
+// into ctx->dview, then k_render at equal sizes (its copy branch)
+static void render_pixels_call(gk_ctx* ctx, const DecSrc& src, const uint32_t* win, void* pixels, size_t row_bytes,
+                               uint32_t sample_bytes, bool out_on_device) {
+    hipStream_t st = ctx->st;
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    DecStream o;
+    open_stream(o, src, st, true);
+    const Plan& W = o.Hd.want;
+    if (win && (win[0] >= win[2] || win[1] >= win[3] || win[2] > W.w || win[3] > W.h)) throw GkError("bad decode window");
+    const DisplayOut D = call_display(ctx, o, ctx->dec_display, win, &ctx->dec_prec);
+    const uint32_t nin = (uint32_t)D.ch.size();
+    const uint32_t cout = render_channels(ctx->dec_render, nin);
+    const uint32_t red = D.upsampled ? 0 : ctx->dec_reduce;
+    uint32_t w = 0, h = 0;
+    for (uint32_t k = 0; k < nin; ++k) {
+        uint32_t cw, chh;
+        comp_dims(W, D.ch[k].dx, D.ch[k].dy, red, win, cw, chh);
+        if (!cw || !chh) throw GkError(win ? "the window is empty at this reduction" : "output: a channel without samples in this area");
+        if (k && (cw != w || chh != h))
+            throw GkError("pixels: output channels of different sizes (subsampled components): set GK_DISPLAY_UPSAMPLE");
+        w = cw; h = chh;
+    }
+    render_buffer(sample_bytes, row_bytes, (size_t)w * cout);
+    if ((uint64_t)((w + 15) / 16) * ((h + 15) / 16) > GK_VIEW_MAX_TILES) throw GkError("render: an output of 2^24 tiles of 16 x 16 pixels or more is too large for one launch");
+    const size_t src_row = (size_t)w * nin * 4;
+    void* region = ctx->dview.get(src_row * h);
+    decode_opened(ctx, o, DecDst{nullptr, nullptr, region, src_row, 0, true}, win);
+    GkViewArgs va{};
+    va.src = region;
+    va.rw = va.ow = w; va.rh = va.oh = h; va.nch = nin;
+    render_launch(ctx, ctx->dec_render, va, cout, pixels, row_bytes, out_on_device);
+}
+
 // The decode: the window path at the chosen reduce level writes the reduced region as packed int32
 // pixels into ctx->dview (what gk_decode_window_pixels returns with sample_bytes 0 under
-// gk_set_decode_reduce(r)), and k_view (gk_view.hip) writes the caller's pixels from it.
+// gk_set_decode_reduce(r)), and k_view (gk_view.hip) writes the caller's pixels from it; under a
+// render k_render (gk_render.hip) does, and gk_decode_levels runs k_levels over it instead.
+static void* view_region(gk_ctx* ctx, DecStream& o, const ViewPlan& V) {
+    const gk_view_result& R = V.res;
+    const uint32_t rw = R.rx1 - R.rx0, rh = R.ry1 - R.ry0;
+    const size_t src_row = (size_t)rw * R.channels * 4;
+    void* region = ctx->dview.get(src_row * rh);
+    // the window path at the view's reduce level; the sticky one (0) is back whatever happens
+    struct Reduce {
+        gk_ctx* c;
+        Reduce(gk_ctx* c_, uint32_t r) : c(c_) { c->dec_reduce = r; }
+        ~Reduce() { c->dec_reduce = 0; }
+    } reduce(ctx, R.reduce);
+    decode_opened(ctx, o, DecDst{nullptr, nullptr, region, src_row, 0, true}, V.whole ? nullptr : V.win);
+    return region;
+}
 static void view_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, void* pixels, size_t row_bytes, uint32_t sample_bytes,
                       bool out_on_device, gk_view_result* res) {
     if (ctx->dec_reduce)
@@ -6339,6 +6479,19 @@ static void view_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, void* pi
     open_stream(o, src, st, true);
     const ViewPlan V = resolve_view(o, ctx->dec_colour, ctx->dec_display, ctx->dec_prec, v);
     const gk_view_result& R = V.res;
+    const uint32_t rw = R.rx1 - R.rx0, rh = R.ry1 - R.ry0;
+    if (ctx->dec_render.mode) {   // the rendered view: bytes of C or 3 channels
+        const uint32_t cout = render_channels(ctx->dec_render, R.channels);
+        render_buffer(sample_bytes, row_bytes, (size_t)R.pix_w * cout);
+        if ((uint64_t)((R.out_w + 15) / 16) * ((R.out_h + 15) / 16) > GK_VIEW_MAX_TILES) throw GkError("view: an output of 2^24 tiles of 16 x 16 pixels or more is too large for one launch");
+        GkViewArgs va{};
+        va.src = view_region(ctx, o, V);
+        va.rw = rw; va.rh = rh; va.ow = R.out_w; va.oh = R.out_h; va.nch = R.channels;
+        va.mirror = v.mirror; va.rot = v.rotate / 90;
+        render_launch(ctx, ctx->dec_render, va, cout, pixels, row_bytes, out_on_device);
+        if (res) { *res = R; res->channels = cout; res->prec = 8; res->sgnd = 0; }
+        return;
+    }
     const int dtype = output_sample_type(V.D, sample_bytes);
     const size_t es = gk_sample_size(dtype), C = R.channels;
     const size_t tight = (size_t)R.pix_w * C * es;
@@ -6346,17 +6499,7 @@ static void view_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, void* pi
     if (row_bytes % es) throw GkError("pixels: row_bytes must be a multiple of the sample size");
     if (out_on_device && ((uintptr_t)pixels % es)) throw GkError("pixels: the buffer is not aligned to its sample size");
     if ((uint64_t)((R.out_w + 15) / 16) * ((R.out_h + 15) / 16) > GK_VIEW_MAX_TILES) throw GkError("view: an output of 2^24 tiles of 16 x 16 pixels or more is too large for one launch");
-    const uint32_t rw = R.rx1 - R.rx0, rh = R.ry1 - R.ry0;
-    const size_t src_row = (size_t)rw * C * 4;
-    void* region = ctx->dview.get(src_row * rh);
-    {   // the window path at the view's reduce level; the sticky one (0) is back whatever happens
-        struct Reduce {
-            gk_ctx* c;
-            Reduce(gk_ctx* c_, uint32_t r) : c(c_) { c->dec_reduce = r; }
-            ~Reduce() { c->dec_reduce = 0; }
-        } reduce(ctx, R.reduce);
-        decode_opened(ctx, o, DecDst{nullptr, nullptr, region, src_row, 0, true}, V.whole ? nullptr : V.win);
-    }
+    void* region = view_region(ctx, o, V);
     const size_t pitch = (tight + 15) & ~(size_t)15;
     GkViewArgs a{};
     a.src = region;
@@ -6372,6 +6515,62 @@ static void view_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, void* pi
     HIPCHK(hipStreamSynchronize(st));
     const float ms = ev_ms(ctx, 24, 25);   // the view pass counts as sample stage, as the output pass does
     ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+    if (res) *res = R;
+}
+// gk_decode_levels: the view's int32 pixels are never written; k_levels (gk_render.hip) folds them
+// into ctx->dlevels, 16 GkLevelsStat and then channels * bins uint64 counters, which this call
+// initialises, reads back and leaves behind as scratch
+static void levels_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, const gk_levels_bins* q, uint32_t nq, uint32_t bins,
+                        gk_channel_levels* stats, uint64_t* hist, size_t hist_cap, gk_view_result* res) {
+    if (ctx->dec_reduce)
+        throw GkError("view: gk_set_decode_reduce is set (a view chooses the reduce level itself): set it to 0");
+    if (bins > GK_LEVELS_MAX_BINS) throw GkError("levels: " + std::to_string(bins) + " bins (at most " + std::to_string(GK_LEVELS_MAX_BINS) + ")");
+    if (nq && !q) throw GkError("levels: no bin entries");
+    for (uint32_t k = 0; k < nq; ++k)
+        if (q[k].shift > 31) throw GkError("levels: entry " + std::to_string(k) + " has a shift of " + std::to_string(q[k].shift) + " (at most 31)");
+    if (bins && !hist) throw GkError("levels: bins without a histogram buffer");
+    hipStream_t st = ctx->st;
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    DecStream o;
+    open_stream(o, src, st, true);
+    const ViewPlan V = resolve_view(o, ctx->dec_colour, ctx->dec_display, ctx->dec_prec, v);
+    const gk_view_result& R = V.res;
+    const uint32_t C = R.channels;
+    if (bins && hist_cap < (size_t)C * bins)
+        throw GkError("levels: hist_cap " + std::to_string(hist_cap) + " is below channels * bins = " + std::to_string((size_t)C * bins));
+    if ((uint64_t)((R.out_w + 15) / 16) * ((R.out_h + 15) / 16) > GK_VIEW_MAX_TILES) throw GkError("view: an output of 2^24 tiles of 16 x 16 pixels or more is too large for one launch");
+    GkLevelsArgs a{};
+    a.v.src = view_region(ctx, o, V);
+    a.v.rw = R.rx1 - R.rx0; a.v.rh = R.ry1 - R.ry0; a.v.ow = R.out_w; a.v.oh = R.out_h; a.v.nch = C;
+    for (uint32_t k = 0; k < C; ++k) {
+        if (nq) { const gk_levels_bins& e = q[std::min(k, nq - 1)]; a.origin[k] = e.origin; a.shift[k] = e.shift; }
+    }
+    const size_t stat_bytes = GK_PIX_MAX_CH * sizeof(GkLevelsStat), hist_bytes = (size_t)C * bins * 8, total = stat_bytes + hist_bytes;
+    uint8_t* dl = (uint8_t*)ctx->dlevels.get(total);
+    ctx->levels_host.assign(total, 0);
+    for (uint32_t k = 0; k < GK_PIX_MAX_CH; ++k) {
+        const GkLevelsStat s0{INT32_MAX, INT32_MIN, 0};
+        memcpy(ctx->levels_host.data() + k * sizeof(GkLevelsStat), &s0, sizeof(s0));
+    }
+    HIPCHK(hipMemcpyAsync(dl, ctx->levels_host.data(), stat_bytes, hipMemcpyHostToDevice, st));
+    if (hist_bytes) HIPCHK(hipMemsetAsync(dl + stat_bytes, 0, hist_bytes, st));
+    a.stats = (GkLevelsStat*)dl; a.hist = (unsigned long long*)(dl + stat_bytes); a.bins = bins;
+    HIPCHK(hipEventRecord(ctx->ev[24], st));
+    if (gk_launch_levels(st, a)) throw GkError("internal: levels geometry");
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[25], st));
+    HIPCHK(hipMemcpyAsync(ctx->levels_host.data(), dl, total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const float ms = ev_ms(ctx, 24, 25);   // counts as sample stage, as the view pass does
+    ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+    for (uint32_t k = 0; k < C; ++k) {
+        GkLevelsStat s;
+        memcpy(&s, ctx->levels_host.data() + k * sizeof(GkLevelsStat), sizeof(s));
+        stats[k].min = s.min; stats[k].max = s.max; stats[k].sum = (int64_t)s.sum;
+        stats[k].count = (uint64_t)R.pix_w * R.pix_h;
+    }
+    if (hist_bytes) memcpy(hist, ctx->levels_host.data() + stat_bytes, hist_bytes);
     if (res) *res = R;
 }
 
@@ -7911,14 +8110,19 @@ int gk_decode_header(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
         ColourOut out = stream_channels(o, ctx->dec_colour);
         // (display flags: the whole image's output; a refusal that depends on a window is the decode's)
         DisplayOut disp = resolve_display(col, out, Hd.want, ctx->dec_display, ctx->dec_reduce, nullptr, &ctx->dec_prec);
+        // (a render: the pixel calls' output, C or 3 unsigned 8-bit channels on channel min(k, C - 1)'s grid)
+        const uint32_t nd = (uint32_t)disp.ch.size();
+        const uint32_t n = ctx->dec_render.mode ? render_channels(ctx->dec_render, nd) : nd;
         fill_image_info(info, Hd, out, &disp);
-        const uint32_t n = (uint32_t)disp.ch.size();
+        if (ctx->dec_render.mode) { info->numcomps = n; info->prec = 8; info->sgnd = 0; }
         ctx->hdr_dx.assign(n, 1); ctx->hdr_dy.assign(n, 1);
         ctx->hdr_prec.assign(n, 0); ctx->hdr_sgnd.assign(n, 0);
         for (uint32_t k = 0; k < n; ++k) {
-            ctx->hdr_dx[k] = disp.ch[k].dx; ctx->hdr_dy[k] = disp.ch[k].dy;
-            ctx->hdr_prec[k] = disp.ch[k].prec; ctx->hdr_sgnd[k] = disp.ch[k].sgnd;
+            const DisplayOut::Ch& h = disp.ch[std::min(k, nd - 1)];
+            ctx->hdr_dx[k] = h.dx; ctx->hdr_dy[k] = h.dy;
+            ctx->hdr_prec[k] = ctx->dec_render.mode ? 8 : h.prec; ctx->hdr_sgnd[k] = ctx->dec_render.mode ? 0 : h.sgnd;
         }
+        ctx->hdr_render = ctx->dec_render.mode;
         ctx->hdr_col = std::move(col); ctx->hdr_out = std::move(out); ctx->hdr_ncs = Hd.want.nc;
         ctx->hdr_disp = std::move(disp);
         return 0;
@@ -7932,6 +8136,10 @@ int gk_header_colour(gk_ctx* ctx, gk_colour_info* ci) {
     if (!ctx || !ci) return -1;
     if (!ctx->hdr_ncs) { ctx->err = "gk_header_colour: no header has been read"; return -1; }
     fill_colour_info(ci, ctx->hdr_col, ctx->hdr_out, ctx->hdr_ncs, ctx->dec_display ? &ctx->hdr_disp : nullptr);   // (a list changes nothing here)
+    if (ctx->hdr_render == GK_RENDER_MAP || ctx->hdr_render == GK_RENDER_BLEND) {   // the rendered output: R, G, B
+        ci->colour_space = 2; ci->num_channels = 3;
+        for (uint32_t k = 0; k < 3; ++k) { ci->typ[k] = 0; ci->asoc[k] = (uint16_t)(k + 1); }
+    }
     return 0;
 }
 
@@ -8314,10 +8522,14 @@ int gk_probe_header(const uint8_t* cs, size_t len, gk_image_info* info, gk_cpara
 static int decode_entry(gk_ctx* ctx, const DecSrc& src, const DecDst& dst, const uint32_t* win) {
     if (!ctx || !src.cs || (!dst.pixels && (!dst.comps || !dst.strides))) return -1;
     try {
+        if (ctx->dec_render.mode && !dst.pixels)
+            throw GkError(std::string(win ? "gk_decode_window" : "gk_decode") +
+                          ": gk_set_decode_render is set (it renders packed pixels: use the pixel calls, or clear it)");
         (void)hipSetDevice(ctx->device);
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
-        decode_call(ctx, src, dst, win);
+        if (ctx->dec_render.mode) render_pixels_call(ctx, src, win, dst.pixels, dst.row_bytes, dst.sample_bytes, dst.on_device);
+        else decode_call(ctx, src, dst, win);
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;
@@ -8520,6 +8732,59 @@ int gk_decode_view_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
         view_call(ctx, DecSrc{cs, len, cs_on_device != 0}, *v, pixels, row_bytes, sample_bytes, out_on_device != 0, res);
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_set_decode_render(gk_ctx* ctx, const gk_render* r) {
+    if (!ctx) return -1;
+    try {
+        DecRender R = checked_render(r);   // (a refusal leaves the previous description)
+        ctx->dec_render = std::move(R);
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+int gk_probe_render(const uint8_t* cs, size_t len, uint32_t display_flags, const gk_precision* list, uint32_t n, const gk_render* r,
+                    gk_render_result* res, char* msg, size_t msg_cap) {
+    if (!cs) return -1;
+    try {
+        if (display_flags & ~(GK_DISPLAY_RGB | GK_DISPLAY_UPSAMPLE | GK_DISPLAY_FORCE_RGB | GK_DISPLAY_ICC)) throw GkError("gk_probe_render: unknown flags");
+        if (n && !list) throw GkError("gk_probe_render: no list");
+        const std::vector<gk_precision> plist(list, list + n);
+        const DecRender R = checked_render(r);
+        DecStream o;
+        open_stream(o, DecSrc{cs, len, false}, nullptr, true);
+        const DisplayOut disp = resolve_display(o.col, stream_channels(o, true), o.Hd.want, display_flags, 0, nullptr, &plist);
+        const uint32_t nd = (uint32_t)disp.ch.size();
+        if (nd > GK_PIX_MAX_CH)
+            throw GkError("pixels: " + std::to_string(nd) + " output channels (at most " + std::to_string(GK_PIX_MAX_CH) +
+                          "): use the planar calls gk_decode / gk_decode_window");
+        gk_render_result out{nd, disp.max_prec(), disp.ch[0].sgnd, display_flags ? disp.colour_space : o.col.colour_space(o.Hd.want.nc)};
+        if (R.mode) {
+            out.channels = render_channels(R, nd); out.prec = 8; out.sgnd = 0;
+            if (R.mode != GK_RENDER_WINDOW) out.colour_space = 2;
+        }
+        if (res) *res = out;
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
+        return -1;
+    }
+}
+int gk_decode_levels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_view* v, const gk_levels_bins* q,
+                     uint32_t nq, uint32_t bins, gk_channel_levels* stats, uint64_t* hist, size_t hist_cap, gk_view_result* res) {
+    if (!ctx || !cs || !v || !stats) return -1;
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
+        levels_call(ctx, DecSrc{cs, len, cs_on_device != 0}, *v, q, nq, bins, stats, hist, hist_cap, res);
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;

@@ -235,6 +235,46 @@ struct GkViewArgs {
 };
 // dtype: GK_U8, GK_U16 or GK_S32 pixels out
 int gk_launch_view(hipStream_t st, int dtype, const GkViewArgs& args);
+// The view's last stage under gk_set_decode_render (gk_render.hip, k_render): the geometry and the
+// area average of k_view, then per channel the window (lo < hi; inv: the caller gave hi < lo)
+//     t = floor((2 * 255 * (clamp(v, lo, hi) - lo) + (hi - lo)) / (2 (hi - lo))),  inv: 255 - t,
+// the optional curve, and the mode: GK_RENDER_WINDOW writes nch bytes a pixel, GK_RENDER_MAP
+// (nch == 1) the three bytes map[3 t + c], GK_RENDER_BLEND min(255, (2 sum_k t_k tint_k,c + 255) /
+// 510).  tables: 1024 device bytes, 4-byte aligned: the curve (256), then the map (768); read only
+// when has_curve / mode MAP say so.  The written image has out_ch (nch or 3) bytes a pixel.
+#define GK_RENDER_TABLE_BYTES 1024u
+enum GkRenderMode { GK_RMODE_WINDOW = 1, GK_RMODE_MAP = 2, GK_RMODE_BLEND = 3 };   // gk_render::mode (grok_amd.h)
+struct GkRenderChan {
+    int32_t lo, hi;            // lo < hi
+    uint8_t tint[3];
+    uint8_t inv;
+};
+struct GkRenderArgs {
+    GkViewArgs v;              // (dst: uint8 pixels of out_ch channels; row_bytes in bytes)
+    GkRenderChan ch[GK_PIX_MAX_CH];
+    const uint8_t* tables;
+    uint32_t mode, has_curve;
+    uint32_t out_ch;           // (set by the launcher)
+};
+int gk_launch_render(hipStream_t st, const GkRenderArgs& args);
+// Statistics of the pixels a view returns as int32 (gk_render.hip, k_levels): per channel k
+// stats[k] = {min, max, sum} and, when bins > 0, hist[k * bins + clamp((v - origin_k) >> shift_k,
+// 0, bins - 1)] += 1.  stats must hold {INT32_MAX, INT32_MIN, 0} per channel and hist zeros before
+// the launch; both are only ever added to.  bins <= GK_LEVELS_BINS_MAX, shift <= 31.
+#define GK_LEVELS_BINS_MAX 4096u
+struct GkLevelsStat {
+    int32_t min, max;
+    unsigned long long sum;    // the int64 sum's bits (two's complement)
+};
+struct GkLevelsArgs {
+    GkViewArgs v;              // (dst, row_bytes, mirror, rot unused)
+    int32_t origin[GK_PIX_MAX_CH];
+    uint32_t shift[GK_PIX_MAX_CH];
+    GkLevelsStat* stats;
+    unsigned long long* hist;
+    uint32_t bins;
+};
+int gk_launch_levels(hipStream_t st, const GkLevelsArgs& args);
 // Input stage of an encode from packed pixels (gk_unpixels.hip): sample k of pixel (x, y) is read
 // at src + y * row_bytes + (x * nch + k) * es and written to plane k, dst + k * plane samples on,
 // row stride ds samples, in the same sample type.  The planes are the engine's own: dst, ds and

@@ -3,13 +3,7 @@
 // written as the caller's packed pixels.
 //
 // The rule (tests/view_ref.py is the same arithmetic in numpy) is an exact area
-// average in integers.  In units of 1 / ow a source column is ow long and an output column rw:
-// output column i covers [i rw, (i + 1) rw), source column s covers [s ow, (s + 1) ow), and the
-// weight wx(i, s) is the length of their overlap; rows alike with rh and oh.  A column's weights
-// sum to rw and a row's to rh, so
-//     out = floor((2 sum(wy wx v) + rw rh) / (2 rw rh))
-// per channel in signed 64-bit integers: floor division, halves round up.  The engine refuses a
-// source with (rw rh) << prec >= 2^62, so 2 sum + rw rh stays inside an int64.
+// average in integers; gk_area.h states it and holds its one definition.
 //
 // Shape.  A 256-thread block owns a 16 x 16 tile of the output in pre-rotation coordinates, so its
 // source footprint is one compact rectangle (at the reduce level the engine chooses a pixel's span
@@ -31,18 +25,11 @@
 #include <stdint.h>
 #include "gk_common.h"
 #include "gk_launch.h"
+#include "gk_area.h"
 
 namespace {
-constexpr int TILE = 16;
-constexpr int CG = 4;   // channels accumulated per walk over the footprint
-
-// floor((2 a + d) / (2 d)), d > 0
-__device__ __forceinline__ int64_t round_div(int64_t a, int64_t d) {
-    const int64_t num = 2 * a + d, den = 2 * d;
-    int64_t q = num / den;
-    if (num - q * den < 0) --q;
-    return q;
-}
+constexpr int TILE = GK_AREA_TILE;
+constexpr int CG = GK_AREA_CG;   // channels accumulated per walk over the footprint
 
 template <typename DST>
 __global__ __launch_bounds__(256) void k_view(GkViewArgs a) {
@@ -70,32 +57,14 @@ __global__ __launch_bounds__(256) void k_view(GkViewArgs a) {
         for (uint32_t k = 0; k < C; ++k) d[k] = (DST)s[k];
         return;
     }
-    // the spans: source columns [s0, s1], rows [t0, t1] overlap the pixel
-    const uint64_t xa = (uint64_t)i * a.rw, xb = xa + a.rw, ya = (uint64_t)j * a.rh, yb = ya + a.rh;
-    const uint32_t s0 = (uint32_t)(xa / a.ow), s1 = min((uint32_t)((xb - 1) / a.ow), a.rw - 1);
-    const uint32_t t0 = (uint32_t)(ya / a.oh), t1 = min((uint32_t)((yb - 1) / a.oh), a.rh - 1);
-    const int64_t den = (int64_t)((uint64_t)a.rw * a.rh);
+    // the spans, the weights and the rounding: gk_area.h, shared with k_render and k_levels
+    const GkAreaSpan p = gk_area_span(a.rw, a.rh, a.ow, a.oh, i, j);
     for (uint32_t c0 = 0; c0 < C; c0 += CG) {
-        int64_t acc[CG] = {0, 0, 0, 0};
-        for (uint32_t t = t0; t <= t1; ++t) {
-            const uint64_t ta = (uint64_t)t * a.oh;
-            const int64_t wy = (int64_t)(min(yb, ta + a.oh) - max(ya, ta));
-            const int32_t* row = src + (size_t)t * a.rw * C + c0;
-            int64_t racc[CG] = {0, 0, 0, 0};
-            for (uint32_t s = s0; s <= s1; ++s) {
-                const uint64_t sa = (uint64_t)s * a.ow;
-                const int64_t wx = (int64_t)(min(xb, sa + a.ow) - max(xa, sa));
-                const int32_t* p = row + (size_t)s * C;
-#pragma unroll
-                for (int k = 0; k < CG; ++k)
-                    if (c0 + k < C) racc[k] += wx * (int64_t)p[k];
-            }
-#pragma unroll
-            for (int k = 0; k < CG; ++k) acc[k] += wy * racc[k];
-        }
+        int64_t acc[CG];
+        gk_area_sum(src, p, a.rw, a.ow, a.oh, C, c0, acc);
 #pragma unroll
         for (int k = 0; k < CG; ++k)
-            if (c0 + k < C) d[c0 + k] = (DST)round_div(acc[k], den);
+            if (c0 + k < C) d[c0 + k] = (DST)gk_round_div(acc[k], p.den);
     }
 }
 }  // namespace

@@ -678,6 +678,83 @@ int gk_decode_view_pixels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_
                           void* pixels, size_t row_bytes, uint32_t sample_bytes, int out_on_device,
                           gk_view_result* res /* may be NULL */);
 
+/* Render for display: the int32 pixels of the pixel calls (gk_decode_pixels,
+ * gk_decode_window_pixels, gk_decode_view_pixels) become unsigned 8-bit display pixels on the
+ * device, by the engine's own integer rule (Grok's CLI stops at -p).  Sticky and
+ * copied in; NULL or mode 0 clears it; a refused description leaves the previous one.
+ * Input: the int32 sample v of output channel k exactly as the same call delivers it with
+ * sample_bytes 0 and no render (after colour boxes, display flags and the precision list; for a
+ * view after the area average).  Channel k takes entry min(k, n - 1) of ch.
+ * Window (lo, hi), lo < hi, any int32 pair, in signed 64-bit integers:
+ *   u = min(max(v, lo), hi),  t = floor((2 * 255 * (u - lo) + (hi - lo)) / (2 * (hi - lo)))
+ * (0, 4095): 2048 -> 128, 8 -> 0, 9 -> 1, 4095 -> 255.  lo > hi inverts: t = 255 - level(v; hi, lo)
+ * (MONOCHROME1).  lo == hi is refused.  For a centre c and width w use lo = c - w / 2,
+ * hi = c + w / 2 with your own rounding: the engine takes the two ends as they are.
+ * curve: NULL or 256 bytes, t = curve[t] (gamma, sigmoid: tables the caller builds).
+ * GK_RENDER_WINDOW: C channels in, C out, out_k = t_k.
+ * GK_RENDER_MAP: exactly one channel in, three out, out_c = map[3 t + c] (map: 768 bytes).
+ * GK_RENDER_BLEND: 1..16 channels in, three out, out_c = min(255, floor((2 sum_k t_k tint_k,c +
+ * 255) / 510)); a channel whose tint is (0, 0, 0) is left out.
+ * While it is set sample_bytes must be 1, the header calls (gk_decode_header,
+ * gk_header_components, gk_header_colour) and gk_view_result describe the output (C or 3
+ * channels, precision 8, unsigned; sRGB under MAP / BLEND), and the planar calls gk_decode /
+ * gk_decode_window refuse by name.  Refused here, each by name: a mode above 3; n of 0 or above
+ * 16; no ch; lo == hi (the entry is named); MAP without a map; BLEND with every tint zero.  Refused
+ * by the header, probe and decode calls, before anything is allocated or launched: MAP on a
+ * channel count other than 1; BLEND whose channels' tints are all zero; more than 16 channels; a
+ * sample_bytes other than 1. */
+#define GK_RENDER_WINDOW 1u
+#define GK_RENDER_MAP 2u
+#define GK_RENDER_BLEND 3u
+#define GK_RENDER_MAX_CHANNELS 16u
+typedef struct gk_render_channel {
+    int32_t lo, hi;
+    uint8_t tint[3];           /* BLEND: r, g, b in 0..255 */
+} gk_render_channel;
+typedef struct gk_render {
+    uint32_t mode;             /* 0: none */
+    uint32_t n;                /* entries of ch, 1..16 */
+    const gk_render_channel* ch;
+    const uint8_t* curve;      /* NULL or 256 bytes */
+    const uint8_t* map;        /* MAP: 256 x 3 bytes */
+} gk_render;
+int gk_set_decode_render(gk_ctx* ctx, const gk_render* r);
+typedef struct gk_render_result {
+    uint32_t channels, prec, sgnd;   /* of the rendered output: C or 3, 8, 0 */
+    uint32_t colour_space;           /* GRK_COLOR_SPACE: sRGB (2) under MAP / BLEND, else the unrendered output's */
+} gk_render_result;
+/* What the pixel calls return for host bytes under these display flags, this precision list
+ * (n = 0: none) and this render description (NULL or mode 0: none), no device needed: 0 and *res,
+ * or -1 with the refusal in msg. */
+int gk_probe_render(const uint8_t* cs, size_t len, uint32_t display_flags, const gk_precision* list, uint32_t n,
+                    const gk_render* r, gk_render_result* res, char* msg, size_t msg_cap);
+
+/* Where a view's values lie: the view is resolved and decoded exactly as gk_decode_view_pixels does
+ * (same reduce level, same sticky settings; a sticky render is ignored here, so it can stay set
+ * while the window is re-measured), no pixels are written, and per output channel k stats[k]
+ * receives min, max, sum and count (= pix_w * pix_h) of exactly the int32 pixels the same view
+ * returns.  bins > 0: hist[k * bins + b] counts the pixels with
+ *   b = clamp(floor((v - origin_k) / 2^shift_k), 0, bins - 1),
+ * channel k taking entry min(k, nq - 1) of q (nq = 0: origin 0, shift 0); values outside the binned
+ * range fall into the end bins.  A 16-bit histogram at full resolution is two calls: min / max
+ * first, then origin = min and the smallest shift that fits.  stats holds res->channels entries
+ * (at most 16).  Refused by name, before anything is allocated or launched: bins above
+ * GK_LEVELS_MAX_BINS; a shift above 31; bins > 0 without hist, or hist_cap below channels * bins;
+ * everything gk_decode_view_pixels refuses. */
+#define GK_LEVELS_MAX_BINS 4096u
+typedef struct gk_levels_bins {
+    int32_t origin;
+    uint32_t shift;
+} gk_levels_bins;
+typedef struct gk_channel_levels {
+    int32_t min, max;
+    int64_t sum;
+    uint64_t count;
+} gk_channel_levels;
+int gk_decode_levels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_view* v,
+                     const gk_levels_bins* q, uint32_t nq, uint32_t bins, gk_channel_levels* stats, uint64_t* hist,
+                     size_t hist_cap, gk_view_result* res /* may be NULL */);
+
 /* Inverse 5/3 rule of later gk_decode_window calls.  whole_tile = 0 (default): Grok's partial-tile
  * inverse, which a window set through setDecompressWindow selects for every tile
  * (CodeStreamDecompress.cpp:389; a one-sample-wide resolution on an odd coordinate shifts its
