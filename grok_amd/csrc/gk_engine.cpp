@@ -4233,7 +4233,7 @@ static void dump_blocks(gk_ctx* ctx, const uint32_t* hinfo, const GkPass* dps, u
 struct PixSrc { const void* pixels; size_t row_bytes; int on_device; };
 
 // ---- Transcode (gk_transcode): Part-1 <-> HTJ2K at the block-coder level.  The source coder's
-// decoders leave signed quantisation indices in work plane A (decode_core stops after T1), the
+// decoders leave signed quantisation indices in work plane A (xcode_call runs decode_parse and decode_t1 only), the
 // target coder's encoders read them there (encode_impl starts at T1): no DWT, MCT or sample stage.
 struct Xcode {
     bool to_ht = true;
@@ -6774,78 +6774,97 @@ static void xcode_check_part(const Plan& P, const TilePart& TPt, const PartState
         }
 }
 
-// The decode proper of the tile parts in Hd.parts, whose coding is Hd's and ctx->plan's, into
-// out: packet headers (T2), code-blocks (T1), inverse DWT and MCT, egress.  rq.win is the
-// rectangle written (null: the tile parts' own) and (fx, fy) the image-relative origin of out's
-// planes: the window's, and for a tile pass the whole call's.
-// xc (a transcode): every tile of the image; the T1 decoders write quantisation indices and the
-// call returns after them (out is not written).
-static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, const DecReq& rq, uint32_t fx, uint32_t fy,
-                        HostClock::time_point h0, Xcode* xc = nullptr) {
-    hipStream_t st = ctx->st;
-    Plan& P = ctx->plan;
-    const uint8_t* const cs = S.dev ? S.dev : S.host;
-    const size_t len = S.len;
-    const bool cs_on_device = S.dev != nullptr, out_on_device = out.on_device;
-    void* const* comps = out.comps;
-    const uint32_t* strides = out.strides;
-    const uint32_t sample_bytes = out.sample_bytes, red = ctx->dec_reduce;
-    const uint32_t* win = rq.win;
-    // GK_PROFILE=1: host phase times of the decode (stderr)
-    static const bool prof = getenv("GK_PROFILE") != nullptr;
-    auto now = [] { return HostClock::now(); };
-    auto ms = [](HostClock::time_point a, HostClock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    if (S.dev) prefetch_packet_headers(ctx, S, P, Hd);
-    // ---- tiles present, their rectangle, and the code-blocks that reach the output
-    std::vector<int32_t> part_of(P.tiles.size(), -1);
-    for (size_t q = 0; q < Hd.parts.size(); ++q) {
-        const TilePart& TPt = Hd.parts[q];
-        if (TPt.tile >= P.tiles.size()) throw GkError("corrupt SOT (tile index)");
-        if (part_of[TPt.tile] >= 0) throw GkError("corrupt stream (tile parts of one tile merged twice)");
-        part_of[TPt.tile] = (int32_t)q;
+// ---- The stages of the decode core, each a function of what it reads.  decode_parse, decode_t1
+// and decode_core below run them in order; a transcode (xcode_call) stops after T1.
+namespace {
+// The tiles a call decodes and the rectangle it writes
+struct TileRect {
+    uint32_t ib = 0, ie = 0, jb = 0, je = 0;       // tiles [ib, ie) x [jb, je)
+    std::vector<int32_t> part_of;                  // tile -> its entry of the tile parts (-1: none)
+    Region RG;                                     // the tiles' region (image-relative): the work planes
+    std::vector<Region> RGg;                       // RG on each sampling group's grid (RG itself without subsampling)
+    uint32_t rx0 = 0, ry0 = 0, rx1 = 0, ry1 = 0;   // the output rectangle: RG clipped to the window
+};
+// The decode table's figures: the needed blocks of the rectangle's tiles, compacted
+struct BlockTable {
+    uint32_t nblk = 0;
+    uint64_t staged = 0, t1_bytes = 0;             // bytes of the staging slots; compressed bytes of the blocks
+    std::vector<uint32_t> seglen;                  // BYPASS / TERMALL: segment lengths, a block's at G.data_cap
+    std::vector<std::vector<int32_t>> part_idx;    // per tile part: tile-local block -> table entry (-1: none)
+};
+// The lane decoder's host tables in one buffer: slot -> block (0xffffffff: none), block -> slot,
+// the identity (compact table) and the scratch offset of every wave (hwo[nw]: the total)
+struct LaneTables {
+    uint32_t nsw = 0, nw = 0, nslots = 0, nbr = 0;   // nsw: solo waves, rounded up to whole workgroups of 12
+    uint32_t *ord = nullptr, *pos = nullptr, *ids = nullptr;
+    uint64_t* wo = nullptr;
+    LaneTables() = default;
+    // sized for nbr blocks, nsb of them in the solo waves `bins`, at L lanes per lane-parallel wave
+    LaneTables(const std::vector<std::vector<uint32_t>>& bins, uint32_t nbr_, uint32_t nsb, uint32_t L) : nbr(nbr_) {
+        for (uint32_t b = 0; b < bins.size(); ++b)
+            if (!bins[b].empty()) nsw = b + 1;
+        nsw = (nsw + 11) / 12 * 12;
+        nw = nsw + (nbr - nsb + L - 1) / L;
+        nslots = nw * 64;
     }
-    uint32_t ib = P.ntx, ie = 0, jb = P.nty, je = 0;
-    for (const TilePart& TPt : Hd.parts) {
+    size_t bytes() const { return 4 * ((size_t)nslots + 2 * (size_t)nbr + 2) + 8 * ((size_t)nw + 1); }
+    void bind(void* buf) { ord = (uint32_t*)buf; pos = ord + nslots; ids = pos + nbr; wo = (uint64_t*)(ids + nbr + 2); }
+};
+// Component c's output: its rectangle on its reduced grid (less the reduced image origin rox,
+// roy) and the caller plane's origin there
+struct CompRect { uint32_t x0, y0, x1, y1, wx0, wy0, rox, roy; };
+struct OutRects { std::vector<CompRect> c; bool win_empty = false; };   // win_empty: the window holds no sample of some component
+}  // namespace
+
+// The tiles present and their rectangle (whole_image: every tile of the image).  Work planes
+// cover the tile rectangle only (tiles of the rectangle without a tile part decode as zero); the
+// output region is the rectangle, clipped to the window.
+static TileRect tile_rect(const Plan& P, const std::vector<TilePart>& parts, const uint32_t* win, bool whole_image) {
+    TileRect TR;
+    TR.part_of.assign(P.tiles.size(), -1);
+    for (size_t q = 0; q < parts.size(); ++q) {
+        const uint32_t t = parts[q].tile;
+        if (t >= P.tiles.size()) throw GkError("corrupt SOT (tile index)");
+        if (TR.part_of[t] >= 0) throw GkError("corrupt stream (tile parts of one tile merged twice)");
+        TR.part_of[t] = (int32_t)q;
+    }
+    TR.ib = P.ntx; TR.jb = P.nty;
+    for (const TilePart& TPt : parts) {
         const uint32_t t = TPt.tile;
-        ib = std::min(ib, t % P.ntx); ie = std::max(ie, t % P.ntx + 1);
-        jb = std::min(jb, t / P.ntx); je = std::max(je, t / P.ntx + 1);
+        TR.ib = std::min(TR.ib, t % P.ntx); TR.ie = std::max(TR.ie, t % P.ntx + 1);
+        TR.jb = std::min(TR.jb, t / P.ntx); TR.je = std::max(TR.je, t / P.ntx + 1);
     }
-    if (xc) { ib = 0; ie = P.ntx; jb = 0; je = P.nty; }   // the planes the encoders read hold the image
-    // work planes cover the tile rectangle only (tiles of the rectangle without a tile part
-    // decode as zero); the output region is the rectangle, clipped to the window
-    const TileG& Tfirst = P.tiles[(size_t)jb * P.ntx + ib];
-    const TileG& Tlast = P.tiles[(size_t)(je - 1) * P.ntx + ie - 1];
-    const Region RG = make_region(Tfirst.x0 - P.x0, Tfirst.y0 - P.y0, Tlast.x1 - P.x0, Tlast.y1 - P.y0);   // image-relative
-    uint32_t rx0 = RG.x0, ry0 = RG.y0, rx1 = RG.x0 + RG.w, ry1 = RG.y0 + RG.h;
+    if (whole_image) { TR.ib = 0; TR.ie = P.ntx; TR.jb = 0; TR.je = P.nty; }
+    const TileG& Tfirst = P.tiles[(size_t)TR.jb * P.ntx + TR.ib];
+    const TileG& Tlast = P.tiles[(size_t)(TR.je - 1) * P.ntx + TR.ie - 1];
+    TR.RG = make_region(Tfirst.x0 - P.x0, Tfirst.y0 - P.y0, Tlast.x1 - P.x0, Tlast.y1 - P.y0);
+    TR.rx0 = TR.RG.x0; TR.ry0 = TR.RG.y0; TR.rx1 = TR.RG.x0 + TR.RG.w; TR.ry1 = TR.RG.y0 + TR.RG.h;
     if (win) {
-        rx0 = std::max(rx0, win[0]); ry0 = std::max(ry0, win[1]); rx1 = std::min(rx1, win[2]); ry1 = std::min(ry1, win[3]);
+        TR.rx0 = std::max(TR.rx0, win[0]); TR.ry0 = std::max(TR.ry0, win[1]);
+        TR.rx1 = std::min(TR.rx1, win[2]); TR.ry1 = std::min(TR.ry1, win[3]);
     }
-    const uint32_t ox = fx, oy = fy;
-    const uint32_t ncols = rx1 - rx0, nrows = ry1 - ry0;
-    // the region on each sampling group's grid (RG itself without subsampling)
-    std::vector<Region> RGg;
-    for (const SGroup& G : P.groups) RGg.push_back(group_region(P, RG, G));
-    // Per tile: which code-blocks reach [rx0, rx1) x [ry0, ry1).  Inverse lifting reconstructs
-    // sample n of a level from low/high coefficients within a few positions of n/2 (5/3: the
-    // update/predict steps reach one neighbour each; 9/7: four steps), so the coefficients a
-    // window needs at each level are its projection padded by that reach, clamped to the band
-    // (the padded band window of TileComponentWindowBuffer / T2Decompress.cpp:55-116).  Blocks
-    // outside are not decoded (their samples only feed outputs outside the window), and with
-    // PLT a packet none of whose blocks is needed is skipped unparsed.
-    // (on the canvas: the output rectangle moved by the image origin)
-    const uint32_t cx0 = rx0 + P.x0, cy0 = ry0 + P.y0, cx1 = rx1 + P.x0, cy1 = ry1 + P.y0;
-    auto block_needed = [&](const TileG& T, std::vector<uint8_t>& need) {
-        need.assign(T.b1 - T.b0, 1);
-        if (!win || (cx0 <= T.x0 && T.x1 <= cx1 && cy0 <= T.y0 && T.y1 <= cy1)) return;
-        // per sampling group (its grid, levels and transform; the components of a group share
-        // their geometry): lo[a][l], hi[a][l] = needed [begin, end) in level-l low / high band
-        // coordinates, axis a
-        const size_t ng = P.groups.size();
-        std::vector<std::array<std::array<std::array<uint32_t, 2>, GK_MAXRLVLS + 1>, 2>> LO(ng), HI(ng);
-        std::vector<uint8_t> done(ng, 0);
-        for (uint32_t c = 0; c < P.nc; ++c) {
+    for (const SGroup& G : P.groups) TR.RGg.push_back(group_region(P, TR.RG, G));
+    return TR;
+}
+
+// Which code-blocks of tile T reach the canvas window cw = [cw[0], cw[2]) x [cw[1], cw[3])
+// (null: all do).  Inverse lifting reconstructs
+// sample n of a level from low/high coefficients within a few positions of n/2 (5/3: the
+// update/predict steps reach one neighbour each; 9/7: four steps), so the coefficients a
+// window needs at each level are its projection padded by that reach, clamped to the band
+// (the padded band window of TileComponentWindowBuffer / T2Decompress.cpp:55-116).  Blocks
+// outside are not decoded (their samples only feed outputs outside the window), and with
+// PLT a packet none of whose blocks is needed is skipped unparsed.
+static void blocks_needed(const Plan& P, const TileG& T, const uint32_t* cw, std::vector<uint8_t>& need) {
+    need.assign(T.b1 - T.b0, 1);
+    if (!cw || (cw[0] <= T.x0 && T.x1 <= cw[2] && cw[1] <= T.y0 && T.y1 <= cw[3])) return;
+    // per sampling group (its grid, levels and transform; the components of a group share
+    // their geometry): lo[a][l], hi[a][l] = needed [begin, end) in level-l low / high band
+    // coordinates, axis a
+    const size_t ng = P.groups.size();
+    std::vector<std::array<std::array<std::array<uint32_t, 2>, GK_MAXRLVLS + 1>, 2>> LO(ng), HI(ng);
+    std::vector<uint8_t> done(ng, 0);
+    for (uint32_t c = 0; c < P.nc; ++c) {
         const uint32_t g = P.group_of[c];
         if (done[g]) continue;
         done[g] = 1;
@@ -6857,8 +6876,8 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
         for (int ax = 0; ax < 2; ++ax) {
             // the window and the tile on the group's grid
             const uint32_t d = ax ? SG.dy : SG.dx;
-            uint32_t s0 = ceildiv(ax ? std::max(cy0, T.y0) : std::max(cx0, T.x0), d);
-            uint32_t s1 = ceildiv(ax ? std::min(cy1, T.y1) : std::min(cx1, T.x1), d);
+            uint32_t s0 = ceildiv(ax ? std::max(cw[1], T.y0) : std::max(cw[0], T.x0), d);
+            uint32_t s1 = ceildiv(ax ? std::min(cw[3], T.y1) : std::min(cw[2], T.x1), d);
             lo[ax][0][0] = s0; lo[ax][0][1] = s1;
             for (uint32_t l = 1; l <= Lv; ++l) {
                 const ResG& Rl = C0.res[SG.numres - l];       // resolution holding level-l bands
@@ -6872,190 +6891,161 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
                 s0 = lo[ax][l][0]; s1 = std::max(lo[ax][l][0], lo[ax][l][1]);
             }
         }
-        }
-        for (uint32_t c = 0; c < P.nc; ++c) {
-            const uint32_t g = P.group_of[c], nres = P.groups[g].numres;
-            const auto& lo = LO[g];
-            const auto& hi = HI[g];
-            for (uint32_t r = 0; r < nres; ++r) {
-                const ResG& R = T.comps[c].res[r];
-                const uint32_t lev = r ? nres - r : nres - 1;
-                for (uint32_t bi = 0; bi < R.bands.size(); ++bi) {
-                    const uint32_t o = R.bands[bi].orient;
-                    const uint32_t* nx = (o & 1) ? hi[0][lev].data() : lo[0][lev].data();
-                    const uint32_t* ny = (o & 2) ? hi[1][lev].data() : lo[1][lev].data();
-                    for (uint32_t pi = 0; pi < R.pw * R.ph; ++pi) {
-                        const PrecG& PG = R.prc[bi][pi];
-                        for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
-                            const uint32_t bb = PG.first_block + k;
-                            const GkBlock& G = P.blocks[bb];
-                            const uint32_t x = P.bxy[2 * (size_t)bb], y = P.bxy[2 * (size_t)bb + 1];
-                            need[bb - T.b0] = x < nx[1] && nx[0] < x + G.w && y < ny[1] && ny[0] < y + G.h;
-                        }
+    }
+    for (uint32_t c = 0; c < P.nc; ++c) {
+        const uint32_t g = P.group_of[c], nres = P.groups[g].numres;
+        const auto& lo = LO[g];
+        const auto& hi = HI[g];
+        for (uint32_t r = 0; r < nres; ++r) {
+            const ResG& R = T.comps[c].res[r];
+            const uint32_t lev = r ? nres - r : nres - 1;
+            for (uint32_t bi = 0; bi < R.bands.size(); ++bi) {
+                const uint32_t o = R.bands[bi].orient;
+                const uint32_t* nx = (o & 1) ? hi[0][lev].data() : lo[0][lev].data();
+                const uint32_t* ny = (o & 2) ? hi[1][lev].data() : lo[1][lev].data();
+                for (uint32_t pi = 0; pi < R.pw * R.ph; ++pi) {
+                    const PrecG& PG = R.prc[bi][pi];
+                    for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
+                        const uint32_t bb = PG.first_block + k;
+                        const GkBlock& G = P.blocks[bb];
+                        const uint32_t x = P.bxy[2 * (size_t)bb], y = P.bxy[2 * (size_t)bb + 1];
+                        need[bb - T.b0] = x < nx[1] && nx[0] < x + G.w && y < ny[1] && ny[0] < y + G.h;
                     }
                 }
             }
         }
-    };
-    std::vector<std::vector<uint8_t>> part_need(Hd.parts.size());
-    host_pool().run(Hd.parts.size(), [&](size_t q) { block_needed(P.tiles[Hd.parts[q].tile], part_need[q]); });
-    // ---- T2 (T2Decompress.cpp:216-570), LRCP, per tile part.  Tile parts are independent
-    // (own precincts, tag trees and code-blocks), so they are parsed in parallel host threads
-    // into tile-local state (index = block - tile's first block).
-    // BYPASS / TERMALL components: several codeword segments per block (per component with COC)
-    auto comp_multiseg = [&](uint32_t c) { return (P.p.c_sty(c) & (GK_STY_LAZY | GK_STY_TERMALL)) != 0; };
-    bool multiseg = false;
-    for (uint32_t c = 0; c < P.nc; ++c) multiseg = multiseg || comp_multiseg(c);
-    auto seg_max = [&](uint32_t c, uint32_t sg) -> uint32_t {
-        if (P.p.c_sty(c) & GK_STY_TERMALL) return 1;
-        return sg == 0 ? 10 : ((sg & 1) ? 2 : 1);
-    };
-    std::vector<PartState> ps(Hd.parts.size());
-    auto t2_part = [&](size_t q, ByteSrc& BS) {
-        t2_parse_part(P, Hd.parts[q], part_need[q], ctx->dec_layers, ctx->dec_reduce, BS, ps[q]);
-    };
-    const auto h1 = now();
-    if (Hd.parts.size() == 1) {
-        t2_part(0, S);
+    }
+}
+
+// T2 (T2Decompress.cpp:216-570), LRCP, per tile part.  Tile parts are independent (own
+// precincts, tag trees and code-blocks), so they are parsed in parallel host threads into
+// tile-local state (index = block - tile's first block).
+static std::vector<PartState> parse_parts(const Plan& P, ByteSrc& S, const std::vector<TilePart>& parts,
+                                          const std::vector<std::vector<uint8_t>>& part_need, uint32_t dec_layers,
+                                          uint32_t dec_reduce) {
+    std::vector<PartState> ps(parts.size());
+    if (parts.size() == 1) {
+        t2_parse_part(P, parts[0], part_need[0], dec_layers, dec_reduce, S, ps[0]);
     } else {
-        host_pool().run(Hd.parts.size(), [&](size_t q) {
+        host_pool().run(parts.size(), [&](size_t q) {
             ByteSrc BS = S.fork();   // per-call cursor caches (batched regions are shared read-only)
-            t2_part(q, BS);
+            t2_parse_part(P, parts[q], part_need[q], dec_layers, dec_reduce, BS, ps[q]);
         });
     }
-    const auto h2 = now();
-    if (xc)   // (before anything is staged or launched)
-        for (size_t q = 0; q < Hd.parts.size(); ++q) xcode_check_part(P, Hd.parts[q], ps[q]);
-    // ---- the decode table: the needed blocks of the rectangle's tiles, compacted, with offsets
-    // into this call's planes and staging slots, band quantisation from QCD (decoder semantics)
-    // (written straight into the pinned upload buffer: no vector growth, no extra copy)
-    size_t nmax = 0;
-    for (const auto& nd : part_need) nmax += (size_t)std::count(nd.begin(), nd.end(), (uint8_t)1);
-    GkBlock* blk = (GkBlock*)ctx->hinfo.get(sizeof(GkBlock) * std::max<size_t>(nmax, 1));
-    uint32_t nblk = 0;
-    std::vector<uint32_t> hseglen;   // BYPASS / TERMALL: segment lengths, a block's at G.data_cap
-    std::vector<std::vector<int32_t>> part_idx(Hd.parts.size());   // tile-local block -> table entry
-    uint64_t o = 0, t1_bytes = 0;
-    // one tile's needed blocks into blk[nb0 ..) with staging offsets from o0 (its blocks in
-    // (component, resolution, band, precinct, block) order); count-only when blk is null
-    struct TileFill { int32_t q; uint32_t t, nb; uint64_t bytes, t1; };
-    // the blocks of one precinct-band (c, r, bi, pi) of a tile, continuing n / oo / t1
-    auto fill_prec = [&](const TileFill& tf, uint32_t c, uint32_t r, uint32_t bi, uint32_t pi, uint32_t nb0,
-                         bool count_only, uint32_t& n, uint64_t& oo, uint64_t& t1) {
-        const TileG& T = P.tiles[tf.t];
-        const PartState& st2 = ps[tf.q];
-        const std::vector<uint8_t>& need = part_need[tf.q];
-        std::vector<int32_t>& idx = part_idx[tf.q];
-        const ResG& R = T.comps[c].res[r];
-        const PrecG& PG = R.prc[bi][pi];
-        for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
-            const uint32_t lb = PG.first_block + k - T.b0;
-            if (!need[lb]) continue;
-            const uint32_t len = st2.len[lb];
-            if (!count_only) {
-                GkBlock& G = blk[nb0 + n];
-                G = P.blocks[T.b0 + lb];
-                G.band_off = relocate(P, RGg[P.group_of[G.comp]], G.band_off);
-                G.stride = RG.stride;
-                G.band_numbps = (uint8_t)R.bands[bi].numbps;
-                G.step = R.bands[bi].step_dec / 2.0f;
-                if (P.p.c_ht(c) && P.p.c_irrev(c)) {   // ScaleHTFilter: stepsize / 2^(31 - numbps) (Quantizer.cpp:52-62)
-                    if (R.bands[bi].numbps > 31) throw GkError("unsupported number of band bit-planes");
-                    G.step = R.bands[bi].step_dec / (float)(1u << (31 - R.bands[bi].numbps));
-                }
-                G.numbps = st2.numbps[lb];
-                G.npasses = len ? st2.npasses[lb] : 0;
-                if (multiseg) {
-                    G.data_cap = (uint32_t)hseglen.size();
-                    hseglen.insert(hseglen.end(), st2.seglens[lb].begin(), st2.seglens[lb].end());
-                }
-                G.data_off = oo;
-                G.len = len;
-                idx[lb] = (int32_t)(nb0 + n);
-            }
-            t1 += len;
-            oo += (((uint64_t)len + 15) & ~15ull) + 32;
-            ++n;
-        }
-    };
-    auto fill_tile = [&](const TileFill& tf, uint32_t nb0, uint64_t o0, bool count_only, TileFill* out) {
-        const TileG& T = P.tiles[tf.t];
-        if (!count_only) part_idx[tf.q].assign(T.b1 - T.b0, -1);
-        uint32_t n = 0;
-        uint64_t oo = o0, t1 = 0;
-        for (uint32_t c = 0; c < P.nc; ++c)
-            for (uint32_t r = 0; r < (uint32_t)T.comps[c].res.size(); ++r) {
-                const ResG& R = T.comps[c].res[r];
-                for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
-                    for (uint32_t pi = 0; pi < R.pw * R.ph; ++pi) fill_prec(tf, c, r, bi, pi, nb0, count_only, n, oo, t1);
-            }
-        if (out) { out->nb = n; out->bytes = oo - o0; out->t1 = t1; }
-    };
-    std::vector<TileFill> tiles_in;
-    for (uint32_t j = jb; j < je; ++j)
-        for (uint32_t i = ib; i < ie; ++i) {
-            const int32_t q = part_of[(size_t)j * P.ntx + i];
-            if (q >= 0) tiles_in.push_back({q, j * P.ntx + i, 0, 0, 0});
-        }
-    // many tiles (C4: 256) fill in parallel from per-tile counts; BYPASS / TERMALL segment
-    // lengths append in table order, so those streams take the serial pass
-    const bool par_fill = !multiseg && tiles_in.size() >= 8;
-    std::vector<uint32_t> tb0(tiles_in.size() + 1, 0);
-    std::vector<uint64_t> to0(tiles_in.size() + 1, 0);
-    if (par_fill) {
-        host_pool().run(tiles_in.size(), [&](size_t k) { fill_tile(tiles_in[k], 0, 0, true, &tiles_in[k]); });
-        for (size_t k = 0; k < tiles_in.size(); ++k) {
-            tb0[k + 1] = tb0[k] + tiles_in[k].nb; to0[k + 1] = to0[k] + tiles_in[k].bytes; t1_bytes += tiles_in[k].t1;
-        }
-        host_pool().run(tiles_in.size(), [&](size_t k) { fill_tile(tiles_in[k], tb0[k], to0[k], false, nullptr); });
-        nblk = tb0.back(); o = to0.back();
-    } else if (!multiseg) {
-        // few tiles (C2 / C3: one, 49 k blocks): the same two passes over precinct-bands
-        struct Unit { uint32_t k, c, r, bi, pi, nb; uint64_t bytes, t1; };
-        std::vector<Unit> units;
-        for (uint32_t k = 0; k < tiles_in.size(); ++k) {
-            const TileG& T = P.tiles[tiles_in[k].t];
-            part_idx[tiles_in[k].q].assign(T.b1 - T.b0, -1);
+    return ps;
+}
+
+// The decode table into blk: the needed blocks of the rectangle's tiles in (tile, component,
+// resolution, band, precinct, block) order, with offsets into this call's planes and staging
+// slots, band quantisation from QCD (decoder semantics).  Two parallel passes over the
+// precinct-bands: each is counted (blocks, staged bytes, T1 bytes, codeword segments), a prefix
+// sum gives it its place in the table, the staging buffer and the segment lengths, and it is
+// written there (C2 / C3: one tile of 49 k blocks in 48 precinct-bands; C4: 256 tiles).
+static BlockTable fill_table(const Plan& P, const TileRect& TR, const std::vector<std::vector<uint8_t>>& part_need,
+                             const std::vector<PartState>& ps, GkBlock* blk) {
+    // BYPASS / TERMALL components: several codeword segments per block (per component with COC)
+    bool multiseg = false;
+    for (uint32_t c = 0; c < P.nc; ++c) multiseg = multiseg || (P.p.c_sty(c) & (GK_STY_LAZY | GK_STY_TERMALL)) != 0;
+    BlockTable BT;
+    BT.part_idx.resize(ps.size());
+    // a precinct-band with blocks: its counts, then its first table entry, segment length and staging offset
+    struct Unit { int32_t q; uint32_t c; const TileG* T; const BandG* B; const PrecG* PG; uint32_t nb, nseg; uint64_t bytes, t1; };
+    std::vector<Unit> units;
+    size_t nall = 0;   // blocks of the tiles present
+    for (uint32_t j = TR.jb; j < TR.je; ++j)
+        for (uint32_t i = TR.ib; i < TR.ie; ++i) {
+            const uint32_t t = j * P.ntx + i;
+            const int32_t q = TR.part_of[t];
+            if (q < 0) continue;
+            const TileG& T = P.tiles[t];
+            BT.part_idx[q].assign(T.b1 - T.b0, -1);
+            nall += T.b1 - T.b0;
             for (uint32_t c = 0; c < P.nc; ++c)
                 for (uint32_t r = 0; r < (uint32_t)T.comps[c].res.size(); ++r) {
                     const ResG& R = T.comps[c].res[r];
                     for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
                         for (uint32_t pi = 0; pi < R.pw * R.ph; ++pi)
-                            if (R.prc[bi][pi].cw * R.prc[bi][pi].ch) units.push_back({k, c, r, bi, pi, 0, 0, 0});
+                            if (R.prc[bi][pi].cw * R.prc[bi][pi].ch) units.push_back({q, c, &T, &R.bands[bi], &R.prc[bi][pi], 0, 0, 0, 0});
                 }
         }
-        auto run_unit = [&](size_t i, uint32_t nb0, uint64_t o0, bool count_only) {
-            Unit& u = units[i];
-            uint32_t n = 0;
-            uint64_t oo = o0, t1 = 0;
-            fill_prec(tiles_in[u.k], u.c, u.r, u.bi, u.pi, nb0, count_only, n, oo, t1);
-            if (count_only) { u.nb = n; u.bytes = oo - o0; u.t1 = t1; }
-        };
-        host_pool().run(units.size(), [&](size_t i) { run_unit(i, 0, 0, true); });
-        std::vector<uint32_t> ub(units.size());
-        std::vector<uint64_t> uo(units.size());
-        for (size_t i = 0; i < units.size(); ++i) {
-            ub[i] = nblk; uo[i] = o;
-            nblk += units[i].nb; o += units[i].bytes; t1_bytes += units[i].t1;
+    auto slot_bytes = [](uint32_t len) { return (((uint64_t)len + 15) & ~15ull) + 32; };
+    // A pass over the units: on the pool in runs of consecutive units, eight runs per thread, and
+    // inline when the tiles hold under 1,024 blocks.  With one pool item per unit and every table
+    // on the pool, many tiles and small tables were slower than the per-tile and serial fills this
+    // one replaces (C4, C5 and the multi-segment stream in profiles/decode_stages_bench.txt)
+    const size_t nu = units.size(), run = std::max<size_t>(1, nu / (8 * host_pool().size()));
+    auto each_unit = [&](auto&& f) {
+        if (nall < 1024) { for (size_t i = 0; i < nu; ++i) f(i); return; }
+        host_pool().run((nu + run - 1) / run, [&](size_t k) { for (size_t i = k * run; i < std::min(nu, (k + 1) * run); ++i) f(i); });
+    };
+    each_unit([&](size_t i) {
+        Unit& u = units[i];
+        for (uint32_t k = 0; k < u.PG->cw * u.PG->ch; ++k) {
+            const uint32_t lb = u.PG->first_block + k - u.T->b0;
+            if (!part_need[u.q][lb]) continue;
+            ++u.nb; u.bytes += slot_bytes(ps[u.q].len[lb]); u.t1 += ps[u.q].len[lb];
+            if (multiseg) u.nseg += (uint32_t)ps[u.q].seglens[lb].size();
         }
-        host_pool().run(units.size(), [&](size_t i) { run_unit(i, ub[i], uo[i], false); });
-    } else {
-        for (TileFill& tf : tiles_in) {
-            fill_tile(tf, nblk, o, false, &tf);
-            nblk += tf.nb; o += tf.bytes; t1_bytes += tf.t1;
-        }
+    });
+    uint32_t nseg = 0;
+    for (Unit& u : units) {   // (counts become starts)
+        const Unit n = u;
+        u.nb = BT.nblk; u.bytes = BT.staged; u.nseg = nseg;
+        BT.nblk += n.nb; BT.staged += n.bytes; BT.t1_bytes += n.t1; nseg += n.nseg;
     }
-    const uint32_t nbr = nblk, nbx = std::max(nbr, 1u);
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
-    // ---- stage compressed bytes on the device.  A host stream of which the selected blocks
-    // use a small part (window decode of a large file) is gathered on the host and only those
-    // bytes cross PCIe; otherwise the whole stream is copied and gathered on the device.
-    const bool host_gather = !cs_on_device && o * 2 < len;
+    BT.seglen.resize(nseg);
+    each_unit([&](size_t i) {
+        const Unit& u = units[i];
+        const TileG& T = *u.T;
+        const BandG& B = *u.B;
+        const PrecG& PG = *u.PG;
+        const PartState& st2 = ps[u.q];
+        uint32_t n = u.nb, sg = u.nseg;
+        uint64_t oo = u.bytes;
+        for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
+            const uint32_t lb = PG.first_block + k - T.b0;
+            if (!part_need[u.q][lb]) continue;
+            const uint32_t len = st2.len[lb];
+            GkBlock& G = blk[n];
+            G = P.blocks[T.b0 + lb];
+            G.band_off = relocate(P, TR.RGg[P.group_of[G.comp]], G.band_off);
+            G.stride = TR.RG.stride; G.band_numbps = (uint8_t)B.numbps;
+            G.step = B.step_dec / 2.0f;
+            if (P.p.c_ht(u.c) && P.p.c_irrev(u.c)) {   // ScaleHTFilter: stepsize / 2^(31 - numbps) (Quantizer.cpp:52-62)
+                if (B.numbps > 31) throw GkError("unsupported number of band bit-planes");
+                G.step = B.step_dec / (float)(1u << (31 - B.numbps));
+            }
+            G.numbps = st2.numbps[lb];
+            G.npasses = len ? st2.npasses[lb] : 0;
+            if (multiseg) {
+                G.data_cap = sg;
+                std::copy(st2.seglens[lb].begin(), st2.seglens[lb].end(), BT.seglen.begin() + sg);
+                sg += (uint32_t)st2.seglens[lb].size();
+            }
+            G.data_off = oo; G.len = len;
+            BT.part_idx[u.q][lb] = (int32_t)n++;
+            oo += slot_bytes(len);
+        }
+    });
+    return BT;
+}
+
+// Stage the compressed bytes of the table's blocks on the device; returns the staging buffer.
+// A host stream of which the selected blocks use a small part (window decode of a large file) is
+// gathered on the host and only those bytes cross PCIe; otherwise the whole stream is copied
+// and gathered on the device.
+static const uint8_t* stage_bytes(gk_ctx* ctx, const ByteSrc& S, const std::vector<PartState>& ps, const BlockTable& BT,
+                                  const GkBlock* blk) {
+    hipStream_t st = ctx->st;
+    const Plan& P = ctx->plan;
+    const bool cs_on_device = S.dev != nullptr;
+    const uint8_t* const cs = cs_on_device ? S.dev : S.host;
+    const uint64_t o = BT.staged;
+    const bool host_gather = !cs_on_device && o * 2 < S.len;
     const uint8_t* dcs = cs;
     if (!cs_on_device && !host_gather) {
-        uint8_t* d = (uint8_t*)ctx->dout.get(len + 16);
-        HIPCHK(hipMemcpyAsync(d, cs, len, hipMemcpyHostToDevice, st));
+        uint8_t* d = (uint8_t*)ctx->dout.get(S.len + 16);
+        HIPCHK(hipMemcpyAsync(d, cs, S.len, hipMemcpyHostToDevice, st));
         dcs = d;
     }
     // gather every selected block's segments into a 16-byte aligned slot followed by >= 32
@@ -7069,34 +7059,29 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
     // (a chunk lands at its block's slot + the block's bytes before it, recorded by the parse, so
     // pieces of one part's chunk list fill in parallel; a chunk of a block the table does not
     // hold becomes an empty triple)
-    size_t nseg = 0;
-    uint64_t* seg = nullptr;
-    {
-        std::vector<size_t> sb(ps.size() + 1, 0);
-        for (size_t q = 0; q < ps.size(); ++q) sb[q + 1] = sb[q] + (part_idx[q].empty() ? 0 : 3 * ps[q].chunks.size());
-        seg = (uint64_t*)ctx->hseg.get(sb.back() * 8 + 8);
-        struct Piece { size_t q, b, e; };
-        std::vector<Piece> pieces;
-        for (size_t q = 0; q < ps.size(); ++q) {
-            if (part_idx[q].empty()) continue;
-            const size_t n = ps[q].chunks.size(), step = std::max<size_t>(4096, n / 32);
-            for (size_t b = 0; b < n; b += step) pieces.push_back({q, b, std::min(n, b + step)});
-        }
-        host_pool().run(pieces.size(), [&](size_t i) {
-            const Piece& pc = pieces[i];
-            const std::vector<Chunk>& chs = ps[pc.q].chunks;
-            const std::vector<int32_t>& idx = part_idx[pc.q];
-            for (size_t j = pc.b; j < pc.e; ++j) {
-                const Chunk& ch = chs[j];
-                const int32_t k = idx[ch.b];
-                uint64_t* w = seg + sb[pc.q] + 3 * j;
-                w[0] = ch.pos;
-                w[1] = k < 0 ? 0 : blk[k].data_off + ch.boff;
-                w[2] = k < 0 ? 0 : ch.len;
-            }
-        });
-        nseg = sb.back();
+    std::vector<size_t> sb(ps.size() + 1, 0);
+    struct Piece { size_t q, b, e; };
+    std::vector<Piece> pieces;
+    for (size_t q = 0; q < ps.size(); ++q) {
+        const size_t n = BT.part_idx[q].empty() ? 0 : ps[q].chunks.size(), step = std::max<size_t>(4096, n / 32);
+        sb[q + 1] = sb[q] + 3 * n;
+        for (size_t b = 0; b < n; b += step) pieces.push_back({q, b, std::min(n, b + step)});
     }
+    const size_t nseg = sb.back();
+    uint64_t* seg = (uint64_t*)ctx->hseg.get(nseg * 8 + 8);
+    host_pool().run(pieces.size(), [&](size_t i) {
+        const Piece& pc = pieces[i];
+        const std::vector<Chunk>& chs = ps[pc.q].chunks;
+        const std::vector<int32_t>& idx = BT.part_idx[pc.q];
+        for (size_t j = pc.b; j < pc.e; ++j) {
+            const Chunk& ch = chs[j];
+            const int32_t k = idx[ch.b];
+            uint64_t* w = seg + sb[pc.q] + 3 * j;
+            w[0] = ch.pos;
+            w[1] = k < 0 ? 0 : blk[k].data_off + ch.boff;
+            w[2] = k < 0 ? 0 : ch.len;
+        }
+    });
     uint8_t* stg = (uint8_t*)ctx->bytes.get(o + 256);   // decoder window loads read up to 48 B past a block
     bool pad_ff = false;
     for (uint32_t c = 0; c < P.nc; ++c) pad_ff = pad_ff || !P.p.c_ht(c);
@@ -7106,464 +7091,521 @@ static void decode_core(gk_ctx* ctx, ByteSrc& S, Header& Hd, const DecDst& out, 
         if (pad_ff) memset(hst, 0xff, o);
         for (size_t k = 0; k < nseg; k += 3) memcpy(hst + seg[k + 1], cs + seg[k], seg[k + 2]);
         HIPCHK(hipMemcpyAsync(stg, hst, o, hipMemcpyHostToDevice, st));
-    } else {
+        return stg;
+    }
     if (pad_ff) HIPCHK(hipMemsetAsync(stg, 0xff, o, st));
     if (nseg) {
         uint64_t* ds = (uint64_t*)ctx->dseg.get(nseg * 8 + 8);
         HIPCHK(hipMemcpyAsync(ds, seg, nseg * 8, hipMemcpyHostToDevice, st));
         gk_launch_gather(st, dcs, stg, ds, (uint32_t)(nseg / 3));
     }
+    return stg;
+}
+
+// Components coded with different T1 coders (COC: Part-1 / mode switches / HT): the table is
+// grouped by coder class (a stable partition; entries keep their staging offsets and segment
+// lists), one decoder launch per class.  Returns (first entry, class) per class run.
+static std::vector<std::pair<uint32_t, uint32_t>> class_runs(const Plan& P, GkBlock* blk, uint32_t nblk) {
+    std::vector<std::pair<uint32_t, uint32_t>> runs;
+    std::vector<uint32_t> classes;
+    for (uint32_t c = 0; c < P.nc; ++c)
+        if (std::find(classes.begin(), classes.end(), P.p.c_class(c)) == classes.end()) classes.push_back(P.p.c_class(c));
+    if (classes.size() == 1 || !nblk) return {{0, classes[0]}};
+    std::vector<GkBlock> tmp(blk, blk + nblk);
+    uint32_t k = 0;
+    for (uint32_t cl : classes) {
+        const uint32_t k0 = k;
+        for (const GkBlock& G : tmp)
+            if (P.p.c_class(G.comp) == cl) blk[k++] = G;
+        if (k > k0) runs.push_back({k0, cl});
     }
-    const uint8_t* src_bytes = stg;
-    if (prof)
-        fprintf(stderr, "decode host: headers+setup %.3f ms, packet headers %.3f ms, segments %.3f ms (%zu parts, "
-                        "%u blocks); %llu page fetches %.3f ms (cumulative)\n",
-                ms(h0, h1), ms(h1, h2), ms(h2, now()), Hd.parts.size(), nbr,
-                (unsigned long long)ByteSrc::fetch_cnt.load(), ByteSrc::fetch_ns.load() * 1e-6);
-    // components coded with different T1 coders (COC: Part-1 / mode switches / HT): the table is
-    // grouped by coder class (a stable partition; entries keep their staging offsets and segment
-    // lists), one decoder launch per class below
-    std::vector<std::pair<uint32_t, uint32_t>> cls_range;   // (first entry, class) per class run
-    {
-        bool mixed = false;
-        for (uint32_t c = 1; c < P.nc; ++c) mixed = mixed || P.p.c_class(c) != P.p.c_class(0);
-        if (mixed && nbr) {
-            std::vector<GkBlock> tmp(blk, blk + nbr);
-            std::vector<uint32_t> classes;
-            for (uint32_t c = 0; c < P.nc; ++c)
-                if (std::find(classes.begin(), classes.end(), P.p.c_class(c)) == classes.end()) classes.push_back(P.p.c_class(c));
-            uint32_t k = 0;
-            for (uint32_t cl : classes) {
-                const uint32_t k0 = k;
-                for (const GkBlock& G : tmp)
-                    if (P.p.c_class(G.comp) == cl) blk[k++] = G;
-                if (k > k0) cls_range.push_back({k0, cl});
-            }
-        } else {
-            cls_range.push_back({0, P.p.c_class(0)});
-        }
+    return runs;
+}
+
+// The heaviest blocks go to solo waves (gk_t1dec.hip solo_block) on the SIMDs the
+// lane-parallel waves leave.  Weight = compressed bytes (decisions follow them within
+// ~10 %).  K, the number of solo blocks, balances the two sides: the lane-parallel
+// waves last as long as the heaviest block left to them (weight w[K]), a solo wave as
+// long as its blocks' sum / ratio; the top K are packed longest-first into the solo
+// waves (LPT) and K is the crossing point of the two (binary search: the first falls,
+// the second grows with K).  GK_T1DEC_SOLO=n (sp.forced): the n heaviest, one per wave.
+// shared: the device is shared with another engine's call in progress (e.g. two images in flight; engines
+// that merely exist, like the bench's C2 + C3 pair run one after the other, do not count):
+// no SIMD is idle, so a solo
+// wave's time is taken from the other decodes; only clear outliers (> 1.3 x the weight of
+// the block at rank 1,024) go solo, one per wave.  C2 (LL blocks 1.06 x the plateau): none,
+// 2,394 -> 2,548 Mpix/s with two images in flight; C3 (LL ~1.6 x): kept (1,761 -> 2,056).
+// Returns the number of solo blocks; bins[b]: the blocks of solo wave b.
+static uint32_t solo_split(const GkBlock* blk, uint32_t nbr, const GkSoloPlan& sp, bool shared,
+                           std::vector<std::vector<uint32_t>>& bins) {
+    bins.clear();
+    if (!sp.waves) return 0;
+    auto weight = [&](uint32_t q) -> uint64_t { return blk[q].npasses ? blk[q].len : 0; };
+    // (at most 4 blocks per solo wave: the search stays a fraction of a millisecond of host time)
+    const uint32_t kmax = sp.forced >= 0 ? (uint32_t)sp.forced : std::min<uint32_t>(nbr / 4, 4u * sp.waves);
+    std::vector<uint32_t> byl(nbr);
+    for (uint32_t q = 0; q < nbr; ++q) byl[q] = q;
+    auto heavier = [&](uint32_t x, uint32_t y) { return weight(x) != weight(y) ? weight(x) > weight(y) : x < y; };
+    const uint32_t top = std::min<uint32_t>(kmax + 1, nbr);
+    if (top) {
+        std::nth_element(byl.begin(), byl.begin() + (top - 1), byl.end(), heavier);
+        std::sort(byl.begin(), byl.begin() + top, heavier);
     }
-    GkBlock* dblk_all = (GkBlock*)ctx->dblocks.get(sizeof(GkBlock) * nbx);
-    HIPCHK(hipMemcpyAsync(dblk_all, blk, sizeof(GkBlock) * nbr, hipMemcpyHostToDevice, st));
-    ctx->blocks_uploaded = false;   // the encode table must be re-uploaded
-    int32_t* arena = (int32_t*)ctx->arena.get(RG.plane * P.nc * 2 * sizeof(int32_t));
-    // tiles of the rectangle without a tile part decode as zero; blocks skipped by the window
-    // need no clearing (they only feed samples outside the output region)
-    if (Hd.parts.size() < (size_t)(ie - ib) * (je - jb))
-        HIPCHK(hipMemsetAsync(arena, 0, RG.plane * P.nc * 2 * sizeof(int32_t), st));
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[2], st));
-    // one class of the table: entries [s, s + n), decoder class cls (Params::c_class)
-    auto t1_class = [&](uint32_t s0, uint32_t n, uint32_t cls) {
-        const uint32_t nbr = n, nbx = std::max(n, 1u);
-        GkBlock* const blk_all = blk;
-        GkBlock* const blk = blk_all + s0;
-        GkBlock* const dblk = dblk_all + s0;
-        const bool cls_ht = (cls & 3) == 2, cls_generic = (cls & 3) == 1, cls_wide = (cls >> 8) & 1;
-        const uint32_t cls_sty = (cls >> 2) & 0x3f;
-        (void)blk_all;
-        if (nbr == 0) {
-            // nothing to decode (all-zero tiles)
-        } else if (cls_ht) {
-            // HT cleanup pass decode straight into the band windows (T1HT::decompress, T1HT.cpp:134-187)
-            uint32_t* dsel = (uint32_t*)ctx->dord.get(4 * (size_t)nbx + 16);
-            uint32_t* hsel = (uint32_t*)ctx->hord.get(4 * (size_t)nbx + 16);
-            for (uint32_t k = 0; k < nbr; ++k) hsel[k] = k;
-            HIPCHK(hipMemcpyAsync(dsel, hsel, 4 * (size_t)nbr, hipMemcpyHostToDevice, st));
-            int* derr = (int*)ctx->derr.get(64);
-            HIPCHK(hipMemsetAsync(derr, 0, 64, st));
-            gk_launch_ht_dec(st, src_bytes, dblk, dsel, arena, nbr, derr, cls_wide, xc != nullptr);
-            launch_check(__LINE__);
-            HIPCHK(hipEventRecord(ctx->ev[8], st));
-            int herr = 0;
-            HIPCHK(hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (herr) throw GkError("corrupt HT code-block segment");
-        } else if (cls_generic) {
-            // mode switches or wide code-blocks: lane-per-block decoder over the codeword segments
-            // (gk_t1ms.hip)
-            uint32_t* dsl = nullptr;   // (segment tables for BYPASS / TERMALL classes only: one segment otherwise)
-            if ((cls_sty & (GK_STY_LAZY | GK_STY_TERMALL)) && !hseglen.empty()) {
-                uint32_t* hsl = (uint32_t*)ctx->hord.get(4 * hseglen.size());
-                memcpy(hsl, hseglen.data(), 4 * hseglen.size());
-                dsl = (uint32_t*)ctx->dseglen.get(4 * hseglen.size());
-                HIPCHK(hipMemcpyAsync(dsl, hsl, 4 * hseglen.size(), hipMemcpyHostToDevice, st));
-            }
-            uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(nbx));
-            gk_launch_t1_dec_ms(st, src_bytes, dblk, dsl, arena, nbr, mst, cls_sty, xc != nullptr);
-            launch_check(__LINE__);
-            HIPCHK(hipEventRecord(ctx->ev[8], st));
-            if (dsl) HIPCHK(hipStreamSynchronize(st));   // the pinned table is reused
-        } else {
-            // lane assignment: blocks bucketed by pass count (descending), so the lanes of a
-            // wave decode similar amounts of work and the longest waves start first.  Only
-            // `L` lanes of each 64-lane wave carry a block (gk_t1dec_lanes): fewer lanes per wave
-            // give more waves, so every SIMD of the chip holds waves and can hide latency.
-            const uint32_t L = gk_t1dec_lanes();
-            // The heaviest blocks go to solo waves (gk_t1dec.hip solo_block) on the SIMDs the
-            // lane-parallel waves leave.  Weight = compressed bytes (decisions follow them within
-            // ~10 %).  K, the number of solo blocks, balances the two sides: the lane-parallel
-            // waves last as long as the heaviest block left to them (weight w[K]), a solo wave as
-            // long as its blocks' sum / ratio; the top K are packed longest-first into the solo
-            // waves (LPT) and K is the crossing point of the two (binary search: the first falls,
-            // the second grows with K).  GK_T1DEC_SOLO=n: the n heaviest, one per wave.
-            GkSoloPlan sp = nbr ? gk_t1dec_solo_plan(nbr, L) : GkSoloPlan{0, -1, 1.f};
-            // Device shared with another engine's call in progress (e.g. two images in flight; engines
-            // that merely exist, like the bench's C2 + C3 pair run one after the other, do not count):
-            // no SIMD is idle, so a solo
-            // wave's time is taken from the other decodes; only clear outliers (> 1.3 x the weight of
-            // the block at rank 1,024) go solo, one per wave.  C2 (LL blocks 1.06 x the plateau): none,
-            // 2,394 -> 2,548 Mpix/s with two images in flight; C3 (LL ~1.6 x): kept (1,761 -> 2,056).
-            const bool shared = sp.forced < 0 && engines_busy(ctx->device) > 1;
-            uint32_t nsb = 0;
-            std::vector<uint32_t> byl;
-            std::vector<std::vector<uint32_t>> bins;
-            auto weight = [&](uint32_t q) -> uint64_t { return blk[q].npasses ? blk[q].len : 0; };
-            if (sp.waves) {
-                // (at most 4 blocks per solo wave: the search stays a fraction of a millisecond of host time)
-                const uint32_t kmax = sp.forced >= 0 ? (uint32_t)sp.forced : std::min<uint32_t>(nbr / 4, 4u * sp.waves);
-                byl.resize(nbr);
-                for (uint32_t q = 0; q < nbr; ++q) byl[q] = q;
-                auto heavier = [&](uint32_t x, uint32_t y) { return weight(x) != weight(y) ? weight(x) > weight(y) : x < y; };
-                const uint32_t top = std::min<uint32_t>(kmax + 1, nbr);
-                if (top) {
-                    std::nth_element(byl.begin(), byl.begin() + (top - 1), byl.end(), heavier);
-                    std::sort(byl.begin(), byl.begin() + top, heavier);
-                }
-                // longest-first packing of the k heaviest into the solo waves; returns the largest load
-                auto pack = [&](uint32_t k, std::vector<std::vector<uint32_t>>* out) -> uint64_t {
-                    std::vector<uint64_t> load(sp.waves, 0);
-                    std::vector<uint32_t> cnt(sp.waves, 0);
-                    if (out) out->assign(sp.waves, {});
-                    using E = std::pair<uint64_t, uint32_t>;
-                    std::priority_queue<E, std::vector<E>, std::greater<E>> pq;
-                    for (uint32_t b = 0; b < sp.waves; ++b) pq.push({0, b});
-                    uint64_t mx = 0;
-                    for (uint32_t j = 0; j < k && !pq.empty(); ++j) {
-                        const E e = pq.top();
-                        pq.pop();
-                        load[e.second] = e.first + weight(byl[j]);
-                        mx = std::max(mx, load[e.second]);
-                        if (out) (*out)[e.second].push_back(byl[j]);
-                        if (++cnt[e.second] < 64) pq.push({load[e.second], e.second});
-                    }
-                    return mx;
-                };
-                uint32_t k = 0;
-                if (sp.forced >= 0) {
-                    k = (uint32_t)sp.forced;
-                    bins.assign(sp.waves, {});
-                    for (uint32_t j = 0; j < k; ++j) bins[j].push_back(byl[j]);
-                } else if (shared) {
-                    const uint32_t r = std::min<uint32_t>(std::max<uint32_t>(1024u, top), nbr - 1);
-                    if (r >= top) std::nth_element(byl.begin() + top, byl.begin() + r, byl.end(), heavier);
-                    const double ref = 1.3 * (double)weight(byl[r]);
-                    while (k < std::min<uint32_t>(kmax, sp.waves) && (double)weight(byl[k]) > ref) ++k;
-                    bins.assign(sp.waves, {});
-                    for (uint32_t j = 0; j < k; ++j) bins[j].push_back(byl[j]);
-                } else {
-                    auto lane_side = [&](uint32_t kk) -> double { return kk < nbr ? (double)weight(byl[kk]) : 0.0; };
-                    auto solo_side = [&](uint32_t kk) -> double { return (double)pack(kk, nullptr) / sp.ratio; };
-                    uint32_t lo = 0, hi = kmax;   // first k with solo_side(k) >= lane_side(k)
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) / 2;
-                        if (solo_side(mid) >= lane_side(mid)) hi = mid; else lo = mid + 1;
-                    }
-                    k = lo;
-                    if (k > 0 && std::max(solo_side(k - 1), lane_side(k - 1)) <= std::max(solo_side(k), lane_side(k))) --k;
-                    if (k) pack(k, &bins);
-                }
-                nsb = k;
-            }
-            uint32_t nsw = 0;   // solo waves holding a block, rounded up to whole workgroups of 12
-            for (uint32_t b = 0; b < bins.size(); ++b)
-                if (!bins[b].empty()) nsw = b + 1;
-            nsw = (nsw + 11) / 12 * 12;
-            const uint32_t nw = nsw + (nbr - nsb + L - 1) / L, nslots = nw * 64;
-            uint32_t* hord = (uint32_t*)ctx->hord.get(4 * ((size_t)nslots + 2 * (size_t)nbr + 2) + 8 * ((size_t)nw + 1));
-            uint32_t* hpos = hord + nslots;               // slot of block k
-            uint32_t* hids = hpos + nbr;                  // identity (compact table)
-            uint64_t* hwo = (uint64_t*)(hids + nbr + 2);
-            {
-                std::fill(hord, hord + nslots, 0xffffffffu);
-                std::vector<uint8_t> solo(nbr, 0);
-                for (uint32_t b = 0; b < bins.size() && b < nsw; ++b)
-                    for (uint32_t i = 0; i < bins[b].size(); ++i) {
-                        const uint32_t q = bins[b][i];
-                        solo[q] = 1;
-                        hord[(size_t)b * 64 + i] = q; hpos[q] = b * 64 + i;
-                    }
-                std::vector<uint32_t> cnt(GK_MAX_PASSES + 2, 0);
-                for (uint32_t q = 0; q < nbr; ++q)
-                    if (!solo[q]) cnt[std::min<uint32_t>(blk[q].npasses, GK_MAX_PASSES + 1)]++;
-                std::vector<uint32_t> start(GK_MAX_PASSES + 2, 0);
-                uint32_t acc = 0;
-                for (int k = GK_MAX_PASSES + 1; k >= 0; --k) { start[k] = acc; acc += cnt[k]; }
-                for (uint32_t q = 0; q < nbr; ++q) {
-                    hids[q] = q;
-                    if (solo[q]) continue;
-                    const uint32_t k = std::min<uint32_t>(blk[q].npasses, GK_MAX_PASSES + 1);
-                    const uint32_t idx = start[k]++;
-                    const uint32_t slot = (nsw + idx / L) * 64 + idx % L;
-                    hord[slot] = q; hpos[q] = slot;
-                }
-                uint64_t wo = 0;
-                for (uint32_t wv = 0; wv < nw; ++wv) {
-                    hwo[wv] = wo;
-                    uint32_t mp = 0;
-                    for (uint32_t i = wv * 64; i < wv * 64 + (wv < nsw ? 64 : L); ++i)
-                        if (hord[i] != 0xffffffffu) mp = std::max(mp, (uint32_t)blk[hord[i]].numbps);
-                    if (wv < nsw && hord[wv * 64] == 0xffffffffu) continue;   // a solo wave without a block
-                    wo += (272 + (uint64_t)mp * 64) * 64;   // per-lane slab: WS_FIXED + planes (gk_t1dec.hip), 128 B lines
-                }
-                hwo[nw] = wo;
-            }
-            const size_t obytes = 4 * ((size_t)nslots + 2 * (size_t)nbr + 2) + 8 * ((size_t)nw + 1);
-            uint32_t* dord = (uint32_t*)ctx->dord.get(obytes);
-            HIPCHK(hipMemcpyAsync(dord, hord, obytes, hipMemcpyHostToDevice, st));
-            const uint32_t* dpos = dord + nslots;
-            const uint32_t* dids = dpos + nbr;
-            const uint64_t* dwo = (const uint64_t*)(dids + nbr + 2);
-            uint64_t* dscr = (uint64_t*)ctx->dscratch.get(8 * hwo[nw] + 64);
-            // lane-parallel decoder state rows start at zero; solo waves write every row recon reads
-            HIPCHK(hipMemsetAsync(dscr + hwo[nsw], 0, 8 * (hwo[nw] - hwo[nsw]), st));
-            gk_launch_t1_dec(st, src_bytes, dblk, dord, dscr, dwo, nslots, nsw);
-            ctx->tm.t1_steps_max = ctx->tm.t1_steps_total = ctx->tm.t1_symbols = 0;
-            ctx->tm.t1_solo_decisions = ctx->tm.t1_solo_decisions_max = 0;
-            ctx->tm.t1_solo_blocks = nsb;
-            // classes whose split the shared rule chose (zeroed when the call began: a call may decode
-            // several classes); without solo waves (under 8 blocks) no rule is taken
-            ctx->tm.t1_shared += (shared && sp.waves) ? 1 : 0;
-            if (getenv("GK_T1_STATS")) {
-                uint64_t sv[5];
-                gk_t1dec_stats(sv);
-                ctx->tm.t1_steps_max = sv[0]; ctx->tm.t1_steps_total = sv[1]; ctx->tm.t1_symbols = sv[2];
-                ctx->tm.t1_solo_decisions = sv[3]; ctx->tm.t1_solo_decisions_max = sv[4];
-            }
-            launch_check(__LINE__);
-            HIPCHK(hipEventRecord(ctx->ev[8], st));
-            uint32_t maxnp = 1;
-            for (uint32_t q = 0; q < nbr; ++q) maxnp = std::max<uint32_t>(maxnp, blk[q].numbps);
-            gk_launch_t1_recon(st, dblk, dids, dpos, dscr, dwo, arena, nbr, maxnp, xc != nullptr);
+    // longest-first packing of the k heaviest into the solo waves; returns the largest load
+    auto pack = [&](uint32_t k, std::vector<std::vector<uint32_t>>* out) -> uint64_t {
+        std::vector<uint64_t> load(sp.waves, 0);
+        std::vector<uint32_t> cnt(sp.waves, 0);
+        if (out) out->assign(sp.waves, {});
+        using E = std::pair<uint64_t, uint32_t>;
+        std::priority_queue<E, std::vector<E>, std::greater<E>> pq;
+        for (uint32_t b = 0; b < sp.waves; ++b) pq.push({0, b});
+        uint64_t mx = 0;
+        for (uint32_t j = 0; j < k && !pq.empty(); ++j) {
+            const E e = pq.top();
+            pq.pop();
+            load[e.second] = e.first + weight(byl[j]);
+            mx = std::max(mx, load[e.second]);
+            if (out) (*out)[e.second].push_back(byl[j]);
+            if (++cnt[e.second] < 64) pq.push({load[e.second], e.second});
         }
+        return mx;
     };
-    for (size_t k = 0; k < cls_range.size(); ++k) {
-        const uint32_t s0 = cls_range[k].first, e0 = k + 1 < cls_range.size() ? cls_range[k + 1].first : nbr;
-        if (k) HIPCHK(hipStreamSynchronize(st));   // (the pinned staging tables are reused per class)
-        t1_class(s0, e0 - s0, cls_range[k].second);
+    uint32_t k = 0;
+    if (sp.forced >= 0 || shared) {
+        if (sp.forced >= 0) {
+            k = (uint32_t)sp.forced;
+        } else {
+            const uint32_t r = std::min<uint32_t>(std::max<uint32_t>(1024u, top), nbr - 1);
+            if (r >= top) std::nth_element(byl.begin() + top, byl.begin() + r, byl.end(), heavier);
+            const double ref = 1.3 * (double)weight(byl[r]);
+            while (k < std::min<uint32_t>(kmax, sp.waves) && (double)weight(byl[k]) > ref) ++k;
+        }
+        bins.assign(sp.waves, {});
+        for (uint32_t j = 0; j < k; ++j) bins[j].push_back(byl[j]);
+    } else {
+        auto lane_side = [&](uint32_t kk) -> double { return kk < nbr ? (double)weight(byl[kk]) : 0.0; };
+        auto solo_side = [&](uint32_t kk) -> double { return (double)pack(kk, nullptr) / sp.ratio; };
+        uint32_t lo = 0, hi = kmax;   // first k with solo_side(k) >= lane_side(k)
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (solo_side(mid) >= lane_side(mid)) hi = mid; else lo = mid + 1;
+        }
+        k = lo;
+        if (k > 0 && std::max(solo_side(k - 1), lane_side(k - 1)) <= std::max(solo_side(k), lane_side(k))) --k;
+        if (k) pack(k, &bins);
     }
+    return k;
+}
+
+// Lane assignment into T (sized and bound to its buffer): solo waves first, then
+// the other blocks bucketed by pass count (descending), so the lanes of a
+// wave decode similar amounts of work and the longest waves start first.  Only
+// `L` lanes of each 64-lane wave carry a block (gk_t1dec_lanes): fewer lanes per wave
+// give more waves, so every SIMD of the chip holds waves and can hide latency.
+static void lane_layout(const GkBlock* blk, const std::vector<std::vector<uint32_t>>& bins, uint32_t L, const LaneTables& T) {
+    const uint32_t nbr = T.nbr;
+    std::fill(T.ord, T.ord + T.nslots, 0xffffffffu);
+    std::vector<uint8_t> solo(nbr, 0);
+    for (uint32_t b = 0; b < bins.size() && b < T.nsw; ++b)
+        for (uint32_t i = 0; i < bins[b].size(); ++i) {
+            const uint32_t q = bins[b][i];
+            solo[q] = 1;
+            T.ord[(size_t)b * 64 + i] = q; T.pos[q] = b * 64 + i;
+        }
+    std::vector<uint32_t> cnt(GK_MAX_PASSES + 2, 0);
+    for (uint32_t q = 0; q < nbr; ++q)
+        if (!solo[q]) cnt[std::min<uint32_t>(blk[q].npasses, GK_MAX_PASSES + 1)]++;
+    std::vector<uint32_t> start(GK_MAX_PASSES + 2, 0);
+    uint32_t acc = 0;
+    for (int k = GK_MAX_PASSES + 1; k >= 0; --k) { start[k] = acc; acc += cnt[k]; }
+    for (uint32_t q = 0; q < nbr; ++q) {
+        T.ids[q] = q;
+        if (solo[q]) continue;
+        const uint32_t k = std::min<uint32_t>(blk[q].npasses, GK_MAX_PASSES + 1);
+        const uint32_t idx = start[k]++;
+        const uint32_t slot = (T.nsw + idx / L) * 64 + idx % L;
+        T.ord[slot] = q; T.pos[q] = slot;
+    }
+    uint64_t wo = 0;
+    for (uint32_t wv = 0; wv < T.nw; ++wv) {
+        T.wo[wv] = wo;
+        uint32_t mp = 0;
+        for (uint32_t i = wv * 64; i < wv * 64 + (wv < T.nsw ? 64 : L); ++i)
+            if (T.ord[i] != 0xffffffffu) mp = std::max(mp, (uint32_t)blk[T.ord[i]].numbps);
+        if (wv < T.nsw && T.ord[wv * 64] == 0xffffffffu) continue;   // a solo wave without a block
+        wo += gk_t1dec_lane_words(mp) * 64;   // 64 per-lane slabs, 128 B lines
+    }
+    T.wo[T.nw] = wo;
+}
+
+// Plain Part-1 blocks: solo and lane-parallel waves (gk_t1dec.hip), then the reconstruction
+static void t1_decode_lanes(gk_ctx* ctx, const GkBlock* blk, const GkBlock* dblk, uint32_t nbr, const uint8_t* src_bytes,
+                            int32_t* arena, bool index) {
+    hipStream_t st = ctx->st;
+    const uint32_t L = gk_t1dec_lanes();
+    const GkSoloPlan sp = gk_t1dec_solo_plan(nbr, L);
+    const bool shared = sp.forced < 0 && engines_busy(ctx->device) > 1;
+    std::vector<std::vector<uint32_t>> bins;
+    const uint32_t nsb = solo_split(blk, nbr, sp, shared, bins);
+    LaneTables H(bins, nbr, nsb, L), D = H;
+    H.bind(ctx->hord.get(H.bytes()));
+    lane_layout(blk, bins, L, H);
+    D.bind(ctx->dord.get(H.bytes()));
+    HIPCHK(hipMemcpyAsync(D.ord, H.ord, H.bytes(), hipMemcpyHostToDevice, st));
+    uint64_t* dscr = (uint64_t*)ctx->dscratch.get(8 * H.wo[H.nw] + 64);
+    // lane-parallel decoder state rows start at zero; solo waves write every row recon reads
+    HIPCHK(hipMemsetAsync(dscr + H.wo[H.nsw], 0, 8 * (H.wo[H.nw] - H.wo[H.nsw]), st));
+    gk_launch_t1_dec(st, src_bytes, dblk, D.ord, dscr, D.wo, H.nslots, H.nsw);
+    ctx->tm.t1_solo_blocks = nsb;
+    // classes whose split the shared rule chose (zeroed when the call began: a call may decode
+    // several classes); without solo waves (under 8 blocks) no rule is taken
+    ctx->tm.t1_shared += (shared && sp.waves) ? 1 : 0;
+    uint64_t sv[5] = {0, 0, 0, 0, 0};   // the launch's counters under GK_T1_STATS, else zero
+    if (getenv("GK_T1_STATS")) gk_t1dec_stats(sv);
+    ctx->tm.t1_steps_max = sv[0]; ctx->tm.t1_steps_total = sv[1]; ctx->tm.t1_symbols = sv[2];
+    ctx->tm.t1_solo_decisions = sv[3]; ctx->tm.t1_solo_decisions_max = sv[4];
     launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[3], st));
-    if (xc) {   // the indices are in place: the target coder's encoders take over
-        HIPCHK(hipStreamSynchronize(st));
-        xc->t2_parse_ms = ev_ms(ctx, 0, 1); xc->stage_ms = ev_ms(ctx, 1, 2); xc->t1_dec_ms = ev_ms(ctx, 2, 3);
-        ctx->tm.t1_blocks = nbr;
+    HIPCHK(hipEventRecord(ctx->ev[8], st));
+    uint32_t maxnp = 1;
+    for (uint32_t q = 0; q < nbr; ++q) maxnp = std::max<uint32_t>(maxnp, blk[q].numbps);
+    gk_launch_t1_recon(st, dblk, D.ids, D.pos, dscr, D.wo, arena, nbr, maxnp, index);
+}
+
+// One class run of the table: nbr entries at blk (on the device: dblk), decoder class cls
+// (Params::c_class); index: the planes take quantisation indices (a transcode)
+static void t1_decode_class(gk_ctx* ctx, const GkBlock* blk, const GkBlock* dblk, uint32_t nbr, uint32_t cls,
+                            const uint8_t* src_bytes, const std::vector<uint32_t>& seglen, int32_t* arena, bool index) {
+    hipStream_t st = ctx->st;
+    const bool cls_ht = (cls & 3) == 2, cls_generic = (cls & 3) == 1, cls_wide = (cls >> 8) & 1;
+    const uint32_t cls_sty = (cls >> 2) & 0x3f;
+    if (nbr == 0) return;   // nothing to decode (all-zero tiles)
+    if (cls_ht) {
+        // HT cleanup pass decode straight into the band windows (T1HT::decompress, T1HT.cpp:134-187)
+        uint32_t* dsel = (uint32_t*)ctx->dord.get(4 * (size_t)nbr + 16);
+        uint32_t* hsel = (uint32_t*)ctx->hord.get(4 * (size_t)nbr + 16);
+        for (uint32_t k = 0; k < nbr; ++k) hsel[k] = k;
+        HIPCHK(hipMemcpyAsync(dsel, hsel, 4 * (size_t)nbr, hipMemcpyHostToDevice, st));
+        int* derr = (int*)ctx->derr.get(64);
+        HIPCHK(hipMemsetAsync(derr, 0, 64, st));
+        gk_launch_ht_dec(st, src_bytes, dblk, dsel, arena, nbr, derr, cls_wide, index);
+        launch_check(__LINE__);
+        HIPCHK(hipEventRecord(ctx->ev[8], st));
+        int herr = 0;
+        HIPCHK(hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));   // the error word decides whether the call goes on
+        if (herr) throw GkError("corrupt HT code-block segment");
+    } else if (cls_generic) {
+        // mode switches or wide code-blocks: lane-per-block decoder over the codeword segments
+        // (gk_t1ms.hip)
+        uint32_t* dsl = nullptr;   // (segment tables for BYPASS / TERMALL classes only: one segment otherwise)
+        if ((cls_sty & (GK_STY_LAZY | GK_STY_TERMALL)) && !seglen.empty()) {
+            uint32_t* hsl = (uint32_t*)ctx->hord.get(4 * seglen.size());
+            memcpy(hsl, seglen.data(), 4 * seglen.size());
+            dsl = (uint32_t*)ctx->dseglen.get(4 * seglen.size());
+            HIPCHK(hipMemcpyAsync(dsl, hsl, 4 * seglen.size(), hipMemcpyHostToDevice, st));
+        }
+        uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(nbr));
+        gk_launch_t1_dec_ms(st, src_bytes, dblk, dsl, arena, nbr, mst, cls_sty, index);
+        launch_check(__LINE__);
+        HIPCHK(hipEventRecord(ctx->ev[8], st));
+        if (dsl) HIPCHK(hipStreamSynchronize(st));   // the pinned table is reused
+    } else {
+        t1_decode_lanes(ctx, blk, dblk, nbr, src_bytes, arena, index);
+    }
+}
+
+// The output rectangle of every component of the tile region RG clipped to the window, at
+// `red` discarded resolutions.  Reduced canvas: positions ceil(x / 2^red), on component c's grid
+// canvas positions first, ceil(x / dx), then reduced; output index = that less the image
+// origin's.  A window (image-relative, full resolution) reduces the same way (the composite
+// component bounds of CodeStreamDecompress.cpp:471-481, rectceildivpow2): the output is
+// the reduced tile rectangle clipped to it.  The caller plane's origin is the frame's (fx, fy):
+// the window's (a tile pass: the whole call's), or the image's.  (red = 0: ceil(x / 2^0) = x.)
+static OutRects output_rects(const Plan& P, const Region& RG, const uint32_t* win, uint32_t red, uint32_t fx, uint32_t fy) {
+    OutRects O;
+    O.c.resize(P.nc);
+    for (uint32_t c = 0; c < P.nc; ++c) {
+        const SGroup& G = P.groups[P.group_of[c]];
+        CompRect& r = O.c[c];
+        r.rox = ceildivpow2(G.ox, red); r.roy = ceildivpow2(G.oy, red);
+        auto rx = [&](uint32_t v) { return ceildivpow2(ceildiv(v + P.x0, G.dx), red) - r.rox; };
+        auto ry = [&](uint32_t v) { return ceildivpow2(ceildiv(v + P.y0, G.dy), red) - r.roy; };
+        r.x0 = rx(RG.x0); r.y0 = ry(RG.y0); r.x1 = rx(RG.x0 + RG.w); r.y1 = ry(RG.y0 + RG.h);
+        if (win) {
+            r.x0 = std::max(r.x0, rx(win[0])); r.y0 = std::max(r.y0, ry(win[1]));
+            r.x1 = std::min(r.x1, rx(win[2])); r.y1 = std::min(r.y1, ry(win[3]));
+            if (r.x1 <= r.x0 || r.y1 <= r.y0) O.win_empty = true;
+        }
+        r.wx0 = rx(fx); r.wy0 = ry(fy);
+    }
+    return O;
+}
+
+namespace {
+// Where the inverse MCT + DC shift + clamp writes component c's rectangle: the caller's device
+// planes at the rectangle, or a staging (tight rows) that core_to_host copies to the caller's
+// host planes
+struct CoreDst { std::vector<uint8_t*> p; std::vector<uint32_t> stride; };
+// DC shift and clamp per component (its precision and sign: mct::decompress_dc_shift_* per
+// component); 8 / 16-bit output takes the largest precision and one sign
+struct DcClamp { std::vector<int32_t> shift, mn, mx; };
+}  // namespace
+static uint8_t* caller_rect(const DecDst& out, const CompRect& r, uint32_t c, size_t es) {
+    return (uint8_t*)out.comps[c] + ((size_t)(r.y0 - r.wy0) * out.strides[c] + (r.x0 - r.wx0)) * es;
+}
+static CoreDst core_dst(gk_ctx* ctx, const DecDst& out, const OutRects& O, size_t es) {
+    const uint32_t nc = (uint32_t)O.c.size();
+    CoreDst D;
+    D.p.resize(nc); D.stride.resize(nc);
+    size_t tot = 0, o2 = 0;
+    for (const CompRect& r : O.c) tot += (size_t)(r.x1 - r.x0) * (r.y1 - r.y0);
+    uint8_t* stage = out.on_device ? nullptr : (uint8_t*)ctx->dplanes.get(tot * es + 16);
+    for (uint32_t c = 0; c < nc; ++c) {
+        const CompRect& r = O.c[c];
+        D.p[c] = stage ? stage + o2 * es : caller_rect(out, r, c, es);
+        D.stride[c] = stage ? r.x1 - r.x0 : out.strides[c];
+        o2 += (size_t)(r.x1 - r.x0) * (r.y1 - r.y0);
+    }
+    return D;
+}
+static void core_to_host(hipStream_t st, const DecDst& out, const OutRects& O, const CoreDst& D, size_t es) {
+    if (out.on_device) return;
+    for (uint32_t c = 0; c < (uint32_t)O.c.size(); ++c) {
+        const CompRect& r = O.c[c];
+        const uint32_t cols = r.x1 - r.x0, rows = r.y1 - r.y0;
+        HIPCHK(hipMemcpy2DAsync(caller_rect(out, r, c, es), (size_t)out.strides[c] * es, D.p[c], (size_t)cols * es,
+                                (size_t)cols * es, rows, hipMemcpyDeviceToHost, st));
+    }
+}
+
+// Inverse MCT of components 0 .. 2 (m3) or component c alone, DC shift and clamp of a w x h
+// rectangle from the work planes s into d, by component c's transform
+static void launch_mct_dc(hipStream_t st, const Plan& P, uint32_t c, bool m3, const int32_t* const s[3], uint32_t sstride,
+                          int stype, uint8_t* const d[3], uint32_t dstride, uint32_t w, uint32_t h, const DcClamp& dc) {
+    auto f = [&](uint32_t k) { return reinterpret_cast<const float*>(s[k]); };
+    const int32_t sh = dc.shift[c], mn = dc.mn[c], mx = dc.mx[c];
+    if (!P.p.c_irrev(c)) {
+        if (m3) gk_launch_rct_inv_dc(st, s[0], s[1], s[2], sstride, stype, d[0], d[1], d[2], dstride, w, h, sh, mn, mx);
+        else gk_launch_dc_inv(st, s[0], sstride, stype, d[0], dstride, w, h, sh, mn, mx);
+    } else {
+        if (m3) gk_launch_ict_inv_dc(st, f(0), f(1), f(2), sstride, stype, d[0], d[1], d[2], dstride, w, h, sh, mn, mx);
+        else gk_launch_dc_inv_f(st, f(0), sstride, stype, d[0], dstride, w, h, sh, mn, mx);
+    }
+}
+
+// Reduced resolution: resolution numres-1-red of each tile is at the tile's corner of plane
+// (red odd ? B : A); the inverse MCT + DC + clamp
+// writes it per tile into the ceil(size / 2^red) output (a tile's reduced origin is
+// ceil(origin / 2^red), B.5).  Subsampled components: the same on each component's grid
+// (tile-component ceil(tile / XRsiz), then reduced), one plane each.
+static void mct_reduced(gk_ctx* ctx, const TileRect& TR, const OutRects& O, const CoreDst& D, const DcClamp& dc,
+                        const int32_t* arena, int stype) {
+    hipStream_t st = ctx->st;
+    const Plan& P = ctx->plan;
+    const Region& RG = TR.RG;
+    const uint32_t red = ctx->dec_reduce;
+    const size_t es = gk_sample_size(stype);
+    const bool mct3 = P.mct3();
+    for (uint32_t j = TR.jb; j < TR.je; ++j)
+        for (uint32_t i = TR.ib; i < TR.ie; ++i) {
+            const TileG& T = P.tiles[(size_t)j * P.ntx + i];
+            for (uint32_t c = 0; c < P.nc;) {
+                const bool m3 = mct3 && c == 0;
+                const SGroup& G = P.groups[P.group_of[c]];
+                const CompRect& q = O.c[c];
+                // the tile-component and its reduced rectangle on the component's grid
+                const uint32_t cx0 = ceildiv(T.x0, G.dx), cy0 = ceildiv(T.y0, G.dy);
+                const uint32_t tx0 = ceildivpow2(cx0, red) - q.rox, ty0 = ceildivpow2(cy0, red) - q.roy;
+                const uint32_t tx1 = ceildivpow2(ceildiv(T.x1, G.dx), red) - q.rox;
+                const uint32_t ty1 = ceildivpow2(ceildiv(T.y1, G.dy), red) - q.roy;
+                // the part of the tile's reduced rectangle inside the output
+                const uint32_t ix0 = std::max(tx0, q.x0), iy0 = std::max(ty0, q.y0);
+                const uint32_t ix1 = std::min(tx1, q.x1), iy1 = std::min(ty1, q.y1);
+                const uint32_t cn = m3 ? 3 : 1;
+                if (ix1 <= ix0 || iy1 <= iy0) { c += cn; continue; }
+                const uint32_t tw = ix1 - ix0, th = iy1 - iy0;
+                const Region& Rg = TR.RGg[P.group_of[c]];
+                auto src = [&](uint32_t k) {
+                    return arena + (size_t)k * 2 * RG.plane + ((red & 1) ? RG.plane : 0) +
+                           (size_t)(cy0 - G.oy - Rg.y0 + (iy0 - ty0)) * RG.stride + (cx0 - G.ox - Rg.x0 + (ix0 - tx0));
+                };
+                auto dst = [&](uint32_t k) { return D.p[k] + ((size_t)(iy0 - O.c[k].y0) * D.stride[k] + (ix0 - O.c[k].x0)) * es; };
+                const int32_t* const s[3] = {src(c), m3 ? src(1) : nullptr, m3 ? src(2) : nullptr};
+                uint8_t* const d[3] = {dst(c), m3 ? dst(1) : nullptr, m3 ? dst(2) : nullptr};
+                launch_mct_dc(st, P, c, m3, s, RG.stride, stype, d, D.stride[c], tw, th, dc);
+                c += cn;
+            }
+        }
+    if (mct3 && (D.stride[1] != D.stride[0] || D.stride[2] != D.stride[0])) throw GkError("the first three components must share a stride");
+}
+
+// Full size: the inverse DWT, whose last level writes the output region through the inverse MCT
+// + DC shift + clamp into the output planes (l1_fusable), or the levels and then one MCT / DC
+// pass over the whole rectangle (also without decomposition levels)
+static void inverse_full(gk_ctx* ctx, const TileRect& TR, const OutRects& O, const CoreDst& D, const DcClamp& dc,
+                         int32_t* arena, int stype, bool partial) {
+    hipStream_t st = ctx->st;
+    const Plan& P = ctx->plan;
+    const Region& RG = TR.RG;
+    auto planeA = [&](uint32_t c) {
+        const Region& Rg = TR.RGg[P.group_of[c]];
+        return arena + (size_t)c * 2 * RG.plane + (size_t)(O.c[c].y0 - Rg.y0) * RG.stride + (O.c[c].x0 - Rg.x0);
+    };
+    const bool mct3 = P.mct3();
+    if (P.max_numres() > 1 && !P.l1_fusable)   // levels first, then the inverse MCT + DC shift + clamp below
+        run_dwt(ctx, RG, false, TR.jb, TR.je, TR.ib, TR.ie, nullptr, 1, partial);
+    if (P.max_numres() > 1 && P.l1_fusable) {
+        L1Io io;
+        io.stype = stype; io.mct3 = mct3; io.shift = dc.shift; io.mn = dc.mn; io.mx = dc.mx;
+        io.planes.assign(D.p.begin(), D.p.end());
+        io.strides = D.stride;
+        io.cx0 = TR.rx0 + P.x0; io.cy0 = TR.ry0 + P.y0; io.cx1 = TR.rx1 + P.x0; io.cy1 = TR.ry1 + P.y0;
+        if (mct3 && (D.stride[1] != D.stride[0] || D.stride[2] != D.stride[0])) throw GkError("the first three components must share a stride");
+        run_dwt(ctx, RG, false, TR.jb, TR.je, TR.ib, TR.ie, &io, 1, partial);
+        launch_check(__LINE__);
+        HIPCHK(hipEventRecord(ctx->ev[4], st));
         return;
     }
-    // ---- inverse DWT; its last level writes the output region through the inverse MCT + DC
-    // shift + clamp into the output planes (without decomposition levels a separate pass does)
-    // DC shift and clamp per component (its precision and sign: mct::decompress_dc_shift_* per
-    // component); 8 / 16-bit output takes the largest precision and one sign
-    std::vector<int32_t> shiftv(P.nc), mnv(P.nc), mxv(P.nc);
+    // (each component by its own transform: COC may differ; the MCT's three share component 0's)
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[4], st));
+    for (uint32_t c = 0; c < P.nc;) {
+        const bool m3 = mct3 && c == 0;
+        const int32_t* const s[3] = {planeA(c), m3 ? planeA(1) : nullptr, m3 ? planeA(2) : nullptr};
+        uint8_t* const d[3] = {D.p[c], m3 ? D.p[1] : nullptr, m3 ? D.p[2] : nullptr};
+        launch_mct_dc(st, P, c, m3, s, RG.stride, stype, d, D.stride[c], O.c[c].x1 - O.c[c].x0, O.c[c].y1 - O.c[c].y0, dc);
+        c += m3 ? 3 : 1;
+    }
+}
+
+// Inverse DWT, inverse MCT + DC shift + clamp into the output planes, copy back to host planes.
+// The two launch strategies (their launch counts differ) share rectangles, destination and copy.
+static void write_output(gk_ctx* ctx, const TileRect& TR, const OutRects& O, int32_t* arena, const DecDst& out, bool partial) {
+    hipStream_t st = ctx->st;
+    const Plan& P = ctx->plan;
+    const uint32_t red = ctx->dec_reduce;
+    DcClamp dc{std::vector<int32_t>(P.nc), std::vector<int32_t>(P.nc), std::vector<int32_t>(P.nc)};
     for (uint32_t c = 0; c < P.nc; ++c) {
         const uint32_t pr = P.c_prec(c);
         const bool sg = P.c_sgnd(c) != 0;
-        shiftv[c] = sg ? 0 : (1 << (pr - 1));
-        mnv[c] = sg ? -(1 << (pr - 1)) : 0;
-        mxv[c] = sg ? (1 << (pr - 1)) - 1 : (int32_t)((1u << pr) - 1);
-        if ((sample_bytes == 1 || sample_bytes == 2) && sg != (P.sgnd != 0))
+        dc.shift[c] = sg ? 0 : (1 << (pr - 1));
+        dc.mn[c] = sg ? -(1 << (pr - 1)) : 0;
+        dc.mx[c] = sg ? (1 << (pr - 1)) - 1 : (int32_t)((1u << pr) - 1);
+        if ((out.sample_bytes == 1 || out.sample_bytes == 2) && sg != (P.sgnd != 0))
             throw GkError("8 / 16-bit output of components with different signs: use int32 planes");
     }
-    const int stype = sample_type(sample_bytes, P.prec, P.sgnd != 0);
+    const int stype = sample_type(out.sample_bytes, P.prec, P.sgnd != 0);
     const size_t es = gk_sample_size(stype);
-    const bool mct3r = P.mct3();
-    if (red) {
-        // reduced resolution: undo levels L .. red+1; resolution numres-1-red of each tile is
-        // then at the tile's corner of plane (red odd ? B : A); the inverse MCT + DC + clamp
-        // writes it per tile into the ceil(size / 2^red) output (a tile's reduced origin is
-        // ceil(origin / 2^red), B.5).  Subsampled components: the same on each component's grid
-        // (tile-component ceil(tile / XRsiz), then reduced), one plane each.
-        run_dwt(ctx, RG, false, jb, je, ib, ie, nullptr, red + 1, rq.partial);
+    if (red) {   // undo levels L .. red+1
+        run_dwt(ctx, TR.RG, false, TR.jb, TR.je, TR.ib, TR.ie, nullptr, red + 1, partial);
         launch_check(__LINE__);
         HIPCHK(hipEventRecord(ctx->ev[4], st));
-        // reduced canvas: positions ceil(x / 2^red); output index = that less the image origin's.
-        // A window (image-relative, full resolution) reduces the same way (the composite
-        // component bounds of CodeStreamDecompress.cpp:471-481, rectceildivpow2): the output is
-        // the reduced tile rectangle clipped to it, the caller's planes addressing its origin
-        std::vector<uint32_t> rox(P.nc), roy(P.nc), qx0(P.nc), qy0(P.nc), qx1(P.nc), qy1(P.nc), wx0(P.nc, 0), wy0(P.nc, 0);
-        // (component c: canvas positions on its grid first, ceil(x / dx), then reduced)
-        for (uint32_t c = 0; c < P.nc; ++c) {
-            const SGroup& G = P.groups[P.group_of[c]];
-            auto rx = [&](uint32_t v) { return ceildivpow2(ceildiv(v, G.dx), red); };
-            auto ry = [&](uint32_t v) { return ceildivpow2(ceildiv(v, G.dy), red); };
-            rox[c] = ceildivpow2(G.ox, red); roy[c] = ceildivpow2(G.oy, red);
-            qx0[c] = rx(RG.x0 + P.x0) - rox[c]; qy0[c] = ry(RG.y0 + P.y0) - roy[c];
-            qx1[c] = rx(RG.x0 + P.x0 + RG.w) - rox[c]; qy1[c] = ry(RG.y0 + P.y0 + RG.h) - roy[c];
-            if (win) {
-                qx0[c] = std::max(qx0[c], rx(win[0] + P.x0) - rox[c]); qy0[c] = std::max(qy0[c], ry(win[1] + P.y0) - roy[c]);
-                qx1[c] = std::min(qx1[c], rx(win[2] + P.x0) - rox[c]);
-                qy1[c] = std::min(qy1[c], ry(win[3] + P.y0) - roy[c]);
-                if (qx1[c] <= qx0[c] || qy1[c] <= qy0[c]) throw GkError("the window is empty at this reduction");
-            }
-            // the caller plane's origin: the window's (a tile pass: the whole call's frame), or the image's
-            wx0[c] = rx(ox + P.x0) - rox[c]; wy0[c] = ry(oy + P.y0) - roy[c];
-        }
-        std::vector<uint8_t*> qd(P.nc);
-        std::vector<uint32_t> qs(P.nc);
-        if (!out_on_device) {
-            size_t tot = 0;
-            for (uint32_t c = 0; c < P.nc; ++c) tot += (size_t)(qx1[c] - qx0[c]) * (qy1[c] - qy0[c]);
-            uint8_t* stage = (uint8_t*)ctx->dplanes.get(tot * es + 16);
-            size_t o2 = 0;
-            for (uint32_t c = 0; c < P.nc; ++c) {
-                qd[c] = stage + o2 * es; qs[c] = qx1[c] - qx0[c];
-                o2 += (size_t)(qx1[c] - qx0[c]) * (qy1[c] - qy0[c]);
-            }
-        } else {
-            for (uint32_t c = 0; c < P.nc; ++c) {
-                qd[c] = (uint8_t*)comps[c] + ((size_t)(qy0[c] - wy0[c]) * strides[c] + (qx0[c] - wx0[c])) * es;
-                qs[c] = strides[c];
-            }
-        }
-        for (uint32_t j = jb; j < je; ++j)
-            for (uint32_t i = ib; i < ie; ++i) {
-                const TileG& T = P.tiles[(size_t)j * P.ntx + i];
-                for (uint32_t c = 0; c < P.nc;) {
-                    const bool m3 = mct3r && c == 0;
-                    const SGroup& G = P.groups[P.group_of[c]];
-                    // the tile-component and its reduced rectangle on the component's grid
-                    const uint32_t cx0 = ceildiv(T.x0, G.dx), cy0 = ceildiv(T.y0, G.dy);
-                    const uint32_t tx0 = ceildivpow2(cx0, red) - rox[c], ty0 = ceildivpow2(cy0, red) - roy[c];
-                    const uint32_t tx1 = ceildivpow2(ceildiv(T.x1, G.dx), red) - rox[c];
-                    const uint32_t ty1 = ceildivpow2(ceildiv(T.y1, G.dy), red) - roy[c];
-                    // the part of the tile's reduced rectangle inside the output
-                    const uint32_t ix0 = std::max(tx0, qx0[c]), iy0 = std::max(ty0, qy0[c]);
-                    const uint32_t ix1 = std::min(tx1, qx1[c]), iy1 = std::min(ty1, qy1[c]);
-                    const uint32_t cn = m3 ? 3 : 1;
-                    if (ix1 <= ix0 || iy1 <= iy0) { c += cn; continue; }
-                    const uint32_t tw = ix1 - ix0, th = iy1 - iy0;
-                    const Region& Rg = RGg[P.group_of[c]];
-                    auto src = [&](uint32_t k) {
-                        return arena + (size_t)k * 2 * RG.plane + ((red & 1) ? RG.plane : 0) +
-                               (size_t)(cy0 - G.oy - Rg.y0 + (iy0 - ty0)) * RG.stride + (cx0 - G.ox - Rg.x0 + (ix0 - tx0));
-                    };
-                    auto srcf = [&](uint32_t k) { return reinterpret_cast<const float*>(src(k)); };
-                    auto dst = [&](uint32_t k) { return qd[k] + ((size_t)(iy0 - qy0[k]) * qs[k] + (ix0 - qx0[k])) * es; };
-                    if (!P.p.c_irrev(c)) {
-                        if (m3) gk_launch_rct_inv_dc(st, src(0), src(1), src(2), RG.stride, stype, dst(0), dst(1), dst(2), qs[0],
-                                                     tw, th, shiftv[c], mnv[c], mxv[c]);
-                        else gk_launch_dc_inv(st, src(c), RG.stride, stype, dst(c), qs[c], tw, th, shiftv[c], mnv[c], mxv[c]);
-                    } else {
-                        if (m3) gk_launch_ict_inv_dc(st, srcf(0), srcf(1), srcf(2), RG.stride, stype, dst(0), dst(1), dst(2),
-                                                     qs[0], tw, th, shiftv[c], mnv[c], mxv[c]);
-                        else gk_launch_dc_inv_f(st, srcf(c), RG.stride, stype, dst(c), qs[c], tw, th, shiftv[c], mnv[c], mxv[c]);
-                    }
-                    c += cn;
-                }
-            }
-        if (mct3r && (qs[1] != qs[0] || qs[2] != qs[0])) throw GkError("the first three components must share a stride");
-        launch_check(__LINE__);
-        HIPCHK(hipEventRecord(ctx->ev[5], st));
-        if (!out_on_device)
-            for (uint32_t c = 0; c < P.nc; ++c) {
-                const uint32_t qcols = qx1[c] - qx0[c], qrows = qy1[c] - qy0[c];
-                HIPCHK(hipMemcpy2DAsync((uint8_t*)comps[c] + ((size_t)(qy0[c] - wy0[c]) * strides[c] + (qx0[c] - wx0[c])) * es,
-                                        (size_t)strides[c] * es, qd[c], (size_t)qcols * es, (size_t)qcols * es, qrows,
-                                        hipMemcpyDeviceToHost, st));
-            }
-        launch_check(__LINE__);
-        HIPCHK(hipEventRecord(ctx->ev[6], st));
-        HIPCHK(hipStreamSynchronize(st));
-        ctx->tm.t2_ms = ev_ms(ctx, 0, 1); ctx->tm.t1_ms = ev_ms(ctx, 2, 3); ctx->tm.t1_cm_ms = 0.f;
-        ctx->tm.t1_coder_ms = ev_ms(ctx, 2, 8); ctx->tm.cs_bytes = len; ctx->tm.t1_bytes = t1_bytes;
-        ctx->tm.dwt_ms = ev_ms(ctx, 3, 4); ctx->tm.mct_ms = ev_ms(ctx, 4, 5); ctx->tm.assemble_ms = ev_ms(ctx, 1, 2);
-        ctx->tm.total_ms = ev_ms(ctx, 0, 6); ctx->tm.t1_blocks = nbr;
-        return;
+        if (O.win_empty) throw GkError("the window is empty at this reduction");
     }
-    // the output rectangle of component c on its grid ([rx0, rx1) x [ry0, ry1) without
-    // subsampling), and the caller plane's origin there (the window's, or the image's)
-    std::vector<uint32_t> qx0(P.nc), qy0(P.nc), qx1(P.nc), qy1(P.nc), qox(P.nc), qoy(P.nc);
-    for (uint32_t c = 0; c < P.nc; ++c) {
-        const SGroup& G = P.groups[P.group_of[c]];
-        qx0[c] = ceildiv(rx0 + P.x0, G.dx) - G.ox; qx1[c] = ceildiv(rx1 + P.x0, G.dx) - G.ox;
-        qy0[c] = ceildiv(ry0 + P.y0, G.dy) - G.oy; qy1[c] = ceildiv(ry1 + P.y0, G.dy) - G.oy;
-        qox[c] = ceildiv(ox + P.x0, G.dx) - G.ox; qoy[c] = ceildiv(oy + P.y0, G.dy) - G.oy;
-    }
-    auto ocols = [&](uint32_t c) { return qx1[c] - qx0[c]; };
-    auto orows = [&](uint32_t c) { return qy1[c] - qy0[c]; };
-    std::vector<void*> dst(P.nc);
-    std::vector<uint32_t> dstr(P.nc);
-    if (!out_on_device) {
-        size_t tot = 0;
-        for (uint32_t c = 0; c < P.nc; ++c) tot += (size_t)ocols(c) * orows(c);
-        uint8_t* stage = (uint8_t*)ctx->dplanes.get(tot * es + 16);
-        size_t o2 = 0;
-        for (uint32_t c = 0; c < P.nc; ++c) {
-            dst[c] = stage + o2 * es; dstr[c] = ocols(c);
-            o2 += (size_t)ocols(c) * orows(c);
-        }
-    } else {
-        for (uint32_t c = 0; c < P.nc; ++c) {
-            dst[c] = (uint8_t*)comps[c] + ((size_t)(qy0[c] - qoy[c]) * strides[c] + (qx0[c] - qox[c])) * es;
-            dstr[c] = strides[c];
-        }
-    }
-    auto planeA = [&](uint32_t c) {
-        const Region& Rg = RGg[P.group_of[c]];
-        return arena + (size_t)c * 2 * RG.plane + (size_t)(qy0[c] - Rg.y0) * RG.stride + (qx0[c] - Rg.x0);
-    };
-    auto planeAf = [&](uint32_t c) { return reinterpret_cast<const float*>(planeA(c)); };
-    const bool mct3 = P.mct3();
-    if (P.max_numres() > 1 && !P.l1_fusable) {   // levels first, then the inverse MCT + DC shift + clamp below
-        run_dwt(ctx, RG, false, jb, je, ib, ie, nullptr, 1, rq.partial);
-    }
-    if (P.max_numres() > 1 && P.l1_fusable) {
-        L1Io io;
-        io.stype = stype; io.mct3 = mct3; io.shift = shiftv; io.mn = mnv; io.mx = mxv;
-        io.planes.assign(dst.begin(), dst.end());
-        io.strides = dstr;
-        io.cx0 = rx0 + P.x0; io.cy0 = ry0 + P.y0; io.cx1 = rx1 + P.x0; io.cy1 = ry1 + P.y0;
-        if (mct3 && (dstr[1] != dstr[0] || dstr[2] != dstr[0])) throw GkError("the first three components must share a stride");
-        run_dwt(ctx, RG, false, jb, je, ib, ie, &io, 1, rq.partial);
-        launch_check(__LINE__);
-        HIPCHK(hipEventRecord(ctx->ev[4], st));
-    } else {
-        // (each component by its own transform: COC may differ; the MCT's three share component 0's)
-        launch_check(__LINE__);
-        HIPCHK(hipEventRecord(ctx->ev[4], st));
-        if (mct3 && !P.p.c_irrev(0))
-            gk_launch_rct_inv_dc(st, planeA(0), planeA(1), planeA(2), RG.stride, stype, dst[0], dst[1], dst[2], dstr[0],
-                                 ocols(0), orows(0), shiftv[0], mnv[0], mxv[0]);
-        if (mct3 && P.p.c_irrev(0))
-            gk_launch_ict_inv_dc(st, planeAf(0), planeAf(1), planeAf(2), RG.stride, stype, dst[0], dst[1], dst[2], dstr[0],
-                                 ocols(0), orows(0), shiftv[0], mnv[0], mxv[0]);
-        for (uint32_t c = mct3 ? 3 : 0; c < P.nc; ++c) {
-            if (!P.p.c_irrev(c)) gk_launch_dc_inv(st, planeA(c), RG.stride, stype, dst[c], dstr[c], ocols(c), orows(c), shiftv[c], mnv[c], mxv[c]);
-            else gk_launch_dc_inv_f(st, planeAf(c), RG.stride, stype, dst[c], dstr[c], ocols(c), orows(c), shiftv[c], mnv[c], mxv[c]);
-        }
-    }
+    const CoreDst D = core_dst(ctx, out, O, es);
+    if (red) mct_reduced(ctx, TR, O, D, dc, arena, stype);
+    else inverse_full(ctx, TR, O, D, dc, arena, stype, partial);
     launch_check(__LINE__);
     HIPCHK(hipEventRecord(ctx->ev[5], st));
-    if (!out_on_device) {
-        for (uint32_t c = 0; c < P.nc; ++c)
-            HIPCHK(hipMemcpy2DAsync((uint8_t*)comps[c] + ((size_t)(qy0[c] - qoy[c]) * strides[c] + (qx0[c] - qox[c])) * es,
-                                    (size_t)strides[c] * es, dst[c], (size_t)ocols(c) * es, (size_t)ocols(c) * es, orows(c),
-                                    hipMemcpyDeviceToHost, st));
-    }
+    core_to_host(st, out, O, D, es);
     launch_check(__LINE__);
     HIPCHK(hipEventRecord(ctx->ev[6], st));
     HIPCHK(hipStreamSynchronize(st));
-    ctx->tm.t2_ms = ev_ms(ctx, 0, 1);
-    ctx->tm.t1_ms = ev_ms(ctx, 2, 3);
-    ctx->tm.t1_cm_ms = 0.f;
-    ctx->tm.t1_coder_ms = ev_ms(ctx, 2, 8);
-    ctx->tm.cs_bytes = len;
-    ctx->tm.t1_bytes = t1_bytes;
-    ctx->tm.dwt_ms = ev_ms(ctx, 3, 4);
-    ctx->tm.mct_ms = ev_ms(ctx, 4, 5);
-    ctx->tm.assemble_ms = ev_ms(ctx, 1, 2);
-    ctx->tm.total_ms = ev_ms(ctx, 0, 6);
-    ctx->tm.t1_blocks = nbr;
+}
+
+// The times and counts of a decode that ran to its output (events 0 .. 6, 8 of the call)
+static void decode_timings(gk_ctx* ctx, size_t cs_len, uint64_t t1_bytes, uint32_t nblk) {
+    gk_timings& tm = ctx->tm;
+    tm.t2_ms = ev_ms(ctx, 0, 1); tm.t1_ms = ev_ms(ctx, 2, 3); tm.t1_cm_ms = 0.f;
+    tm.t1_coder_ms = ev_ms(ctx, 2, 8); tm.cs_bytes = cs_len; tm.t1_bytes = t1_bytes;
+    tm.dwt_ms = ev_ms(ctx, 3, 4); tm.mct_ms = ev_ms(ctx, 4, 5); tm.assemble_ms = ev_ms(ctx, 1, 2);
+    tm.total_ms = ev_ms(ctx, 0, 6); tm.t1_blocks = nblk;
+}
+
+namespace {
+// What the parse leaves for T1, and what T1 leaves for the output (or a transcode's encoders)
+struct DecParsed {
+    TileRect TR;
+    std::vector<std::vector<uint8_t>> part_need;   // per tile part: which tile-local blocks reach the output
+    std::vector<PartState> ps;
+    HostClock::time_point h1, h2;                  // GK_PROFILE: the parse began / ended
+};
+struct DecT1 { int32_t* arena; uint32_t nblk; uint64_t t1_bytes; };
+}  // namespace
+
+// Tiles present, their rectangle, the code-blocks that reach the output, and the packet headers
+// of the tile parts in Hd.parts (whole_image: the rectangle is every tile of the image)
+static DecParsed decode_parse(gk_ctx* ctx, ByteSrc& S, const Header& Hd, const uint32_t* win, bool whole_image) {
+    const Plan& P = ctx->plan;
+    if (S.dev) prefetch_packet_headers(ctx, S, P, Hd);
+    DecParsed D;
+    D.TR = tile_rect(P, Hd.parts, win, whole_image);
+    // (on the canvas: the output rectangle moved by the image origin)
+    const uint32_t cw[4] = {D.TR.rx0 + P.x0, D.TR.ry0 + P.y0, D.TR.rx1 + P.x0, D.TR.ry1 + P.y0};
+    D.part_need.resize(Hd.parts.size());
+    host_pool().run(Hd.parts.size(), [&](size_t q) { blocks_needed(P, P.tiles[Hd.parts[q].tile], win ? cw : nullptr, D.part_need[q]); });
+    D.h1 = HostClock::now();
+    D.ps = parse_parts(P, S, Hd.parts, D.part_need, ctx->dec_layers, ctx->dec_reduce);
+    D.h2 = HostClock::now();
+    return D;
+}
+
+// Table, staging and the T1 decoders: the work planes (arena) then hold the coefficients of the
+// rectangle's tiles, or with index their quantisation indices.  h0: GK_PROFILE's start of the
+// host phases.
+static DecT1 decode_t1(gk_ctx* ctx, const ByteSrc& S, const Header& Hd, const DecParsed& D, bool index, HostClock::time_point h0) {
+    hipStream_t st = ctx->st;
+    const Plan& P = ctx->plan;
+    const TileRect& TR = D.TR;
+    // (the table is written straight into the pinned upload buffer: no vector growth, no extra copy)
+    size_t nmax = 0;
+    for (const auto& nd : D.part_need) nmax += (size_t)std::count(nd.begin(), nd.end(), (uint8_t)1);
+    GkBlock* blk = (GkBlock*)ctx->hinfo.get(sizeof(GkBlock) * std::max<size_t>(nmax, 1));
+    const BlockTable BT = fill_table(P, TR, D.part_need, D.ps, blk);
+    const uint32_t nblk = BT.nblk;
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[1], st));
+    const uint8_t* src_bytes = stage_bytes(ctx, S, D.ps, BT, blk);
+    // GK_PROFILE=1: host phase times of the decode (stderr)
+    static const bool prof = getenv("GK_PROFILE") != nullptr;
+    auto ms = [](HostClock::time_point a, HostClock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (prof)
+        fprintf(stderr, "decode host: headers+setup %.3f ms, packet headers %.3f ms, segments %.3f ms (%zu parts, "
+                        "%u blocks); %llu page fetches %.3f ms (cumulative)\n",
+                ms(h0, D.h1), ms(D.h1, D.h2), ms(D.h2, HostClock::now()), Hd.parts.size(), nblk,
+                (unsigned long long)ByteSrc::fetch_cnt.load(), ByteSrc::fetch_ns.load() * 1e-6);
+    const std::vector<std::pair<uint32_t, uint32_t>> runs = class_runs(P, blk, nblk);
+    GkBlock* dblk = (GkBlock*)ctx->dblocks.get(sizeof(GkBlock) * std::max(nblk, 1u));
+    HIPCHK(hipMemcpyAsync(dblk, blk, sizeof(GkBlock) * nblk, hipMemcpyHostToDevice, st));
+    ctx->blocks_uploaded = false;   // the encode table must be re-uploaded
+    int32_t* arena = (int32_t*)ctx->arena.get(TR.RG.plane * P.nc * 2 * sizeof(int32_t));
+    // tiles of the rectangle without a tile part decode as zero; blocks skipped by the window
+    // need no clearing (they only feed samples outside the output region)
+    if (Hd.parts.size() < (size_t)(TR.ie - TR.ib) * (TR.je - TR.jb))
+        HIPCHK(hipMemsetAsync(arena, 0, TR.RG.plane * P.nc * 2 * sizeof(int32_t), st));
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[2], st));
+    for (size_t k = 0; k < runs.size(); ++k) {
+        const uint32_t s0 = runs[k].first, e0 = k + 1 < runs.size() ? runs[k + 1].first : nblk;
+        if (k) HIPCHK(hipStreamSynchronize(st));   // (the pinned staging tables are reused per class)
+        t1_decode_class(ctx, blk + s0, dblk + s0, e0 - s0, runs[k].second, src_bytes, BT.seglen, arena, index);
+    }
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[3], st));
+    return DecT1{arena, nblk, BT.t1_bytes};
+}
+
+// The decode proper of the tile parts in Hd.parts, whose coding is Hd's and ctx->plan's, into
+// out: packet headers (T2), code-blocks (T1), inverse DWT and MCT, egress.  rq.win is the
+// rectangle written (null: the tile parts' own) and (fx, fy) the image-relative origin of out's
+// planes: the window's, and for a tile pass the whole call's.
+static void decode_core(gk_ctx* ctx, ByteSrc& S, const Header& Hd, const DecDst& out, const DecReq& rq, uint32_t fx, uint32_t fy,
+                        HostClock::time_point h0) {
+    const DecParsed D = decode_parse(ctx, S, Hd, rq.win, false);
+    const DecT1 T = decode_t1(ctx, S, Hd, D, false, h0);
+    const OutRects O = output_rects(ctx->plan, D.TR.RG, rq.win, ctx->dec_reduce, fx, fy);
+    write_output(ctx, D.TR, O, T.arena, out, rq.partial);
+    decode_timings(ctx, S.len, T.t1_bytes, T.nblk);
 }
 
 // The engine's plan for Hd's image and coding (the main header's, or a tile pass's own), with
@@ -7807,8 +7849,14 @@ static size_t xcode_call(gk_ctx* ctx, const DecSrc& src, const gk_transcode_para
     }
     merge_tile_parts(Hd);
     xcode_check_plan(P, Hd, X);
-    // the source coder's T1 decoders leave the indices in the work planes
-    decode_core(ctx, S, Hd, DecDst{nullptr, nullptr, nullptr, 0, 4, true}, DecReq{nullptr, false}, 0, 0, o.t0, &X);
+    // the source coder's T1 decoders leave the indices in the work planes, which hold the image
+    // (every tile: the encoders read them all); nothing is written out
+    const DecParsed D = decode_parse(ctx, S, Hd, nullptr, true);
+    for (size_t q = 0; q < Hd.parts.size(); ++q) xcode_check_part(P, Hd.parts[q], D.ps[q]);   // (before anything is staged or launched)
+    const DecT1 T = decode_t1(ctx, S, Hd, D, true, o.t0);
+    HIPCHK(hipStreamSynchronize(st));   // the indices are in place: the target coder's encoders take over
+    X.t2_parse_ms = ev_ms(ctx, 0, 1); X.stage_ms = ev_ms(ctx, 1, 2); X.t1_dec_ms = ev_ms(ctx, 2, 3);
+    ctx->tm.t1_blocks = T.nblk;
     // the target coder's T1 encoders and T2 on the same plan (its bands keep the source's
     // quantisation, band_qcd, as after a decode), under the target's parameters for this call
     struct Restore {

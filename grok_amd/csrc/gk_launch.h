@@ -58,6 +58,12 @@ void gk_launch_t1_mq(hipStream_t st, const uint8_t* sym, const uint64_t* sym_off
 void gk_launch_t1_weight(hipStream_t st, const int32_t* coef, const GkBlock* blocks, uint32_t* weight, uint32_t nblocks,
                          const uint8_t* roi = nullptr, uint64_t roi_mod = 0);
 uint32_t gk_t1dec_lanes();
+// The Part-1 decoder's per-lane scratch slab in 64-bit words (gk_t1dec.hip indexes it, the engine
+// allocates it): the state rows, then one plane of 64 rows per bit-plane of the largest numbps
+// (mp) among the blocks of the lane's wave
+#define GK_T1DEC_WS_FIXED 272
+#define GK_T1DEC_WS_PLANE 64
+static inline uint64_t gk_t1dec_lane_words(uint32_t mp) { return GK_T1DEC_WS_FIXED + (uint64_t)mp * GK_T1DEC_WS_PLANE; }
 // counters of the last k_t1_dec2 launch made with GK_T1_STATS set: max steps per wave, steps,
 // symbols (lane-parallel waves), decisions of the solo waves and of the busiest one
 void gk_t1dec_stats(uint64_t out[5]);

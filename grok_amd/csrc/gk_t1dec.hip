@@ -35,6 +35,7 @@
 #include <stdint.h>
 #include "gk_common.h"
 #include "gk_t1_common.h"
+#include "gk_launch.h"
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -49,8 +50,9 @@
 #define WS_N 4        // sign (set where significant)
 #define WS_P 8        // visited in SP of the current plane
 #define WS_M 12       // refined in an earlier plane
-#define WS_BITS 272   // numbps planes x 64 rows: bit of the plane (plane 0 = most significant)
-#define WS_FIXED 272
+#define WS_FIXED GK_T1DEC_WS_FIXED   // the state rows; a lane's slab is gk_t1dec_lane_words (gk_launch.h), which the host allocates
+#define WS_PLANE GK_T1DEC_WS_PLANE   // rows of one bit-plane
+#define WS_BITS WS_FIXED   // numbps planes x WS_PLANE rows: bit of the plane (plane 0 = most significant)
 
 // ------------------------------------------------------------------ MQ byte ring
 // Compressed bytes reach the coder through a 128-byte per-lane ring in LDS
@@ -137,7 +139,7 @@ __device__ __forceinline__ void st2(uint64_t* p, uint64_t a, uint64_t b) { *(ulo
 // ignores refinement rows; the first cleanup pass (k == 0) has no plane or visited rows yet.
 __device__ __forceinline__ void load_rows(Rows22& R, const uint64_t* WS, uint32_t k, uint32_t t, uint32_t y0) {
     const uint64_t* st = WS + 4 * y0;   // this stripe's line (y0 = 4 s)
-    const uint64_t* bt = WS + WS_BITS + (size_t)k * 64 + y0;
+    const uint64_t* bt = WS + WS_BITS + (size_t)k * WS_PLANE + y0;
     ld2(st + WS_S, R.s1, R.s2); ld2(st + WS_S + 2, R.s3, R.s4); R.s5 = st[16 + WS_S];
     if (t != 1) { ld2(st + WS_N, R.n1, R.n2); ld2(st + WS_N + 2, R.n3, R.n4); R.n5 = st[16 + WS_N]; }
     if (t != 0 && k != 0) { ld2(st + WS_P, R.p0, R.p1); ld2(st + WS_P + 2, R.p2, R.p3); ld2(bt, R.b0, R.b1); ld2(bt + 2, R.b2, R.b3); }
@@ -392,7 +394,7 @@ __device__ uint32_t solo_block(const uint8_t* __restrict__ bytes, const GkBlock&
     uint32_t k = 0, t = 2;   // plane (0 = most significant) and pass type (0 SP, 1 MR, 2 CL)
     auto flush_plane = [&](uint32_t kk) {
         const uint64_t rows = rows_of(BT, h, lane);
-        if ((uint32_t)lane < h) WS[WS_BITS + (size_t)kk * 64 + lane] = rows;
+        if ((uint32_t)lane < h) WS[WS_BITS + (size_t)kk * WS_PLANE + lane] = rows;
     };
     for (uint32_t pidx = 0; pidx < npasses && k < numbps; ++pidx) {
         for (uint32_t s = 0; s < ns; ++s) {
@@ -753,7 +755,7 @@ __global__ __launch_bounds__(64 * W) void k_t1_dec2(const uint8_t* __restrict__ 
                     uint64_t* sgp = WS + 4 * y0 + WS_S;
                     uint64_t* ngp = WS + 4 * y0 + WS_N;
                     uint64_t* pip = WS + 4 * y0 + WS_P;
-                    uint64_t* btp = WS + WS_BITS + (size_t)k * 64 + y0;
+                    uint64_t* btp = WS + WS_BITS + (size_t)k * WS_PLANE + y0;
                     if (t != 1 && wdirty) {   // MR changes neither significance nor signs
                         st2(sgp, S1, S2); st2(sgp + 2, S3, S4);
                         st2(ngp, N1, N2); st2(ngp + 2, N3, N4);
@@ -830,7 +832,7 @@ __global__ __launch_bounds__(64 * W) void k_t1_dec2(const uint8_t* __restrict__ 
                 uint64_t* sgp = WS + 4 * wy0 + WS_S;
                 uint64_t* ngp = WS + 4 * wy0 + WS_N;
                 uint64_t* pip = WS + 4 * wy0 + WS_P;
-                uint64_t* btp = WS + WS_BITS + (size_t)wk * 64 + wy0;
+                uint64_t* btp = WS + WS_BITS + (size_t)wk * WS_PLANE + wy0;
                 if (wt != 1 && wdirty) {
                     st2(sgp, W0, W1); st2(sgp + 2, W2, W3);
                     st2(ngp, W4, W5); st2(ngp + 2, W6, W7);
@@ -1091,7 +1093,7 @@ __global__ __launch_bounds__(64) void k_t1_recon(const GkBlock* __restrict__ blo
         const int np = min((int)numbps - bpl, (int)npmax);   // planes numbps-1 .. bpl, row i = numbps-1-p
         if (x < (int)h) {
 #pragma unroll 4
-            for (int i = 0; i < np; ++i) Lr[i * 64 + x] = WS[WS_BITS + (size_t)i * 64 + x];
+            for (int i = 0; i < np; ++i) Lr[i * 64 + x] = WS[WS_BITS + (size_t)i * WS_PLANE + x];
             Ls[x] = WS[4 * (x & ~3) + WS_N + (x & 3)];
         }
     }
@@ -1126,7 +1128,6 @@ __global__ __launch_bounds__(64) void k_t1_recon(const GkBlock* __restrict__ blo
     }
 }
 
-#include "gk_launch.h"
 // Blocks per 64-lane wave (GK_T1DEC_LANES, 1..64).
 uint32_t gk_t1dec_lanes() {
     // (read once; the language makes a function-local static's initialisation thread-safe)

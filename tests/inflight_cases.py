@@ -9,7 +9,7 @@ every round, failures collected per thread and reported by the main thread, join
 The oracle is the judge everywhere: encoded bytes equal oracle.encode's, decoded samples equal
 oracle.decode's, display output equals tests/display_ref.py applied to the oracle's planes.
 
-The shared packing rule (gk_engine.cpp t1_class, `shared`): while another engine of the device is
+The shared packing rule (gk_engine.cpp solo_split, `shared`): while another engine of the device is
 inside a call, a Part-1 decode gives a block to a solo wave only if it is heavier than 1.3 x the
 block at rank min(max(1024, top), nbr - 1), one block per wave, at most min(nbr / 4, waves) of them.
 shared_solo() restates it over the oracle's block lengths; shared_matrix() holds one case per edge.
