@@ -1495,26 +1495,24 @@ struct T2Enc {
                 }
         }
     }
-    // one band's packet body bytes; advances its code-blocks' pass counts
-    uint64_t band_body(const PrecG& PG, uint32_t l) {
+    // one band's packet body bytes; advances its code-blocks' pass counts.  seg (optional)
+    // receives (block, first byte, length) of every non-empty contribution
+    uint64_t band_body(const PrecG& PG, uint32_t l, std::vector<uint32_t>* seg = nullptr) {
         uint64_t sum = 0;
         for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
             const uint32_t b = PG.first_block + k;
             const uint32_t np = lnp[(size_t)b * L + l];
             if (!np) continue;
-            const uint32_t r0 = inprev[b] ? rate(b, inprev[b] - 1) : 0;
-            sum += rate(b, inprev[b] + np - 1) - r0;
+            const uint32_t r0 = inprev[b] ? rate(b, inprev[b] - 1) : 0, r1 = rate(b, inprev[b] + np - 1);
+            if (seg && r1 > r0) { seg->push_back(b); seg->push_back(r0); seg->push_back(r1 - r0); }
+            sum += r1 - r0;
             inprev[b] = (uint16_t)(inprev[b] + np);
         }
         return sum;
     }
 
     // One packet.  budget: remaining bytes (nullptr = unbounded).  seg (optional) receives
-    // (block, first byte, length) body segments.  Returns false when the budget is exceeded.
-    bool write_packet(const ResG& R, uint32_t pi, uint32_t l, uint64_t* budget,
-                      std::vector<uint32_t>* seg) {
-        return write_packet(R, pi, l, budget, seg, hdr);
-    }
+    // (block, first byte, length) of every non-empty body segment.  Returns false when the budget is exceeded.
     // hdr_out: the packet header bytes (a per-thread buffer when tiles are written in parallel;
     // all other state touched is per code-block / per precinct, i.e. disjoint across tiles).
     // With a budget the header is only counted, as compressPacketSimulate (T2Compress.cpp:
@@ -1577,7 +1575,7 @@ struct T2Enc {
                     if (M != UMAX) M -= r1 - r0;
                     counted += r1 - r0;
                 }
-                if (seg) { seg->push_back(b); seg->push_back(r0); seg->push_back(r1 - r0); }
+                if (seg && r1 > r0) { seg->push_back(b); seg->push_back(r0); seg->push_back(r1 - r0); }
                 if (body_bytes) *body_bytes += r1 - r0;
                 inprev[b] = (uint16_t)(inprev[b] + np);
             }
@@ -2483,6 +2481,7 @@ struct T2Enc {
 
 static void put16(std::vector<uint8_t>& o, uint32_t v) { o.push_back((uint8_t)(v >> 8)); o.push_back((uint8_t)v); }
 static void put32(std::vector<uint8_t>& o, uint32_t v) { put16(o, v >> 16); put16(o, v & 0xffff); }
+static void store_be(uint8_t* p, uint64_t v, int n) { for (int k = 0; k < n; ++k) p[k] = (uint8_t)(v >> (8 * (n - 1 - k))); }   // n bytes, big-endian, in place
 
 // POC marker (A.6.6, CodeStreamCompress::writePoc :1278-1340): per entry RSpoc, CSpoc (1 or 2
 // bytes), LYEpoc (2), REpoc, CEpoc (1 or 2), Ppoc.  clamp (a tile-part POC): layers /
@@ -2508,18 +2507,46 @@ static void write_poc(std::vector<uint8_t>& o, const std::vector<Poc>& pocs, uin
 
 // Main header: SOC SIZ [CAP] COD QCD [TLM] [POC] [RGN] [COM]  (CodeStreamCompress::init_header_writing
 // :822-860; marker writers :1054-1685)
-static void write_main_header(std::vector<uint8_t>& o, const Plan& P, size_t* tlm_pos = nullptr) {
+// SOC and SIZ.  per_comp: Ssiz from each component's own precision and sign (a transcode's source)
+static void write_soc_siz(std::vector<uint8_t>& o, const Plan& P, uint32_t rsiz, bool per_comp) {
     put16(o, 0xff4f);
     put16(o, 0xff51); put16(o, 38 + 3 * P.nc);
-    put16(o, P.p.ht() ? 0x4000 : 0);   // Rsiz: GRK_JPH_RSIZ_FLAG for HT (CodeStreamCompress.cpp:216-219)
+    put16(o, rsiz);
     put32(o, P.x0 + P.w); put32(o, P.y0 + P.h); put32(o, P.x0); put32(o, P.y0);   // Xsiz Ysiz XOsiz YOsiz
     put32(o, P.p.tw ? P.p.tw : P.x0 + P.w - P.gx0); put32(o, P.p.th ? P.p.th : P.y0 + P.h - P.gy0);
     put32(o, P.gx0); put32(o, P.gy0);                                              // XTsiz YTsiz XTOsiz YTOsiz
     put16(o, P.nc);
     for (uint32_t i = 0; i < P.nc; ++i) {   // Ssiz, XRsiz, YRsiz
-        o.push_back((uint8_t)((P.prec - 1) | (P.sgnd ? 0x80 : 0)));
+        o.push_back((uint8_t)(((per_comp ? P.c_prec(i) : P.prec) - 1) | ((per_comp ? P.c_sgnd(i) : P.sgnd) ? 0x80 : 0)));
         o.push_back((uint8_t)P.sx(i)); o.push_back((uint8_t)P.sy(i));
     }
+}
+// COD.  Scod: precincts and the given SOP / EPH bits
+static void write_cod(std::vector<uint8_t>& o, const Plan& P, uint32_t sop_eph, uint32_t nlayers, uint32_t mct) {
+    put16(o, 0xff52); put16(o, 12 + (P.p.custom_prc ? P.p.numres : 0));
+    o.push_back((uint8_t)((P.p.custom_prc ? 1 : 0) | sop_eph));
+    o.push_back((uint8_t)P.p.prog);   // progression order
+    put16(o, nlayers);
+    o.push_back((uint8_t)mct);
+    o.push_back((uint8_t)(P.p.numres - 1));
+    o.push_back((uint8_t)(P.p.cbw - 2)); o.push_back((uint8_t)(P.p.cbh - 2));
+    o.push_back((uint8_t)P.p.cblk_sty);
+    o.push_back(P.p.irrev ? 0 : 1);
+    if (P.p.custom_prc) for (uint32_t r = 0; r < P.p.numres; ++r) o.push_back((uint8_t)(P.p.prcw[r] | (P.p.prch[r] << 4)));
+}
+// RGN per component with an ROI shift (CodeStreamCompress::write_regions / write_rgn :746-780, 1397-1410)
+static void write_rgn(std::vector<uint8_t>& o, const Plan& P) {
+    for (uint32_t c = 0; c < P.nc; ++c)
+        if (P.p.roi(c)) {
+            const uint32_t cw = P.nc <= 256 ? 1 : 2;
+            put16(o, 0xff5e); put16(o, 4 + cw);
+            if (cw == 1) o.push_back((uint8_t)c); else put16(o, c);
+            o.push_back(0);   // Srgn: implicit (maxshift)
+            o.push_back((uint8_t)P.p.roi(c));
+        }
+}
+static void write_main_header(std::vector<uint8_t>& o, const Plan& P, size_t* tlm_pos = nullptr) {
+    write_soc_siz(o, P, P.p.ht() ? 0x4000 : 0, false);   // Rsiz: GRK_JPH_RSIZ_FLAG for HT (CodeStreamCompress.cpp:216-219)
     if (P.p.ht()) {   // CAP (CodeStreamCompress::write_cap :1064-1111): Pcap bit 15, Ccap = MAGBp code
         uint32_t B = 0;
         // param_qcd::get_MAGBp (HTParams.cpp:318-336): scalar expounded bands count from their
@@ -2537,16 +2564,7 @@ static void write_main_header(std::vector<uint8_t>& o, const Plan& P, size_t* tl
         uint32_t Bp = B <= 8 ? 0 : B < 28 ? B - 8 : B < 48 ? 13 + (B >> 2) : 31;
         put16(o, 0xff50); put16(o, 8); put32(o, 0x00020000); put16(o, (P.p.irrev ? 0x20 : 0) | Bp);
     }
-    put16(o, 0xff52); put16(o, 12 + (P.p.custom_prc ? P.p.numres : 0));
-    o.push_back((uint8_t)((P.p.custom_prc ? 1 : 0) | P.p.sop_eph));   // Scod: precincts, SOP, EPH
-    o.push_back((uint8_t)P.p.prog);   // progression order
-    put16(o, P.p.nlayers);
-    o.push_back((uint8_t)((P.p.mct && P.nc >= 3) ? 1 : 0));
-    o.push_back((uint8_t)(P.p.numres - 1));
-    o.push_back((uint8_t)(P.p.cbw - 2)); o.push_back((uint8_t)(P.p.cbh - 2));
-    o.push_back((uint8_t)P.p.cblk_sty);
-    o.push_back(P.p.irrev ? 0 : 1);
-    if (P.p.custom_prc) for (uint32_t r = 0; r < P.p.numres; ++r) o.push_back((uint8_t)(P.p.prcw[r] | (P.p.prch[r] << 4)));
+    write_cod(o, P, P.p.sop_eph, P.p.nlayers, (P.p.mct && P.nc >= 3) ? 1 : 0);
     uint32_t nbands = 3 * P.p.numres - 2;
     put16(o, 0xff5c);
     const CompG& C = P.tiles[0].comps[0];
@@ -2572,14 +2590,7 @@ static void write_main_header(std::vector<uint8_t>& o, const Plan& P, size_t* tl
     // POC of tile 0 in the main header (init_header_writing :839-840), entries as given: writePoc
     // (:1278-1340) writes each before clamping it to the tile's layers / resolutions / components
     if (!P.p.pocs.empty()) write_poc(o, P.p.pocs, P.nc, nullptr);
-    for (uint32_t c = 0; c < P.nc; ++c)   // RGN (CodeStreamCompress::write_regions / write_rgn :746-780, 1397-1410)
-        if (P.p.roi(c)) {
-            const uint32_t cw = P.nc <= 256 ? 1 : 2;
-            put16(o, 0xff5e); put16(o, 4 + cw);
-            if (cw == 1) o.push_back((uint8_t)c); else put16(o, c);
-            o.push_back(0);   // Srgn: implicit (maxshift)
-            o.push_back((uint8_t)P.p.roi(c));
-        }
+    write_rgn(o, P);
     if (!P.p.comments.empty()) {   // (CodeStreamCompress::write_com :1114-1145)
         for (const auto& c : P.p.comments) {
             put16(o, 0xff64); put16(o, 4 + (uint32_t)c.second.size()); put16(o, c.first);
@@ -4251,17 +4262,7 @@ struct Xcode {
 // read, band_qcd in the plan's bands), RGN and COM, with the target coder's code-block style, Rsiz
 // bit 14 and CAP; markers in write_main_header's order.
 static void write_xcode_header(std::vector<uint8_t>& o, const Plan& P, const Xcode& X, size_t* tlm_pos) {
-    put16(o, 0xff4f);
-    put16(o, 0xff51); put16(o, 38 + 3 * P.nc);
-    put16(o, P.p.ht() ? (X.rsiz | 0x4000u) : (X.rsiz & ~0x4000u));
-    put32(o, P.x0 + P.w); put32(o, P.y0 + P.h); put32(o, P.x0); put32(o, P.y0);
-    put32(o, P.p.tw ? P.p.tw : P.x0 + P.w - P.gx0); put32(o, P.p.th ? P.p.th : P.y0 + P.h - P.gy0);
-    put32(o, P.gx0); put32(o, P.gy0);
-    put16(o, P.nc);
-    for (uint32_t i = 0; i < P.nc; ++i) {
-        o.push_back((uint8_t)((P.c_prec(i) - 1) | (P.c_sgnd(i) ? 0x80 : 0)));
-        o.push_back((uint8_t)P.sx(i)); o.push_back((uint8_t)P.sy(i));
-    }
+    write_soc_siz(o, P, P.p.ht() ? (X.rsiz | 0x4000u) : (X.rsiz & ~0x4000u), true);
     if (P.p.ht()) {
         // CAP: MAGBp bounds the coded magnitudes.  Reversible: the largest band bit-plane count of
         // the stream, exponent + guard bits - 1 plus the component's ROI shift (the bands' numbps
@@ -4278,16 +4279,7 @@ static void write_xcode_header(std::vector<uint8_t>& o, const Plan& P, const Xco
         const uint32_t Bp = B <= 8 ? 0 : B < 28 ? B - 8 : B < 48 ? 13 + (B >> 2) : 31;
         put16(o, 0xff50); put16(o, 8); put32(o, 0x00020000); put16(o, (P.p.irrev ? 0x20 : 0) | Bp);
     }
-    put16(o, 0xff52); put16(o, 12 + (P.p.custom_prc ? P.p.numres : 0));
-    o.push_back((uint8_t)(P.p.custom_prc ? 1 : 0));   // Scod: no SOP / EPH
-    o.push_back((uint8_t)P.p.prog);
-    put16(o, 1);                                      // one layer
-    o.push_back((uint8_t)X.mct);
-    o.push_back((uint8_t)(P.p.numres - 1));
-    o.push_back((uint8_t)(P.p.cbw - 2)); o.push_back((uint8_t)(P.p.cbh - 2));
-    o.push_back((uint8_t)P.p.cblk_sty);
-    o.push_back(P.p.irrev ? 0 : 1);
-    if (P.p.custom_prc) for (uint32_t r = 0; r < P.p.numres; ++r) o.push_back((uint8_t)(P.p.prcw[r] | (P.p.prch[r] << 4)));
+    write_cod(o, P, 0, 1, X.mct);   // no SOP / EPH, one layer, the source's MCT byte
     put16(o, 0xff5c); put16(o, 2 + (uint32_t)X.qcd_body.size());
     o.insert(o.end(), X.qcd_body.begin(), X.qcd_body.end());
     for (uint32_t c = 0; c < P.nc; ++c)
@@ -4304,14 +4296,7 @@ static void write_xcode_header(std::vector<uint8_t>& o, const Plan& P, const Xco
         if (tlm_pos) *tlm_pos = o.size();
         o.insert(o.end(), (size_t)(6 * (size_t)nt), 0);
     }
-    for (uint32_t c = 0; c < P.nc; ++c)
-        if (P.p.roi(c)) {
-            const uint32_t cw = P.nc <= 256 ? 1 : 2;
-            put16(o, 0xff5e); put16(o, 4 + cw);
-            if (cw == 1) o.push_back((uint8_t)c); else put16(o, c);
-            o.push_back(0);
-            o.push_back((uint8_t)P.p.roi(c));
-        }
+    write_rgn(o, P);
     if (X.com)
         for (const auto& c : X.coms) {
             put16(o, 0xff64); put16(o, 4 + (uint32_t)c.second.size()); put16(o, c.first);
@@ -4319,56 +4304,68 @@ static void write_xcode_header(std::vector<uint8_t>& o, const Plan& P, const Xco
         }
 }
 
-static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
-                          int comps_on_device, const gk_cparameters* cp, uint8_t* out, size_t cap, int out_on_device,
-                          int* rc, uint32_t tb = 0, uint32_t te = 0, bool with_header = true,
-                          uint32_t* part_lens = nullptr, bool blocks_only = false, const PixSrc* pix = nullptr,
-                          const EncConvCall* cv = nullptr, const Xcode* xc = nullptr) {
-    // xc (a transcode): the plan is the target's and work plane A holds the source's quantisation
-    // indices; the call starts at T1 and writes the header the transcode keeps
-    if (!xc) setup_plan(ctx, info, cp, cv, blocks_only ? QC_BLOCKS : part_lens ? QC_TILES : QC_ENCODE);
-    Plan& P = ctx->plan;
-    // gk_set_encode_quant (a transcode keeps its source's QCD): STEP is in the plan already
-    const EncQuant quant = xc ? EncQuant() : ctx->enc_quant;
-    gk_quant_result& qres = ctx->quant_res;
-    qres = gk_quant_result();
-    qres.mode = quant.mode;
-    const uint32_t ntiles = (uint32_t)P.tiles.size();
+// ---- The encode core: encode_impl drives the stages below.  A stage takes what it reads and
+// returns what it makes; the ones without a gk_ctx touch no device (tools/encode_stages_check.cpp).
+using HostClock = std::chrono::steady_clock;
+namespace {
+// launch_check at the caller's line, then event i of the call on its stream
+static void enc_mark(gk_ctx* ctx, int i, int line) { launch_check(line); HIPCHK(hipEventRecord(ctx->ev[i], ctx->st)); }
+// What a call encodes: planes, packed pixels (pix) or a transcode (xc: the plan is the target's and
+// work plane A holds the source's quantisation indices), through an optional conversion (cv)
+struct EncSrc {
+    const void* const* comps = nullptr; const uint32_t* strides = nullptr; bool on_device = true;
+    const PixSrc* pix = nullptr; const Xcode* xc = nullptr; const EncConvCall* cv = nullptr;
+};
+// What it writes: tiles [tb, te) (te 0: all of them), with the main header or (gk_encode_tiles)
+// as bare tile parts whose lengths go to part_lens, or (gk_encode_blocks) the T1 results alone
+struct EncReq {
+    uint32_t tb = 0, te = 0, *part_lens = nullptr;
+    bool with_header = true, blocks_only = false;
+    uint8_t* out = nullptr; size_t cap = 0; bool out_on_device = false;
+};
+struct EncLen { size_t n; bool fits; };   // the stream's length; !fits: above cap, nothing written
+// The tiles of a call: their blocks [b0, b1), tile rows [jb, je), image rows [ry0, ry1), the work
+// planes for those rows (RG) and their byte slots (host bytes are staged after slot_span)
+struct EncRange {
+    uint32_t tb, te, b0, b1, nbr, jb, je, ry0, ry1; Region RG; uint64_t slot0, slot_span;
+};
+// The samples on the device: per component a plane of sample type stype; RGg: RG on each sampling group's grid
+struct EncPlanes {
+    int stype = GK_S32; std::vector<Region> RGg;
+    std::vector<const void*> src; std::vector<uint32_t> sstr;
+};
+
+static EncRange enc_range(const Plan& P, uint32_t tb, uint32_t te) {
+    const uint32_t ntiles = (uint32_t)P.tiles.size(), nb = (uint32_t)P.blocks.size();
     if (te == 0) { tb = 0; te = ntiles; }
     if (tb >= te || te > ntiles) throw GkError("bad tile range");
-    const bool sub = P.subsampled();
-    const uint32_t nb = (uint32_t)P.blocks.size();
-    const uint32_t b0 = P.tiles[tb].b0, b1 = P.tiles[te - 1].b1, nbr = b1 - b0;   // block range of the tiles
-    const uint32_t jb = tb / P.ntx, je = (te - 1) / P.ntx + 1;                     // tile rows touched
-    const uint32_t ry0 = P.tiles[jb * P.ntx].y0 - P.y0, ry1 = P.tiles[(je - 1) * P.ntx].y1 - P.y0;  // image rows touched
-    hipStream_t st = ctx->st;
+    EncRange R{}; R.tb = tb; R.te = te;
+    R.b0 = P.tiles[tb].b0; R.b1 = P.tiles[te - 1].b1; R.nbr = R.b1 - R.b0;
+    R.jb = tb / P.ntx; R.je = (te - 1) / P.ntx + 1;
+    R.ry0 = P.tiles[R.jb * P.ntx].y0 - P.y0; R.ry1 = P.tiles[(R.je - 1) * P.ntx].y1 - P.y0;
+    R.RG = make_region(0, R.ry0, P.w, R.ry1); R.slot0 = P.blocks[R.b0].data_off;
+    R.slot_span = (R.b1 < nb ? P.blocks[R.b1].data_off : P.slot_bytes) - R.slot0;
+    return R;
+}
 
-    launch_check(__LINE__);
-
-    HIPCHK(hipEventRecord(ctx->ev[0], st));
-    // work planes for the sample rows of the selected tiles only
-    const Region RG = make_region(0, ry0, P.w, ry1);
-    int32_t* arena = (int32_t*)ctx->arena.get(RG.plane * P.nc * 2 * sizeof(int32_t));
-    if (xc) {
-        HIPCHK(hipEventRecord(ctx->ev[1], st));
-        HIPCHK(hipEventRecord(ctx->ev[2], st));
-    } else {
-    const uint32_t nrows = ry1 - ry0;
-    // the caller's planes (int32 or 8/16-bit samples); host planes are staged (those rows only)
-    const int stype = sample_type(info->sample_bytes, P.prec, P.sgnd != 0);
-    const size_t es = gk_sample_size(stype);
-    std::vector<const void*> src(P.nc);
-    std::vector<uint32_t> sstr(P.nc);
-    // component c reads the rows of the selected tiles on its grid (the region on its sampling
-    // group's grid: every row of the image width); host planes are staged back to back
-    std::vector<Region> RGg;
-    for (const SGroup& G : P.groups) RGg.push_back(group_region(P, RG, G));
-    if (cv) {
+// rows of the host's on the device at their tight width
+static void* stage_rows(hipStream_t st, void* dst, const void* src, size_t pitch, size_t tight, uint32_t rows) {
+    HIPCHK(hipMemcpy2DAsync(dst, tight, src, pitch, tight, rows, hipMemcpyHostToDevice, st)); return dst;
+}
+// The caller's samples (int32 or 8/16-bit) as device planes: component c reads the rows of the
+// selected tiles on its grid (every row of the image width); host input is staged, those rows only
+static EncPlanes stage_samples(gk_ctx* ctx, const gk_image_info* info, const EncSrc& S, const Region& RG) {
+    const Plan& P = ctx->plan; hipStream_t st = ctx->st;
+    EncPlanes E; E.stype = sample_type(info->sample_bytes, P.prec, P.sgnd != 0);
+    const size_t es = gk_sample_size(E.stype);
+    E.src.resize(P.nc); E.sstr.resize(P.nc);
+    for (const SGroup& G : P.groups) E.RGg.push_back(group_region(P, RG, G));
+    const PixSrc* pix = S.pix;
+    if (const EncConvCall* cv = S.cv) {
         // R, G, B (packed pixels or three planes of the image's size; the whole image: tile ranges
         // are refused under a conversion) become Y, Cb, Cr in dplanes, each plane at its own size,
-        // rows starting on GK_UNPIX_ALIGN bytes; host input is staged at its tight width first
-        const Region& RY = RGg[P.group_of[0]];
-        const Region& RC = RGg[P.group_of[1]];
+        // rows starting on GK_UNPIX_ALIGN bytes
+        const Region &RY = E.RGg[P.group_of[0]], &RC = E.RGg[P.group_of[1]];
         GkRgbYccArgs ca{};
         ca.w = RY.w; ca.h = RY.h; ca.cw = RC.w; ca.ch = RC.h;
         ca.mode = cv->c.mode(); ca.prec = P.prec;
@@ -4384,792 +4381,864 @@ static size_t encode_impl(gk_ctx* ctx, const gk_image_info* info, const void* co
             const size_t tight = (size_t)ca.w * 3 * es;
             ca.packed = 1; ca.src[0] = pix->pixels; ca.row_bytes = pix->row_bytes;
             if (!pix->on_device) {
-                void* in = ctx->dpix_in.get(tight * ca.h);
-                HIPCHK(hipMemcpy2DAsync(in, tight, pix->pixels, pix->row_bytes, tight, ca.h, hipMemcpyHostToDevice, st));
-                ca.src[0] = in; ca.row_bytes = tight;
+                ca.src[0] = stage_rows(st, ctx->dpix_in.get(tight * ca.h), pix->pixels, pix->row_bytes, tight, ca.h);
+                ca.row_bytes = tight;
             }
         } else {
             const size_t tight = (size_t)ca.w * es;
-            uint8_t* in = comps_on_device ? nullptr : (uint8_t*)ctx->dpix_in.get(tight * ca.h * 3);
+            uint8_t* in = S.on_device ? nullptr : (uint8_t*)ctx->dpix_in.get(tight * ca.h * 3);
             for (uint32_t c = 0; c < 3; ++c) {
-                ca.src[c] = comps[c]; ca.ss[c] = strides[c];
-                if (comps_on_device) continue;
-                HIPCHK(hipMemcpy2DAsync(in + c * tight * ca.h, tight, comps[c], (size_t)strides[c] * es, tight, ca.h,
-                                        hipMemcpyHostToDevice, st));
-                ca.src[c] = in + c * tight * ca.h; ca.ss[c] = ca.w;
+                ca.src[c] = S.comps[c]; ca.ss[c] = S.strides[c];
+                if (S.on_device) continue;
+                ca.src[c] = stage_rows(st, in + c * tight * ca.h, S.comps[c], (size_t)S.strides[c] * es, tight, ca.h);
+                ca.ss[c] = ca.w;
             }
         }
         gk_launch_rgb_ycc(st, (int)es, ca);
-        src[0] = ca.y; src[1] = ca.cb; src[2] = ca.cr;
-        sstr[0] = ca.ys; sstr[1] = sstr[2] = ca.cs;
+        E.src[0] = ca.y; E.src[1] = ca.cb; E.src[2] = ca.cr; E.sstr[0] = ca.ys; E.sstr[1] = E.sstr[2] = ca.cs;
     } else if (pix) {
-        // packed pixels (one grid): the touched rows, staged at their tight width when they are the
-        // host's, are separated into nc planes whose rows start on GK_UNPIX_ALIGN bytes
+        // packed pixels (one grid): the touched rows are separated into nc planes whose rows start
+        // on GK_UNPIX_ALIGN bytes
         const size_t tight = (size_t)RG.w * P.nc * es;
         const uint8_t* first = (const uint8_t*)pix->pixels + (size_t)RG.y0 * pix->row_bytes;
         GkUnpixArgs ua{};
-        ua.ds = align_up(RG.w, GK_UNPIX_ALIGN);
-        ua.plane = (uint64_t)ua.ds * RG.h;
+        ua.ds = align_up(RG.w, GK_UNPIX_ALIGN); ua.plane = (uint64_t)ua.ds * RG.h;
         ua.w = RG.w; ua.h = RG.h; ua.nch = P.nc;
-        ua.dst = ctx->dplanes.get(ua.plane * P.nc * es);
-        ua.src = first; ua.row_bytes = pix->row_bytes;
+        ua.dst = ctx->dplanes.get(ua.plane * P.nc * es); ua.src = first; ua.row_bytes = pix->row_bytes;
         if (!pix->on_device) {
-            void* dp = ctx->dpix_in.get(tight * RG.h);
-            HIPCHK(hipMemcpy2DAsync(dp, tight, first, pix->row_bytes, tight, RG.h, hipMemcpyHostToDevice, st));
-            ua.src = dp; ua.row_bytes = tight;
+            ua.src = stage_rows(st, ctx->dpix_in.get(tight * RG.h), first, pix->row_bytes, tight, RG.h);
+            ua.row_bytes = tight;
         }
         gk_launch_unpixels(st, (int)es, ua);
-        for (uint32_t c = 0; c < P.nc; ++c) { src[c] = (const uint8_t*)ua.dst + (size_t)c * ua.plane * es; sstr[c] = ua.ds; }
+        for (uint32_t c = 0; c < P.nc; ++c) { E.src[c] = (const uint8_t*)ua.dst + (size_t)c * ua.plane * es; E.sstr[c] = ua.ds; }
     } else {
-        size_t tot = 0;
-        for (uint32_t c = 0; c < P.nc; ++c) tot += (size_t)RGg[P.group_of[c]].w * RGg[P.group_of[c]].h;
-        uint8_t* dp = comps_on_device ? nullptr : (uint8_t*)ctx->dplanes.get(tot * es + 16);
+        size_t tot = 0;   // host planes are staged back to back
+        for (uint32_t c = 0; c < P.nc; ++c) tot += (size_t)E.RGg[P.group_of[c]].w * E.RGg[P.group_of[c]].h;
+        uint8_t* dp = S.on_device ? nullptr : (uint8_t*)ctx->dplanes.get(tot * es + 16);
         size_t o = 0;
         for (uint32_t c = 0; c < P.nc; ++c) {
-            const Region& R = RGg[P.group_of[c]];
-            const uint8_t* first = (const uint8_t*)comps[c] + (size_t)R.y0 * strides[c] * es;
-            if (comps_on_device) { src[c] = first; sstr[c] = strides[c]; continue; }
-            HIPCHK(hipMemcpy2DAsync(dp + o * es, (size_t)R.w * es, first, (size_t)strides[c] * es, (size_t)R.w * es, R.h,
-                                    hipMemcpyHostToDevice, st));
-            src[c] = dp + o * es; sstr[c] = R.w;
+            const Region& R = E.RGg[P.group_of[c]];
+            const uint8_t* first = (const uint8_t*)S.comps[c] + (size_t)R.y0 * S.strides[c] * es;
+            if (S.on_device) { E.src[c] = first; E.sstr[c] = S.strides[c]; continue; }
+            E.src[c] = stage_rows(st, dp + o * es, first, (size_t)S.strides[c] * es, (size_t)R.w * es, R.h);
+            E.sstr[c] = R.w;
             o += (size_t)R.w * R.h;
         }
     }
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
+    return E;
+}
+
+// DC shift and MCT (inside the first DWT level, unless a tile starts on an odd coordinate: then
+// they run first and level 1 takes the parity-general kernels), then the forward DWT
+static void forward_transform(gk_ctx* ctx, const EncRange& R, const EncPlanes& E, int32_t* arena) {
+    const Plan& P = ctx->plan; hipStream_t st = ctx->st;
+    const Region& RG = R.RG;
     int32_t shift = P.sgnd ? 0 : (1 << (P.prec - 1));
     auto planeA = [&](uint32_t c) { return arena + (size_t)c * 2 * RG.plane; };
     auto planeAf = [&](uint32_t c) { return reinterpret_cast<float*>(planeA(c)); };
     const bool mct3 = P.mct3();
-    if (mct3 && (sstr[1] != sstr[0] || sstr[2] != sstr[0])) throw GkError("the first three components must share a stride");
+    if (mct3 && (E.sstr[1] != E.sstr[0] || E.sstr[2] != E.sstr[0])) throw GkError("the first three components must share a stride");
     L1Io io;
-    // DC shift + MCT run inside the first DWT level (unless a tile starts on an odd coordinate:
-    // then they run first and level 1 takes the parity-general kernels)
     const bool fused = P.p.numres > 1 && P.l1_fusable;
     if (fused) {
-        io.stype = stype; io.mct3 = mct3; io.shift.assign(P.nc, shift);
-        io.planes.assign(src.begin(), src.end());
-        io.strides = sstr;
+        io.stype = E.stype; io.mct3 = mct3; io.shift.assign(P.nc, shift);
+        io.planes.assign(E.src.begin(), E.src.end());
+        io.strides = E.sstr;
     } else {
         // no decomposition (or a tile on an odd origin): DC shift + MCT into plane A of each
         // component (each component's plane at its own size)
-        auto cw = [&](uint32_t c) { return RGg[P.group_of[c]].w; };
-        auto ch = [&](uint32_t c) { return RGg[P.group_of[c]].h; };
+        auto cw = [&](uint32_t c) { return E.RGg[P.group_of[c]].w; };
+        auto ch = [&](uint32_t c) { return E.RGg[P.group_of[c]].h; };
         if (!P.p.irrev) {
-            if (mct3) gk_launch_dc_rct_fwd(st, stype, src[0], src[1], src[2], sstr[0], planeA(0), planeA(1), planeA(2), RG.stride, cw(0), ch(0), shift);
-            for (uint32_t c = mct3 ? 3 : 0; c < P.nc; ++c) gk_launch_dc_fwd(st, stype, src[c], sstr[c], planeA(c), RG.stride, cw(c), ch(c), shift);
+            if (mct3) gk_launch_dc_rct_fwd(st, E.stype, E.src[0], E.src[1], E.src[2], E.sstr[0], planeA(0), planeA(1), planeA(2), RG.stride, cw(0), ch(0), shift);
+            for (uint32_t c = mct3 ? 3 : 0; c < P.nc; ++c) gk_launch_dc_fwd(st, E.stype, E.src[c], E.sstr[c], planeA(c), RG.stride, cw(c), ch(c), shift);
         } else {
-            if (mct3) gk_launch_dc_ict_fwd(st, stype, src[0], src[1], src[2], sstr[0], planeAf(0), planeAf(1), planeAf(2), RG.stride, cw(0), ch(0), shift);
-            for (uint32_t c = mct3 ? 3 : 0; c < P.nc; ++c) gk_launch_dc_fwd_f(st, stype, src[c], sstr[c], planeAf(c), RG.stride, cw(c), ch(c), shift);
+            if (mct3) gk_launch_dc_ict_fwd(st, E.stype, E.src[0], E.src[1], E.src[2], E.sstr[0], planeAf(0), planeAf(1), planeAf(2), RG.stride, cw(0), ch(0), shift);
+            for (uint32_t c = mct3 ? 3 : 0; c < P.nc; ++c) gk_launch_dc_fwd_f(st, E.stype, E.src[c], E.sstr[c], planeAf(c), RG.stride, cw(c), ch(c), shift);
         }
     }
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[2], st));
-    run_dwt(ctx, RG, true, jb, je, 0, 0xffffffffu, fused ? &io : nullptr);
+    enc_mark(ctx, 2, __LINE__);
+    run_dwt(ctx, RG, true, R.jb, R.je, 0, 0xffffffffu, fused ? &io : nullptr);
     if (const char* dp = getenv("GK_DUMP_DWT")) {   // debug: the work planes after the forward DWT
         std::vector<int32_t> hv((size_t)P.nc * 2 * RG.plane);
         HIPCHK(hipMemcpyAsync(hv.data(), arena, hv.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (FILE* f = fopen(dp, "wb")) {
             const uint32_t hd[4] = {P.nc, RG.stride, RG.h, RG.w};
-            fwrite(hd, 4, 4, f);
-            fwrite(hv.data(), 4, hv.size(), f);
-            fclose(f);
+            fwrite(hd, 4, 4, f); fwrite(hv.data(), 4, hv.size(), f); fclose(f);
         }
     }
+}
+
+// A transcode's bands carry the source's bit-plane counts: per block its band's count under the
+// source's QCD / QCC (which the plan's own table does not hold) and its symbol stream's offset
+struct XSym { std::vector<uint8_t> numbps; std::vector<uint64_t> off; };
+// This call's device arrays for T1; every per-block one is local to the range.  xcode: the work
+// planes hold a transcode's indices; roi: a shaped region's coefficient masks, indexed like the coefficients
+struct EncT1 {
+    int32_t* arena;
+    uint8_t* dbytes; GkBlock* dblk; GkPass* dps; uint32_t* dinfo; int* derr; uint32_t* dpcount;
+    uint8_t* dsym; uint64_t* dsymoff; uint32_t* dpe; uint32_t* dcm; int32_t* dnmse; uint8_t* mel;
+    const uint8_t* roi; uint64_t roi_mod;
+    bool xcode;
+};
+// T1's results on the host: 4 u32 per block of the plan (the range's filled) and the pass records
+struct T1Out { uint32_t* hinfo; const GkPass* hpasses; uint32_t npass_total; };
+
+static XSym xcode_symbol_layout(const Plan& P) {
+    const uint32_t nb = (uint32_t)P.blocks.size();
+    XSym X; X.numbps.resize(nb);
+    for (const TileG& T : P.tiles)
+        for (uint32_t c = 0; c < P.nc; ++c)
+            for (const ResG& R : T.comps[c].res)
+                for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
+                    for (const PrecG& PG : R.prc[bi])
+                        for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) X.numbps[PG.first_block + k] = (uint8_t)R.bands[bi].numbps;
+    X.off.resize((size_t)nb + 1);
+    uint64_t so = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        X.off[i] = so; so = (so + (uint64_t)(X.numbps[i] + 1) * 11264u + 255) & ~255ull;
     }
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[3], st));
-    // a shaped region: its coefficient masks, which the T1 front ends index like the coefficients
-    const bool region = !xc && P.p.region;
-    const uint8_t* roi = region ? run_roi_masks(ctx) : nullptr;
-    const uint64_t roi_mod = 2 * (uint64_t)RG.plane;
-    // T1 over the block range [b0, b1): every per-block device array is range-local
+    X.off[nb] = so;
+    return X;
+}
+
+static EncT1 enc_t1_arrays(gk_ctx* ctx, const EncRange& R, int32_t* arena, const XSym* xs) {
+    const Plan& P = ctx->plan;
+    EncT1 A{}; A.arena = arena; A.xcode = xs != nullptr;
+    A.roi = !xs && P.p.region ? run_roi_masks(ctx) : nullptr;
+    A.roi_mod = 2 * (uint64_t)R.RG.plane;
+    const uint32_t nbx = std::max(R.nbr, 1u);
+    A.dbytes = (uint8_t*)ctx->bytes.get(R.slot_span + (64u << 20));
+    A.dblk = (GkBlock*)ctx->dblocks.get(sizeof(GkBlock) * nbx);
+    A.dps = (GkPass*)ctx->dpasses.get(sizeof(GkPass) * GK_MAX_PASSES * (size_t)nbx);
+    A.dinfo = (uint32_t*)ctx->dinfo.get(16 * (size_t)nbx + 16);
+    A.derr = (int*)ctx->derr.get(64); A.dpcount = (uint32_t*)(A.derr + 4);
+    const std::vector<uint64_t>& sym_off = xs && !P.p.ht() ? xs->off : P.sym_off;
+    A.dsym = P.p.ht() ? nullptr : (uint8_t*)ctx->dsym.get(sym_off[R.b1] - sym_off[R.b0] + 256);
+    A.dsymoff = (uint64_t*)ctx->dsymoff.get(8 * ((size_t)R.nbr + 1));
+    A.dpe = (uint32_t*)ctx->dpassend.get(4 * GK_MAX_PASSES * (size_t)nbx);
+    A.dcm = (uint32_t*)ctx->dcminfo.get(8 * (size_t)nbx);
+    A.dnmse = P.p.rate_control() ? (int32_t*)ctx->dnmse.get(4 * GK_MAX_PASSES * (size_t)nbx) : nullptr;
+    return A;
+}
+
+// the range's blocks with offsets into this call's planes and slots, and their symbol offsets
+static void range_blocks(const Plan& P, const EncRange& R, const XSym* xs, GkBlock* hb, uint64_t* hso) {
     const bool do_rc = P.p.rate_control();
-    const uint64_t slot0 = P.blocks[b0].data_off;
-    const uint64_t slot1 = b1 < nb ? P.blocks[b1].data_off : P.slot_bytes;
-    const uint64_t slot_span = slot1 - slot0;    // the range's slots; host bytes are staged after them
-    uint8_t* dbytes = (uint8_t*)ctx->bytes.get(slot_span + (64u << 20));
-    const uint32_t nbx = std::max(nbr, 1u);
-    GkBlock* dblk = (GkBlock*)ctx->dblocks.get(sizeof(GkBlock) * nbx);
-    GkPass* dps = (GkPass*)ctx->dpasses.get(sizeof(GkPass) * GK_MAX_PASSES * (size_t)nbx);
-    uint32_t* dinfo = (uint32_t*)ctx->dinfo.get(16 * (size_t)nbx + 16);
-    int* derr = (int*)ctx->derr.get(64);
-    uint32_t* dpcount = (uint32_t*)(derr + 4);
-    // a transcode's bands carry the source's bit-plane counts: its symbol streams are sized by them
-    // (per block: its band's count under the source's QCD / QCC, which the plan's own table does not hold)
-    std::vector<uint8_t> xnumbps;
-    std::vector<uint64_t> xsym;
-    if (xc) {
-        xnumbps.resize(nb);
-        for (const TileG& T : P.tiles)
-            for (uint32_t c = 0; c < P.nc; ++c)
-                for (const ResG& R : T.comps[c].res)
-                    for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
-                        for (const PrecG& PG : R.prc[bi])
-                            for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) xnumbps[PG.first_block + k] = (uint8_t)R.bands[bi].numbps;
-        xsym.resize((size_t)nb + 1);
-        uint64_t so = 0;
-        for (uint32_t i = 0; i < nb; ++i) {
-            xsym[i] = so;
-            so = (so + (uint64_t)(xnumbps[i] + 1) * 11264u + 255) & ~255ull;
-        }
-        xsym[nb] = so;
+    for (uint32_t i = 0; i < R.nbr; ++i) {
+        hb[i] = P.blocks[R.b0 + i];
+        hb[i].band_off = relocate(P, group_region(P, R.RG, P.groups[P.group_of[hb[i].comp]]), hb[i].band_off);
+        hb[i].stride = R.RG.stride;
+        hb[i].data_off -= R.slot0;
+        hb[i].flags = (uint8_t)((hb[i].flags & ~2u) | (do_rc ? 2u : 0u));
+        if (xs) hb[i].band_numbps = xs->numbps[R.b0 + i];
     }
-    const std::vector<uint64_t>& sym_off = xc && !P.p.ht() ? xsym : P.sym_off;
-    uint8_t* dsym = P.p.ht() ? nullptr : (uint8_t*)ctx->dsym.get(sym_off[b1] - sym_off[b0] + 256);
-    uint64_t* dsymoff = (uint64_t*)ctx->dsymoff.get(8 * ((size_t)nbr + 1));
-    uint32_t* dpe = (uint32_t*)ctx->dpassend.get(4 * GK_MAX_PASSES * (size_t)nbx);
-    uint32_t* dcm = (uint32_t*)ctx->dcminfo.get(8 * (size_t)nbx);
-    int32_t* dnmse = do_rc ? (int32_t*)ctx->dnmse.get(4 * GK_MAX_PASSES * (size_t)nbx) : nullptr;
-    auto upload_blocks = [&]() {
-        if (!xc && ctx->blocks_uploaded && ctx->enc_b0 == b0 && ctx->enc_b1 == b1 && ctx->enc_rc == do_rc) return;
-        // the range's blocks with offsets into this call's planes and slots
-        GkBlock* hb = (GkBlock*)ctx->hpasses.get(sizeof(GkBlock) * nbx + 8 * ((size_t)nbr + 1));
-        uint64_t* hso = (uint64_t*)(hb + nbx);
-        for (uint32_t i = 0; i < nbr; ++i) {
-            hb[i] = P.blocks[b0 + i];
-            hb[i].band_off = relocate(P, group_region(P, RG, P.groups[P.group_of[hb[i].comp]]), hb[i].band_off);
-            hb[i].stride = RG.stride;
-            hb[i].data_off -= slot0;
-            hb[i].flags = (uint8_t)((hb[i].flags & ~2u) | (do_rc ? 2u : 0u));
-        }
-        if (xc) for (uint32_t i = 0; i < nbr; ++i) hb[i].band_numbps = xnumbps[b0 + i];
-        for (uint32_t i = 0; i <= nbr; ++i) hso[i] = sym_off[b0 + i] - sym_off[b0];
-        HIPCHK(hipMemcpyAsync(dblk, hb, sizeof(GkBlock) * nbr, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dsymoff, hso, 8 * ((size_t)nbr + 1), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));   // the staging buffer is reused below
-        ctx->blocks_uploaded = !xc; ctx->enc_b0 = b0; ctx->enc_b1 = b1; ctx->enc_rc = do_rc;
-    };
-    upload_blocks();
-    HIPCHK(hipMemsetAsync(derr, 0, 64, st));
-    // solo MQ waves (gk_t1enc.hip mq_solo_block): GK_T1ENC_SOLO = how many of the heaviest blocks
-    // of the first chunk they code (without chunks: the first blocks in index order; tests)
-    const uint32_t nsolo_env = []() { const char* v = getenv("GK_T1ENC_SOLO"); return v ? (uint32_t)atoi(v) : 0u; }();
-    // HT cleanup pass (T1HT::compress, T1HT.cpp:109-133); MEL bytes staged in the symbol buffer
-    uint8_t* const mel = P.p.ht() ? (uint8_t*)ctx->dsym.get((size_t)nbx * GK_HT_MEL_CAP + 256) : nullptr;
-    auto ht_pass = [&]() {
-        launch_check(__LINE__);
-        HIPCHK(hipEventRecord(ctx->ev[8], st));
-        gk_launch_ht_enc(st, arena, dblk, dbytes, mel, GK_HT_MEL_CAP, dinfo, nbr, derr, P.p.wide(), xc != nullptr, roi, roi_mod);
-        qres.t1_passes++;
-    };
-    // ---- gk_set_encode_quant's search modes: the coefficients stay in the work planes, only the
-    // step of the quantise-and-code pass moves.  Notch 0 is the default step (Params::qstep 0).
-    const uint32_t q_top = quant_notches(P.prec) - 1;
-    uint32_t q_notch = 0;
-    uint64_t q_target = 0;
-    bool q_have_pass = false;   // the pass of q_notch has run already (the search's last probe)
-    auto q_step_to = [&](uint32_t n) {
-        P.p.qstep = n ? quant_ladder(P.prec, P.sgnd != 0, n) : 0.0;
-        sync_qstep(ctx);
-        upload_blocks();
-    };
-    std::vector<double> q_mse;   // the estimated MSE of every notch (PSNR mode) or of the step in use and the next notch
-    if (quant.mode == GK_QUANT_PSNR) {
-        // one statistics pass over the whole ladder, then the coarsest notch that reaches the target
-        std::vector<double> ladder(q_top + 1);
-        for (uint32_t n = 0; n <= q_top; ++n) ladder[n] = quant_ladder(P.prec, P.sgnd != 0, n);
-        q_mse = quant_estimate(ctx, arena, dblk, tb, te, b0, b1, ladder);
-        for (q_notch = q_top; q_notch > 0 && quant_psnr(P.prec, q_mse[q_notch]) < quant.value;) --q_notch;
-        q_step_to(q_notch);
-    } else if (quant.mode == GK_QUANT_BYTES) {
-        // Bisect the ladder on the stream length.  A probe's length is the pass's bytes and a lower
-        // bound of its packet-header bits, summed on the device (k_htq_len: the host reads two
-        // numbers), plus the bytes every stream of this plan has: "overshoots" is therefore always
-        // true of the real stream, "fits" is confirmed on the exact length after T2 below.  The
-        // invariant: notch lo overshoots, notch hi fits; lo = -1 and hi = top + 1 stand for "finer
-        // than the ladder" and "refused", so the search ends on an adjacent pair after at most
-        // ceil(log2(notches + 1)) passes whether or not the length is monotone in the step.
-        q_target = quant.value >= 1.8e19 ? ~0ull : (uint64_t)quant.value;
-        std::vector<uint8_t> H0;
-        write_main_header(H0, P);
-        uint64_t fixed = H0.size() + (P.p.jp2 ? jp2_prefix_size(P, ctx->enc_jp2h) : 0) + 2 + 14ull * (te - tb);
-        if (P.p.plt)   // a PLT per tile: its 5 bytes and at least one per packet
-            for (uint32_t t = tb; t < te; ++t) {
-                fixed += 5;
-                for (uint32_t c = 0; c < P.nc; ++c)
-                    for (const ResG& R : P.tiles[t].comps[c].res) fixed += (uint64_t)R.pw * R.ph;
-            }
-        uint64_t* dpart = (uint64_t*)ctx->dq_partial.get(16 * (size_t)gk_htq_len_partials(nbr) + 16);
-        uint64_t* dlen = (uint64_t*)ctx->dq_out.get(64);
-        uint64_t* hlen = (uint64_t*)ctx->hq_out.get(64);
-        uint64_t over = 0;   // the coarsest overshooting probe's length
-        int64_t lo = -1, hi = (int64_t)q_top + 1, last = -1;
-        while (hi - lo > 1) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            q_step_to((uint32_t)mid);
-            ht_pass();
-            gk_launch_htq_len(st, dinfo, nbr, dpart, dlen);
-            HIPCHK(hipMemcpyAsync(hlen, dlen, 16, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            const uint64_t est = fixed + hlen[0] + hlen[1] / 8;
-            last = mid;
-            if (est > q_target) { lo = mid; over = est; } else hi = mid;
-        }
-        if (hi > (int64_t)q_top)
-            throw GkError("quant: max_bytes " + std::to_string(q_target) + " is below what the coarsest notch (" +
-                          std::to_string(q_top) + ") still needs, at least " + std::to_string(over) + " bytes");
-        q_notch = (uint32_t)hi;
-        q_have_pass = last == hi;
-        if (!q_have_pass) q_step_to(q_notch);
+    const std::vector<uint64_t>& sym_off = xs && !P.p.ht() ? xs->off : P.sym_off;
+    for (uint32_t i = 0; i <= R.nbr; ++i) hso[i] = sym_off[R.b0 + i] - sym_off[R.b0];
+}
+static void upload_blocks(gk_ctx* ctx, const EncRange& R, const EncT1& A, const XSym* xs) {
+    const bool do_rc = ctx->plan.p.rate_control();
+    if (!xs && ctx->blocks_uploaded && ctx->enc_b0 == R.b0 && ctx->enc_b1 == R.b1 && ctx->enc_rc == do_rc) return;
+    const uint32_t nbx = std::max(R.nbr, 1u);
+    GkBlock* hb = (GkBlock*)ctx->hpasses.get(sizeof(GkBlock) * nbx + 8 * ((size_t)R.nbr + 1));
+    uint64_t* hso = (uint64_t*)(hb + nbx);
+    range_blocks(ctx->plan, R, xs, hb, hso);
+    HIPCHK(hipMemcpyAsync(A.dblk, hb, sizeof(GkBlock) * R.nbr, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(A.dsymoff, hso, 8 * ((size_t)R.nbr + 1), hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));   // the staging buffer is reused below
+    ctx->blocks_uploaded = !xs; ctx->enc_b0 = R.b0; ctx->enc_b1 = R.b1; ctx->enc_rc = do_rc;
+}
+
+// HT cleanup pass (T1HT::compress, T1HT.cpp:109-133); MEL bytes staged in the symbol buffer
+static void ht_pass(gk_ctx* ctx, const EncRange& R, const EncT1& A) {
+    enc_mark(ctx, 8, __LINE__);
+    gk_launch_ht_enc(ctx->st, A.arena, A.dblk, A.dbytes, A.mel, GK_HT_MEL_CAP, A.dinfo, R.nbr, A.derr, ctx->plan.p.wide(), A.xcode,
+                     A.roi, A.roi_mod);
+    ctx->quant_res.t1_passes++;
+}
+
+// Block indices in descending order of weight: a counting sort on the weight quantised to 4096
+// buckets of the range (index order within a bucket)
+static void weight_order(const uint32_t* hw, uint32_t n, uint32_t* out) {
+    uint32_t wmax = 1; const uint32_t kB = 4096;
+    for (uint32_t i = 0; i < n; ++i) wmax = std::max(wmax, hw[i]);
+    auto key = [&](uint32_t i) { return kB - 1 - (uint32_t)(((uint64_t)hw[i] * (kB - 1)) / wmax); };
+    std::vector<uint32_t> start(kB + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) start[key(i)]++;
+    for (uint32_t k = 0, acc = 0; k <= kB; ++k) { const uint32_t c = start[k]; start[k] = acc; acc += c; }
+    for (uint32_t i = 0; i < n; ++i) out[start[key(i)]++] = i;
+}
+// Chunk ends as fractions of the blocks (a comma-separated list, up to three in (0, 1)), rounded
+// to whole MQ workgroups (4 x 64 blocks): 0, the increasing interior cuts, n
+static std::vector<double> cut_fractions(const std::string& cs) {
+    std::vector<double> fr;
+    for (size_t q = 0; q < cs.size();) {
+        size_t e = cs.find(',', q);
+        if (e == std::string::npos) e = cs.size();
+        const double f = atof(cs.substr(q, e - q).c_str());
+        if (f > 0 && f < 1 && fr.size() < 3) fr.push_back(f);
+        q = e + 1;
     }
-quant_retry:
+    return fr;
+}
+static std::vector<uint32_t> chunk_cuts(uint32_t n, const std::vector<double>& fr) {
+    std::vector<uint32_t> cut(1, 0);
+    for (double f : fr) {
+        const uint32_t c = (uint32_t)(n * f) / 256 * 256;
+        if (c > cut.back() && c < n) cut.push_back(c);
+    }
+    cut.push_back(n);
+    return cut;
+}
+// Context modelling and MQ coding overlap.  Blocks go heaviest first (most coded bit-planes,
+// k_t1_weight) in three chunks; chunk i's MQ kernel starts on its own stream once chunk i is
+// modelled, so the longest MQ chains run while the lighter blocks are still being modelled.  An
+// MQ workgroup fills its CU's LDS, so the modelling waves never share a SIMD with an MQ chain
+// (sharing one slowed the chains more than the overlap gained).  Each block is coded exactly as
+// in one pass; only the launch order changes.
+static void t1_chunked(gk_ctx* ctx, const EncRange& R, const EncT1& A, uint32_t nsolo) {
+    hipStream_t st = ctx->st; const uint32_t nbr = R.nbr;
+    const bool do_rc = ctx->plan.p.rate_control();
+    uint32_t* dw = (uint32_t*)ctx->dweight.get(4 * (size_t)nbr);
+    gk_launch_t1_weight(st, A.arena, A.dblk, dw, nbr, A.roi, A.roi_mod);
+    uint32_t* hw = (uint32_t*)ctx->hweight.get(4 * (size_t)nbr);
+    HIPCHK(hipMemcpyAsync(hw, dw, 4 * (size_t)nbr, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    uint32_t* ho = (uint32_t*)ctx->hord_enc.get(4 * (size_t)nbr);
+    weight_order(hw, nbr, ho);
+    uint32_t* dord = (uint32_t*)ctx->dord_enc.get(4 * (size_t)nbr);
+    HIPCHK(hipMemcpyAsync(dord, ho, 4 * (size_t)nbr, hipMemcpyHostToDevice, st));
+    // GK_T1ENC_CUTS; the last chunk's MQ runs on the main stream.  Defaults measured per workload
+    // (bench enc_t1): without rate control 0.125, 0.375 (C2 9.18 ms; 0.08, 0.25: 9.3), with it,
+    // where the modelling also sums distortions, 0.08, 0.25 (C3 14.96-15.22 ms against 15.6-15.8)
+    static std::vector<double> frs[2];
+    std::vector<double>& fr = frs[do_rc ? 1 : 0];
+    if (fr.empty()) {
+        const char* cv = getenv("GK_T1ENC_CUTS");
+        fr = cut_fractions(cv ? cv : (do_rc ? "0.08,0.25" : "0.125,0.375"));
+    }
+    const std::vector<uint32_t> cut = chunk_cuts(nbr, fr);
+    const int nch = (int)cut.size() - 1;
+    for (int k = 0; k < nch; ++k) {
+        const uint32_t base = cut[k], cnt = cut[k + 1] - cut[k];
+        gk_launch_t1_cm(st, A.arena, A.dblk, A.dsymoff, A.dsym, A.dpe, A.dcm, nbr, A.derr, ctx->nmse_tab, A.dnmse, dord, base, cnt,
+                        A.xcode, A.roi, A.roi_mod);
+        if (k + 1 < nch) {
+            HIPCHK(hipEventRecord(ctx->xev[k], st));
+            HIPCHK(hipStreamWaitEvent(ctx->aux[k], ctx->xev[k], 0));
+            gk_launch_t1_mq(ctx->aux[k], A.dsym, A.dsymoff, A.dpe, A.dcm, A.dblk, A.dbytes, A.dps, A.dinfo, nbr, A.derr, A.dnmse,
+                            A.dpcount, dord, base, cnt, k == 0 ? std::min(nsolo, cnt) : 0u);
+            HIPCHK(hipEventRecord(ctx->xev[3 + k], ctx->aux[k]));
+        } else {
+            enc_mark(ctx, 8, __LINE__);
+            gk_launch_t1_mq(st, A.dsym, A.dsymoff, A.dpe, A.dcm, A.dblk, A.dbytes, A.dps, A.dinfo, nbr, A.derr, A.dnmse, A.dpcount,
+                            dord, base, cnt);
+        }
+    }
+    for (int k = 0; k + 1 < nch; ++k) HIPCHK(hipStreamWaitEvent(st, ctx->xev[3 + k], 0));
+}
+// T1 over the range: ev[8] marks the start of the coder in every arm.  nsolo (GK_T1ENC_SOLO): how
+// many of the heaviest blocks of the first chunk the solo MQ waves code (gk_t1enc.hip
+// mq_solo_block; without chunks: the first blocks in index order; tests)
+static void t1_encode(gk_ctx* ctx, const EncRange& R, const EncT1& A, uint32_t nsolo) {
+    const Plan& P = ctx->plan; hipStream_t st = ctx->st;
+    const uint32_t nbr = R.nbr;
     if (P.p.ht()) {
-        if (!q_have_pass) ht_pass();
-        if (quant.mode == GK_QUANT_STEP || quant.mode == GK_QUANT_BYTES) {
-            // the estimates of the step in use and of the next coarser notch, for the result: queued
-            // behind the pass, so their read-back is the wait for the pass the T2 fetch below needs anyway
-            const bool sg = P.sgnd != 0;
-            const double step = P.p.qstep > 0.0 ? P.p.qstep : quant_ladder(P.prec, sg, 0);
-            if (quant.mode == GK_QUANT_STEP) q_notch = quant_notch_of(P.prec, sg, step);
-            std::vector<double> two(1, step);
-            if (q_notch < q_top) two.push_back(quant_ladder(P.prec, sg, q_notch + 1));
-            q_mse = quant_estimate(ctx, arena, dblk, tb, te, b0, b1, two);
-        }
+        ht_pass(ctx, R, A);
     } else if (P.p.t1_generic()) {
         // mode switches: lane-per-block coder with per-pass termination rules (gk_t1ms.hip)
-        uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(nbx));
-        launch_check(__LINE__);
-        HIPCHK(hipEventRecord(ctx->ev[8], st));
-        gk_launch_t1_enc_ms(st, arena, dblk, dbytes, dps, dinfo, nbr, derr, ctx->nmse_tab, dpcount, mst, P.p.cblk_sty & 0x3f,
-                            xc != nullptr, roi, roi_mod);
+        uint8_t* mst = (uint8_t*)ctx->dmsstate.get(gk_t1ms_state_bytes(std::max(nbr, 1u)));
+        enc_mark(ctx, 8, __LINE__);
+        gk_launch_t1_enc_ms(st, A.arena, A.dblk, A.dbytes, A.dps, A.dinfo, nbr, A.derr, ctx->nmse_tab, A.dpcount, mst,
+                            P.p.cblk_sty & 0x3f, A.xcode, A.roi, A.roi_mod);
     } else if (nbr < 8192 || getenv("GK_T1ENC_SERIAL")) {
-        gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse, nullptr, 0, 0xffffffffu,
-                        xc != nullptr, roi, roi_mod);
-        launch_check(__LINE__);
-        HIPCHK(hipEventRecord(ctx->ev[8], st));
-        gk_launch_t1_mq(st, dsym, dsymoff, dpe, dcm, dblk, dbytes, dps, dinfo, nbr, derr, dnmse, dpcount, nullptr, 0,
-                        0xffffffffu, std::min(nsolo_env, nbr));
+        gk_launch_t1_cm(st, A.arena, A.dblk, A.dsymoff, A.dsym, A.dpe, A.dcm, nbr, A.derr, ctx->nmse_tab, A.dnmse, nullptr, 0,
+                        0xffffffffu, A.xcode, A.roi, A.roi_mod);
+        enc_mark(ctx, 8, __LINE__);
+        gk_launch_t1_mq(st, A.dsym, A.dsymoff, A.dpe, A.dcm, A.dblk, A.dbytes, A.dps, A.dinfo, nbr, A.derr, A.dnmse, A.dpcount,
+                        nullptr, 0, 0xffffffffu, std::min(nsolo, nbr));
     } else {
-        // Context modelling and MQ coding overlap.  Blocks go heaviest first (most coded
-        // bit-planes, k_t1_weight) in three chunks; chunk i's MQ kernel starts on its own stream
-        // once chunk i is modelled, so the longest MQ chains run while the lighter blocks are
-        // still being modelled.  An MQ workgroup fills its CU's LDS, so the modelling waves never
-        // share a SIMD with an MQ chain (sharing one slowed the chains more than the overlap
-        // gained).  Each block is coded exactly as in one pass; only the launch order changes.
-        uint32_t* dw = (uint32_t*)ctx->dweight.get(4 * (size_t)nbr);
-        gk_launch_t1_weight(st, arena, dblk, dw, nbr, roi, roi_mod);
-        uint32_t* hw = (uint32_t*)ctx->hweight.get(4 * (size_t)nbr);
-        HIPCHK(hipMemcpyAsync(hw, dw, 4 * (size_t)nbr, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        // counting sort, descending, on the estimate quantised to 4096 buckets of the range
-        uint32_t wmax = 1;
-        for (uint32_t i = 0; i < nbr; ++i) wmax = std::max(wmax, hw[i]);
-        const uint32_t kB = 4096;
-        auto key = [&](uint32_t i) { return kB - 1 - (uint32_t)(((uint64_t)hw[i] * (kB - 1)) / wmax); };
-        std::vector<uint32_t> start(kB + 1, 0);
-        for (uint32_t i = 0; i < nbr; ++i) start[key(i)]++;
-        for (uint32_t k = 0, acc = 0; k <= kB; ++k) { const uint32_t c = start[k]; start[k] = acc; acc += c; }
-        uint32_t* ho = (uint32_t*)ctx->hord_enc.get(4 * (size_t)nbr);
-        for (uint32_t i = 0; i < nbr; ++i) ho[start[key(i)]++] = i;
-        uint32_t* dord = (uint32_t*)ctx->dord_enc.get(4 * (size_t)nbr);
-        HIPCHK(hipMemcpyAsync(dord, ho, 4 * (size_t)nbr, hipMemcpyHostToDevice, st));
-        // chunk ends as fractions of the blocks (GK_T1ENC_CUTS, up to three), rounded to whole MQ
-        // workgroups (4 x 64 blocks); the last chunk's MQ runs on the main stream.  Defaults
-        // measured per workload (bench enc_t1): without rate control 0.125, 0.375 (C2 9.18 ms;
-        // 0.08, 0.25: 9.3), with it, where the modelling also sums distortions, 0.08, 0.25 (C3
-        // 14.96-15.22 ms against 15.6-15.8)
-        static std::vector<double> frs[2];
-        std::vector<double>& fr = frs[do_rc ? 1 : 0];
-        if (fr.empty()) {
-            const char* cv = getenv("GK_T1ENC_CUTS");
-            std::string cs = cv ? cv : (do_rc ? "0.08,0.25" : "0.125,0.375");
-            for (size_t q = 0; q < cs.size();) {
-                size_t e = cs.find(',', q);
-                if (e == std::string::npos) e = cs.size();
-                const double f = atof(cs.substr(q, e - q).c_str());
-                if (f > 0 && f < 1 && fr.size() < 3) fr.push_back(f);
-                q = e + 1;
-            }
-        }
-        std::vector<uint32_t> cut(1, 0);
-        for (double f : fr) {
-            const uint32_t c = (uint32_t)(nbr * f) / 256 * 256;
-            if (c > cut.back() && c < nbr) cut.push_back(c);
-        }
-        cut.push_back(nbr);
-        const int nch = (int)cut.size() - 1;
-        for (int k = 0; k < nch; ++k) {
-            const uint32_t base = cut[k], cnt = cut[k + 1] - cut[k];
-            gk_launch_t1_cm(st, arena, dblk, dsymoff, dsym, dpe, dcm, nbr, derr, ctx->nmse_tab, dnmse, dord, base, cnt,
-                            xc != nullptr, roi, roi_mod);
-            if (k + 1 < nch) {
-                HIPCHK(hipEventRecord(ctx->xev[k], st));
-                HIPCHK(hipStreamWaitEvent(ctx->aux[k], ctx->xev[k], 0));
-                gk_launch_t1_mq(ctx->aux[k], dsym, dsymoff, dpe, dcm, dblk, dbytes, dps, dinfo, nbr, derr, dnmse, dpcount,
-                                dord, base, cnt, k == 0 ? std::min(nsolo_env, cnt) : 0u);
-                HIPCHK(hipEventRecord(ctx->xev[3 + k], ctx->aux[k]));
-            } else {
-                launch_check(__LINE__);
-                HIPCHK(hipEventRecord(ctx->ev[8], st));
-                gk_launch_t1_mq(st, dsym, dsymoff, dpe, dcm, dblk, dbytes, dps, dinfo, nbr, derr, dnmse, dpcount, dord,
-                                base, cnt);
-            }
-        }
-        for (int k = 0; k + 1 < nch; ++k) HIPCHK(hipStreamWaitEvent(st, ctx->xev[3 + k], 0));
+        t1_chunked(ctx, R, A, nsolo);
     }
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[4], st));
-    // GK_PROFILE=1: host phase times of the encode's T2 (stderr)
-    static const bool eprof = getenv("GK_PROFILE") != nullptr;
-    using eclk = std::chrono::steady_clock;
-    auto ems = [](eclk::time_point a, eclk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto te0 = eclk::now();
-    uint32_t* hinfo = (uint32_t*)ctx->hinfo.get(16 * (size_t)nb + 64);
-    HIPCHK(hipMemcpyAsync(hinfo + 4 * (size_t)b0, dinfo, 16 * (size_t)nbr, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hinfo + 4 * (size_t)nb, derr, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint32_t t1err = hinfo[4 * (size_t)nb], npass_total = hinfo[4 * (size_t)nb + 4];
-    if (t1err) throw GkError(t1err & 2 ? "T1 symbol buffer overflow" : "T1 code-block slot overflow");
-    const bool ht = P.p.ht();
-    const GkPass* hpasses = nullptr;
-    // pass records: rate control, and BYPASS / TERMALL (a length per codeword segment)
-    if ((do_rc || (P.p.cblk_sty & (GK_STY_LAZY | GK_STY_TERMALL))) && !ht) {
-        GkPass* hp = (GkPass*)ctx->hpasses.get(sizeof(GkPass) * (size_t)std::max(npass_total, 1u));
-        HIPCHK(hipMemcpyAsync(hp, dps, sizeof(GkPass) * (size_t)npass_total, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        hpasses = hp;
-    }
-    if (blocks_only) {   // gk_encode_blocks: T1 results only (the host of a T1 plugin runs T2)
-        dump_blocks(ctx, hinfo, dps, npass_total, dbytes, slot0);
-        *rc = 0;
-        return 0;
-    }
+}
 
-    // ---- host T2 (T2Compress.cpp:113-240) with layer formation / rate allocation
-    std::vector<uint8_t> H;
-    H.reserve(1 << 12);
-    size_t tlm_pos = 0;
-    if (xc) write_xcode_header(H, P, *xc, &tlm_pos);
-    else write_main_header(H, P, &tlm_pos);
-    // updateRates' header bytes: the stream position after the main header (JP2 boxes and the
-    // jp2c box header come first in a .jp2), CodeStreamCompress.cpp:963
-    const size_t rc_header_size = H.size() + (P.p.jp2 ? jp2_prefix_size(P, ctx->enc_jp2h) : 0);
-    if (!with_header) H.clear();
-    const auto te1 = eclk::now();
-    if (const char* ds = getenv("GK_DUMP_SYMS"); ds && dsym && !P.p.t1_generic()) {
-        // debug: per-block MQ symbol counts (decisions) and coded bit-planes, u32 pairs
+// T1's results: the per-block info, the two overflow errors, and the pass records where T2 needs
+// them (rate control, and BYPASS / TERMALL: a length per codeword segment)
+static T1Out fetch_t1(gk_ctx* ctx, const EncRange& R, const EncT1& A) {
+    const Plan& P = ctx->plan; hipStream_t st = ctx->st;
+    const uint32_t nb = (uint32_t)P.blocks.size();
+    T1Out F{}; F.hinfo = (uint32_t*)ctx->hinfo.get(16 * (size_t)nb + 64);
+    HIPCHK(hipMemcpyAsync(F.hinfo + 4 * (size_t)R.b0, A.dinfo, 16 * (size_t)R.nbr, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(F.hinfo + 4 * (size_t)nb, A.derr, 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint32_t t1err = F.hinfo[4 * (size_t)nb]; F.npass_total = F.hinfo[4 * (size_t)nb + 4];
+    if (t1err) throw GkError(t1err & 2 ? "T1 symbol buffer overflow" : "T1 code-block slot overflow");
+    if ((P.p.rate_control() || (P.p.cblk_sty & (GK_STY_LAZY | GK_STY_TERMALL))) && !P.p.ht()) {
+        GkPass* hp = (GkPass*)ctx->hpasses.get(sizeof(GkPass) * (size_t)std::max(F.npass_total, 1u));
+        HIPCHK(hipMemcpyAsync(hp, A.dps, sizeof(GkPass) * (size_t)F.npass_total, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st)); F.hpasses = hp;
+    }
+    return F;
+}
+// debug: GK_DUMP_SYMS (per-block MQ symbol counts (decisions) and coded bit-planes, u32 pairs) and
+// GK_DUMP_PASSES (pass records for tools/pcrd_bench)
+static void dump_t1_debug(const Plan& P, const EncRange& R, const EncT1& A, const T1Out& F) {
+    const uint32_t nbr = R.nbr, nb = (uint32_t)P.blocks.size();
+    if (const char* ds = getenv("GK_DUMP_SYMS"); ds && A.dsym && !P.p.t1_generic()) {
         std::vector<uint32_t> pe((size_t)GK_MAX_PASSES * nbr), cm(2 * (size_t)nbr), out(2 * (size_t)nbr);
-        HIPCHK(hipMemcpy(pe.data(), dpe, 4 * pe.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(cm.data(), dcm, 4 * cm.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pe.data(), A.dpe, 4 * pe.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cm.data(), A.dcm, 4 * cm.size(), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < nbr; ++i) {
             out[2 * i] = cm[2 * i + 1] ? pe[(size_t)GK_MAX_PASSES * i + cm[2 * i + 1] - 1] : 0;
             out[2 * i + 1] = cm[2 * i];
         }
         if (FILE* f = fopen(ds, "wb")) { fwrite(out.data(), 4, out.size(), f); fclose(f); }
     }
-    if (const char* dp = getenv("GK_DUMP_PASSES")) {   // debug: pass records for tools/pcrd_bench
+    if (const char* dp = getenv("GK_DUMP_PASSES")) {
         if (FILE* f = fopen(dp, "wb")) {
-            const uint32_t hdr[2] = {nb, npass_total};
-            fwrite(hdr, 4, 2, f);
-            fwrite(hinfo, 16, nb, f);
-            if (hpasses) fwrite(hpasses, sizeof(GkPass), npass_total, f);
+            const uint32_t hdr[2] = {nb, F.npass_total};
+            fwrite(hdr, 4, 2, f); fwrite(F.hinfo, 16, nb, f);
+            if (F.hpasses) fwrite(F.hpasses, sizeof(GkPass), F.npass_total, f);
             fclose(f);
         }
     }
-    T2Enc T2(P, hinfo, hpasses, tb, te);
-    std::vector<T2Enc::Swallow> tsw(te - tb);   // per tile: the final simulation's swallowed failure
-    if (te - tb == 1 || !P.p.rate_control()) {
-        T2.allocate(rc_header_size);
-        tsw[0] = T2.final_sw;
-    } else {
-        // rate control per tile (TileProcessor::pcrdBisectSimple runs per tile): many tiles run
-        // side by side on one thread each, a few run one after the other on the whole pool
-        const bool par = te - tb >= host_pool().size();
-        auto one = [&](size_t q) {
-            const uint32_t t = tb + (uint32_t)q;
-            T2Enc Tt(P, hinfo, hpasses, t, t + 1);
-            Tt.serial = par;
-            Tt.allocate(rc_header_size);
-            tsw[q] = Tt.final_sw;
-            const TileG& TG = P.tiles[t];
-            std::copy(Tt.lnp.begin() + (size_t)TG.b0 * T2.L, Tt.lnp.begin() + (size_t)TG.b1 * T2.L,
-                      T2.lnp.begin() + (size_t)TG.b0 * T2.L);
-        };
-        if (par) host_pool().run(te - tb, one);
-        else for (uint32_t q = 0; q < te - tb; ++q) one(q);
+}
+
+// ---- gk_set_encode_quant's search modes: the coefficients stay in the work planes, only the
+// step of the quantise-and-code pass moves.  Notch 0 is the default step (Params::qstep 0).
+struct QuantPick {
+    uint32_t notch = 0; uint64_t target = 0;
+    bool have_pass = false;    // the pass of notch has run already (the search's last probe)
+    std::vector<double> mse;   // the estimated MSE of every notch (PSNR mode) or of the step in use and the next notch
+};
+struct NotchSearch { int64_t lo, hi, last; uint64_t over; };   // over: the coarsest overshooting probe's length
+static void quant_step_to(gk_ctx* ctx, const EncRange& R, const EncT1& A, uint32_t n) {
+    Plan& P = ctx->plan; P.p.qstep = n ? quant_ladder(P.prec, P.sgnd != 0, n) : 0.0;
+    sync_qstep(ctx);
+    upload_blocks(ctx, R, A, nullptr);
+}
+// one statistics pass over the whole ladder, then the coarsest notch that reaches the target
+static QuantPick quant_pick_psnr(gk_ctx* ctx, const EncRange& R, const EncT1& A, double psnr) {
+    const Plan& P = ctx->plan;
+    const uint32_t top = quant_notches(P.prec) - 1;
+    QuantPick q; std::vector<double> ladder(top + 1);
+    for (uint32_t n = 0; n <= top; ++n) ladder[n] = quant_ladder(P.prec, P.sgnd != 0, n);
+    q.mse = quant_estimate(ctx, A.arena, A.dblk, R.tb, R.te, R.b0, R.b1, ladder);
+    for (q.notch = top; q.notch > 0 && quant_psnr(P.prec, q.mse[q.notch]) < psnr;) --q.notch;
+    quant_step_to(ctx, R, A, q.notch);
+    return q;
+}
+// The invariant: notch lo overshoots, notch hi fits; lo = -1 and hi = top + 1 stand for "finer
+// than the ladder" and "refused", so the search ends on an adjacent pair after at most
+// ceil(log2(notches + 1)) probes whether or not the length is monotone in the step.
+// probe(notch): the estimated length at that notch.
+template <class Probe> static NotchSearch bisect_notch(uint32_t top, uint64_t target, Probe&& probe) {
+    NotchSearch s{-1, (int64_t)top + 1, -1, 0};
+    while (s.hi - s.lo > 1) {
+        const int64_t mid = s.lo + (s.hi - s.lo) / 2;
+        const uint64_t est = probe((uint32_t)mid); s.last = mid;
+        if (est > target) { s.lo = mid; s.over = est; } else s.hi = mid;
     }
-    const auto te2 = eclk::now();
-    // segments: (src_off in dbytes, dst_off in codestream, len); host bytes staged after the slots
-    std::vector<uint64_t> seg;
-    seg.reserve(3 * ((size_t)nb * (ht ? 2 : 1) + 64));
-    std::vector<uint8_t> hdrs;   // all host bytes, in order, copied to staging
-    uint64_t pos = 0;            // codestream position
-    auto add_host = [&](const uint8_t* p, size_t n) {
-        if (!n) return;
-        seg.push_back(slot_span + hdrs.size()); seg.push_back(pos); seg.push_back(n);
-        hdrs.insert(hdrs.end(), p, p + n);
-        pos += n;
-    };
-    // JP2 boxes before the codestream; the jp2c length is written once the size is known
-    std::vector<uint8_t> J;
-    const bool jp2 = P.p.jp2 && with_header;
-    if (jp2) write_jp2_prefix(J, P, 0, ctx->enc_jp2h);
-    if (xc && xc->jp2) J = xc->prefix;   // a JP2 source: its boxes as they are, up to the jp2c header
-    add_host(J.data(), J.size());
-    const size_t main_at = J.size();   // the main header's position in hdrs
-    add_host(H.data(), H.size());
-    // per tile: packets (T2Compress::compressPackets) and the tile-part header; tiles are
-    // independent, so they are built in parallel host threads and appended in tile order
-    struct Pk { uint32_t hoff, hlen, s0, s1, len; };
-    struct TileOut {
-        std::vector<uint8_t> tp;     // SOT [PLT] SOD (every tile part's, concatenated)
-        std::vector<uint8_t> phdr;   // packet headers
-        std::vector<Pk> pk;
-        std::vector<uint32_t> bsegs; // (block, first byte, length) of every packet body
-        uint64_t psot = 0;
-        std::vector<uint32_t> pkey;  // tile part of each packet
-        std::vector<uint32_t> tp_off, pk_first;   // per tile part: header offset in tp, first packet
-        std::vector<uint64_t> psots;
-    };
-    const TilePartSplit TPS = tile_part_split(P);
-    if (part_lens && TPS.n > 1) throw GkError("tile-part generation is not supported with tile sharding");
-    std::vector<TileOut> tout(te - tb);
-    const bool par_chains = te - tb == 1;   // one tile: its precinct chains run in parallel instead
-    auto build_tile_part = [&](uint32_t t, TileOut& O) {
-        const TileG& T = P.tiles[t];
-        const T2Enc::Swallow& sw = tsw[t - tb];
-        // A (resolution, component, precinct) chain owns its code-blocks and tag trees, so chains
-        // are independent; within a chain the layers are sequential (T2 state carries over).
-        struct Chain { uint32_t r, c, pi; };
-        std::vector<Chain> chains;
-        for (uint32_t r = 0; r < P.p.numres; ++r)
+    return s;
+}
+// needs: "at least N" (a probe's estimate) or "N" (an exact length)
+static GkError quant_too_small(uint64_t target, uint32_t top, const std::string& needs) {
+    return GkError("quant: max_bytes " + std::to_string(target) + " is below what the coarsest notch (" + std::to_string(top) +
+                   ") still needs, " + needs + " bytes");
+}
+// Bisect the ladder on the stream length.  A probe's length is the pass's bytes and a lower
+// bound of its packet-header bits, summed on the device (k_htq_len: the host reads two
+// numbers), plus the bytes every stream of this plan has: "overshoots" is therefore always
+// true of the real stream, "fits" is confirmed on the exact length after T2.
+static QuantPick quant_pick_bytes(gk_ctx* ctx, const EncRange& R, const EncT1& A, double max_bytes) {
+    const Plan& P = ctx->plan; hipStream_t st = ctx->st;
+    const uint32_t top = quant_notches(P.prec) - 1;
+    QuantPick q; q.target = max_bytes >= 1.8e19 ? ~0ull : (uint64_t)max_bytes;
+    std::vector<uint8_t> H0;
+    write_main_header(H0, P);
+    uint64_t fixed = H0.size() + (P.p.jp2 ? jp2_prefix_size(P, ctx->enc_jp2h) : 0) + 2 + 14ull * (R.te - R.tb);
+    if (P.p.plt)   // a PLT per tile: its 5 bytes and at least one per packet
+        for (uint32_t t = R.tb; t < R.te; ++t) {
+            fixed += 5;
             for (uint32_t c = 0; c < P.nc; ++c)
-                for (uint32_t pi = 0; pi < T.comps[c].res[r].pw * T.comps[c].res[r].ph; ++pi) chains.push_back({r, c, pi});
-        const uint32_t L = P.p.nlayers;
-        std::vector<TileOut> co(chains.size());   // per chain: headers, body segments, one Pk per layer
-        auto run_chain = [&](size_t q) {
-            const Chain& ch = chains[q];
-            const ResG& R = T.comps[ch.c].res[ch.r];
-            TileOut& C = co[q];
-            std::vector<uint32_t> body;
-            std::vector<uint8_t> hb;
-            for (uint32_t l = 0; l < L; ++l) {
-                body.clear();
-                T2.write_packet(R, ch.pi, l, nullptr, &body, hb);
-                Pk k{(uint32_t)C.phdr.size(), (uint32_t)hb.size(), (uint32_t)C.bsegs.size(), 0, (uint32_t)hb.size()};
-                C.phdr.insert(C.phdr.end(), hb.begin(), hb.end());
-                for (size_t i = 0; i < body.size(); i += 3) {
-                    if (!body[i + 2]) continue;
-                    C.bsegs.push_back(body[i]); C.bsegs.push_back(body[i + 1]); C.bsegs.push_back(body[i + 2]);
-                    k.len += body[i + 2];
-                }
-                k.s1 = (uint32_t)C.bsegs.size();
-                C.pk.push_back(k);
-            }
-        };
-        if (par_chains && chains.size() > 1) {
-            // One tile: (chain, band) units in parallel - a band's tag trees and code-blocks are
-            // its own, so each codes its part of every layer's header as raw bits and its body
-            // segments; per (chain, layer) the header is then the bit 1, the bands' bits in band
-            // order and a flush through the stuffing writer (the same bit sequence write_packet
-            // writes), the body the bands' segments in band order.  The top resolution's three
-            // bands (C2: 4,096 blocks each) no longer run as one chain.
-            struct BandU { uint32_t q, bi; };
-            std::vector<BandU> bu;
-            std::vector<uint32_t> bu0(chains.size() + 1, 0);
-            for (size_t q = 0; q < chains.size(); ++q) {
-                const ResG& R = T.comps[chains[q].c].res[chains[q].r];
-                for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
-                    if (R.prc[bi][chains[q].pi].cw && R.prc[bi][chains[q].pi].ch) bu.push_back({(uint32_t)q, bi});
-                bu0[q + 1] = (uint32_t)bu.size();
-            }
-            std::vector<std::vector<RawBits>> ubit(bu.size(), std::vector<RawBits>(L));
-            std::vector<std::vector<uint32_t>> useg(bu.size());     // (block, first byte, length)
-            std::vector<std::vector<uint32_t>> uend(bu.size(), std::vector<uint32_t>(L));   // useg end per layer
-            std::vector<size_t> bord(bu.size());
-            for (size_t i = 0; i < bord.size(); ++i) bord[i] = bord.size() - 1 - i;   // largest first
-            host_pool().run(bord.size(), [&](size_t j) {
-                const size_t u = bord[j];
-                const Chain& ch = chains[bu[u].q];
-                const ResG& R = T.comps[ch.c].res[ch.r];
-                const PrecG& PG = R.prc[bu[u].bi][ch.pi];
-                T2.band_init(PG, R.bands[bu[u].bi].numbps);
-                std::vector<uint32_t>& sg = useg[u];
-                for (uint32_t l = 0; l < L; ++l) {
-                    RawBits& rb = ubit[u][l];
-                    T2.band_header(PG, l, rb);
-                    rb.finish();
-                    for (uint32_t k = 0; k < PG.cw * PG.ch; ++k) {
-                        const uint32_t b = PG.first_block + k;
-                        const uint32_t np = T2.lnp[(size_t)b * L + l];
-                        if (!np) continue;
-                        const uint32_t r0 = T2.inprev[b] ? T2.rate(b, T2.inprev[b] - 1) : 0, r1 = T2.rate(b, T2.inprev[b] + np - 1);
-                        if (r1 > r0) { sg.push_back(b); sg.push_back(r0); sg.push_back(r1 - r0); }
-                        T2.inprev[b] = (uint16_t)(T2.inprev[b] + np);
-                    }
-                    uend[u][l] = (uint32_t)sg.size();
-                }
-            });
-            host_pool().run(chains.size(), [&](size_t q) {
-                TileOut& C = co[q];
-                for (uint32_t l = 0; l < L; ++l) {
-                    const uint32_t h0 = (uint32_t)C.phdr.size();
-                    PktBitWriter bw(C.phdr);
-                    bw.putbit(1);
-                    for (uint32_t u = bu0[q]; u < bu0[q + 1]; ++u) {
-                        const RawBits& rb = ubit[u][l];
-                        const size_t full = (size_t)(rb.n / 64);
-                        const uint32_t rem = (uint32_t)(rb.n % 64);
-                        for (size_t i = 0; i < full; ++i) { bw.put((uint32_t)(rb.w[i] >> 32), 32); bw.put((uint32_t)rb.w[i], 32); }
-                        if (rem) {
-                            const uint64_t x = rb.w[full] >> (64 - rem);
-                            if (rem > 32) { bw.put((uint32_t)(x >> 32), rem - 32); bw.put((uint32_t)x, 32); }
-                            else bw.put((uint32_t)x, rem);
-                        }
-                    }
-                    bw.flush();
-                    const uint32_t hlen = (uint32_t)C.phdr.size() - h0;
-                    Pk k{h0, hlen, (uint32_t)C.bsegs.size(), 0, hlen};
-                    for (uint32_t u = bu0[q]; u < bu0[q + 1]; ++u) {
-                        const uint32_t s0 = l ? uend[u][l - 1] : 0, s1 = uend[u][l];
-                        for (uint32_t i = s0; i < s1; i += 3) k.len += useg[u][i + 2];
-                        C.bsegs.insert(C.bsegs.end(), useg[u].begin() + s0, useg[u].begin() + s1);
-                    }
-                    k.s1 = (uint32_t)C.bsegs.size();
-                    C.pk.push_back(k);
-                }
-            });
-        } else {
-            for (size_t q = 0; q < chains.size(); ++q) run_chain(q);
+                for (const ResG& Rs : P.tiles[t].comps[c].res) fixed += (uint64_t)Rs.pw * Rs.ph;
         }
-        // packets in the progression order (chains are numbered in (resolution, component,
-        // precinct) order)
-        std::vector<uint32_t> chain_at(P.p.numres * P.nc + 1, 0);
-        for (uint32_t r = 0, q = 0; r < P.p.numres; ++r)
-            for (uint32_t c = 0; c < P.nc; ++c) { chain_at[r * P.nc + c] = q; q += T.comps[c].res[r].pw * T.comps[c].res[r].ph; }
-        std::vector<uint32_t> entry;
-        const std::vector<PacketRef> order = packet_order(P, T, L, &P.p.pocs, TPS.poc ? &entry : nullptr);
-        for (size_t oi = 0; oi < order.size(); ++oi) {
-                const PacketRef& pr = order[oi];
-                O.pkey.push_back(TPS.poc ? entry[2 * oi] : TPS.key(pr));
-                const size_t q = chain_at[pr.r * P.nc + pr.c] + pr.pi;
-                const uint32_t l = pr.l;
-                const TileOut& C = co[q];
-                Pk k = C.pk[l];
-                const uint32_t h0 = (uint32_t)O.phdr.size(), s0 = (uint32_t)O.bsegs.size();
-                if (P.p.sop_eph & 2) {   // SOP: FF91, Lsop 4, Nsop = the packet's index in the tile (T2Compress.cpp:286-303)
-                    const uint32_t nsop = (TPS.poc ? entry[2 * oi + 1] : (uint32_t)O.pk.size()) & 0xffff;
-                    const uint8_t sop[6] = {0xff, 0x91, 0, 4, (uint8_t)(nsop >> 8), (uint8_t)nsop};
-                    O.phdr.insert(O.phdr.end(), sop, sop + 6);
-                }
-                O.phdr.insert(O.phdr.end(), C.phdr.begin() + k.hoff, C.phdr.begin() + k.hoff + k.hlen);
-                if (P.p.sop_eph & 4) { O.phdr.push_back(0xff); O.phdr.push_back(0x92); }   // EPH (:312-319)
-                const uint32_t ovh = ((P.p.sop_eph & 2) ? 6 : 0) + ((P.p.sop_eph & 4) ? 2 : 0);
-                k.hlen += ovh; k.len += ovh;
-                O.bsegs.insert(O.bsegs.end(), C.bsegs.begin() + k.s0, C.bsegs.begin() + k.s1);
-                k.hoff = h0; k.s1 = s0 + (k.s1 - k.s0); k.s0 = s0;
-                O.pk.push_back(k);
-            }
-        // tile parts: SOT [PLT] SOD (CodeStreamCompress::writeTilePart :858-900); the PLT of every
-        // packet of the tile goes into the first part's header (TileProcessor::writeTilePartT2)
-        std::vector<uint8_t>& tp = O.tp;
-        size_t pk0 = 0;
-        for (uint32_t part = 0; part < TPS.n; ++part) {
-            size_t pk1 = pk0;
-            while (pk1 < O.pk.size() && O.pkey[pk1] == part) ++pk1;
-            const size_t h0 = tp.size();
-            O.tp_off.push_back((uint32_t)h0); O.pk_first.push_back((uint32_t)pk0);
-            put16(tp, 0xff90); put16(tp, 10); put16(tp, t); put32(tp, 0); tp.push_back((uint8_t)part);
-            tp.push_back((uint8_t)TPS.n);
-            // POC in the tile's first tile part (writeTilePart :870-875): writePoc writes tile 0's
-            // list (tcp = m_cp.tcps) as the main header's writePoc clamped it, each entry's
-            // progression being what tile 0's last PacketManager left: for tile 0 its own
-            // rate-control simulation (THRESH_CALC: tcp->prg), for later tiles tile 0's final pass
-            // (the given progressions)
-            if (part == 0 && !P.p.pocs.empty()) write_poc(tp, P.p.pocs, P.nc, &P, t == 0 ? P.p.prog : ~0u);
-            if (P.p.plt && part == 0) {   // PacketLengthMarkers::write (PacketLengthMarkers.cpp:107-175): Zplt 0, 7-bit groups MSB first
-                // the lengths come from the final simulation (compressPacketSimulate :427-428):
-                // with progression order changes they are listed in the tile's own progression,
-                // and a swallowed failure there counted its packet's header as Grok's BitIO did
-                std::vector<uint32_t> lens;
-                const uint32_t ovh = ((P.p.sop_eph & 2) ? 6 : 0) + ((P.p.sop_eph & 4) ? 2 : 0);
-                for (const PacketRef& pr : packet_order(P, T, L)) {
-                    uint32_t len = co[chain_at[pr.r * P.nc + pr.c] + pr.pi].pk[pr.l].len + ovh;
-                    if (sw.on && pr.c == sw.c && pr.r == sw.r && pr.pi == sw.pi && pr.l == sw.l)
-                        len = (uint32_t)(len + sw.hcnt - sw.hreal);
-                    lens.push_back(len);
-                }
-                std::vector<uint8_t> v;
-                for (const uint32_t len : lens) {
-                    const int nbits = floorlog2(len) + 1, nbytes = (nbits + 6) / 7;
-                    for (int q = nbytes - 1; q >= 0; --q) v.push_back((uint8_t)(((len >> (7 * q)) & 0x7F) | (q ? 0x80 : 0)));
-                }
-                if (3 + v.size() > 65535) throw GkError("PLT marker overflow (too many packets in one tile)");
-                put16(tp, 0xff58); put16(tp, (uint32_t)(3 + v.size())); tp.push_back(0);
-                tp.insert(tp.end(), v.begin(), v.end());
-            }
-            put16(tp, 0xff93);
-            uint64_t psot = tp.size() - h0;
-            for (size_t q = pk0; q < pk1; ++q) psot += O.pk[q].len;
-            // a tile in one part with one progression writes the length TileProcessor precalculated
-            // from the final simulation (canPreCalculateTileLen, TileProcessor.cpp:54-57, 243-259)
-            if (TPS.n == 1 && sw.on) psot = psot + sw.hcnt - sw.hreal;
-            if (psot > 0xffffffffull) throw GkError("tile part exceeds 4 GiB");
-            tp[h0 + 6] = (uint8_t)(psot >> 24); tp[h0 + 7] = (uint8_t)(psot >> 16); tp[h0 + 8] = (uint8_t)(psot >> 8);
-            tp[h0 + 9] = (uint8_t)psot;
-            O.psots.push_back(psot);
-            pk0 = pk1;
-        }
-        if (pk0 != O.pk.size()) throw GkError("tile-part split out of packet order");
-        O.tp_off.push_back((uint32_t)tp.size()); O.pk_first.push_back((uint32_t)pk0);
-        O.psot = O.psots[0];
+    uint64_t* dpart = (uint64_t*)ctx->dq_partial.get(16 * (size_t)gk_htq_len_partials(R.nbr) + 16);
+    uint64_t *dlen = (uint64_t*)ctx->dq_out.get(64), *hlen = (uint64_t*)ctx->hq_out.get(64);
+    const NotchSearch s = bisect_notch(top, q.target, [&](uint32_t mid) {
+        quant_step_to(ctx, R, A, mid);
+        ht_pass(ctx, R, A);
+        gk_launch_htq_len(st, A.dinfo, R.nbr, dpart, dlen);
+        HIPCHK(hipMemcpyAsync(hlen, dlen, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return fixed + hlen[0] + hlen[1] / 8;
+    });
+    if (s.hi > (int64_t)top) throw quant_too_small(q.target, top, "at least " + std::to_string(s.over));
+    q.notch = (uint32_t)s.hi; q.have_pass = s.last == s.hi;
+    if (!q.have_pass) quant_step_to(ctx, R, A, q.notch);
+    return q;
+}
+// ---- host T2 (T2Compress.cpp:113-240) with layer formation / rate allocation
+// Layers for the range: one allocation, or rate control per tile (TileProcessor::pcrdBisectSimple
+// runs per tile): many tiles run side by side on one thread each, a few run one after the other
+// on the whole pool.  Returns per tile the final simulation's swallowed failure.
+static std::vector<T2Enc::Swallow> allocate_layers(const Plan& P, T2Enc& T2, const T1Out& F, uint32_t tb, uint32_t te,
+                                                   size_t rc_header_size) {
+    std::vector<T2Enc::Swallow> tsw(te - tb);
+    if (te - tb == 1 || !P.p.rate_control()) {
+        T2.allocate(rc_header_size); tsw[0] = T2.final_sw;
+        return tsw;
+    }
+    const bool par = te - tb >= host_pool().size();
+    auto one = [&](size_t q) {
+        const uint32_t t = tb + (uint32_t)q;
+        T2Enc Tt(P, F.hinfo, F.hpasses, t, t + 1);
+        Tt.serial = par; Tt.allocate(rc_header_size); tsw[q] = Tt.final_sw;
+        const TileG& TG = P.tiles[t];
+        std::copy(Tt.lnp.begin() + (size_t)TG.b0 * T2.L, Tt.lnp.begin() + (size_t)TG.b1 * T2.L,
+                  T2.lnp.begin() + (size_t)TG.b0 * T2.L);
     };
-    if (par_chains) build_tile_part(tb, tout[0]);   // (its chains use the pool: no nested pool call)
-    else host_pool().run(te - tb, [&](size_t q) { build_tile_part(tb + (uint32_t)q, tout[q]); });
-    const auto te3 = eclk::now();
-    for (uint32_t t = tb; t < te; ++t) {
-        TileOut& O = tout[t - tb];
-        if (part_lens) part_lens[t - tb] = (uint32_t)O.psot;
-        for (uint32_t part = 0; part < TPS.n; ++part) {
-        const uint64_t psot = O.psots[part];
-        if (P.p.tlm && with_header) {   // one TLM entry per tile part, in stream order
-            uint8_t* e = hdrs.data() + main_at + tlm_pos + 6 * ((size_t)t * TPS.n + part);   // the main header is hdrs[main_at ..)
-            e[0] = (uint8_t)(t >> 8); e[1] = (uint8_t)t;
-            e[2] = (uint8_t)(psot >> 24); e[3] = (uint8_t)(psot >> 16); e[4] = (uint8_t)(psot >> 8); e[5] = (uint8_t)psot;
-        }
-        add_host(O.tp.data() + O.tp_off[part], O.tp_off[part + 1] - O.tp_off[part]);
-        const uint32_t pa = O.pk_first[part], pe = O.pk_first[part + 1];
-        if (!ht && te - tb == 1 && (size_t)O.bsegs.size() >= 3 * 8192) {
-            // one tile's many body segments (C2 / C3: 49 k per layer) in parallel per packet: a
-            // packet's triples, header bytes and stream position follow from the ones before it
-            const uint32_t np = pe - pa;
-            std::vector<size_t> sb(np + 1), hb(np + 1);
-            std::vector<uint64_t> pb(np + 1);
-            sb[0] = seg.size(); hb[0] = hdrs.size(); pb[0] = pos;
-            for (uint32_t i = 0; i < np; ++i) {
-                const Pk& k = O.pk[pa + i];
-                sb[i + 1] = sb[i] + (k.hlen ? 3 : 0) + (k.s1 - k.s0);
-                hb[i + 1] = hb[i] + k.hlen;
-                pb[i + 1] = pb[i] + k.len;
-            }
-            seg.resize(sb[np]);
-            hdrs.resize(hb[np]);
-            host_pool().run(np, [&](size_t i) {
-                const Pk& k = O.pk[pa + i];
-                uint64_t* w = seg.data() + sb[i];
-                uint64_t p = pb[i];
-                if (k.hlen) {
-                    w[0] = slot_span + hb[i]; w[1] = p; w[2] = k.hlen; w += 3;
-                    memcpy(hdrs.data() + hb[i], O.phdr.data() + k.hoff, k.hlen);
-                    p += k.hlen;
-                }
-                for (uint32_t q = k.s0; q < k.s1; q += 3) {
-                    const uint32_t b = O.bsegs[q], off = O.bsegs[q + 1], n = O.bsegs[q + 2];
-                    w[0] = P.blocks[b].data_off - slot0 + off; w[1] = p; w[2] = n; w += 3;
-                    p += n;
-                }
-            });
-            pos = pb[np];
-            continue;
-        }
-        for (uint32_t pq = pa; pq < pe; ++pq) {
-            const Pk& k = O.pk[pq];
-            add_host(O.phdr.data() + k.hoff, k.hlen);
-            for (uint32_t q = k.s0; q < k.s1; q += 3) {
-                const uint32_t b = O.bsegs[q], off = O.bsegs[q + 1], n = O.bsegs[q + 2];
-                const GkBlock& G = P.blocks[b];
-                const uint64_t so = G.data_off - slot0;   // the block's slot in this call's byte arena
-                if (ht) {   // MagSgn head at the slot start, MEL+VLC tail at the slot end
-                    const uint32_t ms = hinfo[4 * (size_t)b + 3], tl = n - ms;
-                    if (ms) { seg.push_back(so); seg.push_back(pos); seg.push_back(ms); pos += ms; }
-                    seg.push_back(so + G.data_cap - tl); seg.push_back(pos); seg.push_back(tl);
-                    pos += tl;
-                    continue;
-                }
-                seg.push_back(so + off); seg.push_back(pos); seg.push_back(n);
-                pos += n;
-            }
-        }
+    if (par) host_pool().run(te - tb, one);
+    else for (uint32_t q = 0; q < te - tb; ++q) one(q);
+    return tsw;
+}
+
+// A packet: its header bytes [hoff, + hlen) and body triples [s0, s1) in its owner's arrays, its length
+struct Pk { uint32_t hoff, hlen, s0, s1, len; };
+// A (resolution, component, precinct) chain owns its code-blocks and tag trees, so chains are
+// independent; within a chain the layers are sequential (T2 state carries over).  Its packets:
+// headers, (block, first byte, length) of every body, one Pk per layer
+struct PkChain { uint32_t r, c, pi; };
+struct ChainOut { std::vector<uint8_t> phdr; std::vector<Pk> pk; std::vector<uint32_t> bsegs; };
+// A tile's packets in stream order and its tile-part headers
+struct TileOut {
+    std::vector<uint8_t> tp;     // SOT [PLT] SOD (every tile part's, concatenated)
+    std::vector<uint8_t> phdr; std::vector<Pk> pk;   // packet headers, packets
+    std::vector<uint32_t> bsegs; // (block, first byte, length) of every packet body
+    std::vector<uint32_t> pkey;  // tile part of each packet
+    std::vector<uint32_t> tp_off, pk_first;   // per tile part: header offset in tp, first packet
+    std::vector<uint64_t> psots;
+};
+static uint32_t sop_eph_bytes(const Params& p) { return ((p.sop_eph & 2) ? 6 : 0) + ((p.sop_eph & 4) ? 2 : 0); }
+// the tile's chains in (resolution, component, precinct) order
+static std::vector<PkChain> tile_chains(const Plan& P, const TileG& T) {
+    std::vector<PkChain> chains;
+    for (uint32_t r = 0; r < P.p.numres; ++r)
+        for (uint32_t c = 0; c < P.nc; ++c)
+            for (uint32_t pi = 0; pi < T.comps[c].res[r].pw * T.comps[c].res[r].ph; ++pi) chains.push_back({r, c, pi});
+    return chains;
+}
+static std::vector<ChainOut> chain_packets_serial(T2Enc& T2, const TileG& T, const std::vector<PkChain>& chains) {
+    std::vector<ChainOut> co(chains.size());
+    std::vector<uint8_t> hb;
+    for (size_t q = 0; q < chains.size(); ++q) {
+        const ResG& R = T.comps[chains[q].c].res[chains[q].r];
+        ChainOut& C = co[q];
+        for (uint32_t l = 0; l < T2.L; ++l) {
+            const uint32_t s0 = (uint32_t)C.bsegs.size();
+            uint64_t body = 0;
+            T2.write_packet(R, chains[q].pi, l, nullptr, &C.bsegs, hb, &body);
+            C.pk.push_back({(uint32_t)C.phdr.size(), (uint32_t)hb.size(), s0, (uint32_t)C.bsegs.size(), (uint32_t)(hb.size() + body)});
+            C.phdr.insert(C.phdr.end(), hb.begin(), hb.end());
         }
     }
-    uint8_t eoc[2] = {0xff, 0xd9};
-    if (with_header) add_host(eoc, 2);
-    if (xc && xc->jp2) {   // the new jp2c length (its form kept), then the boxes behind the codestream
-        const uint64_t cs_len = pos - J.size();
-        uint8_t* h = hdrs.data() + J.size() - (xc->jp2c_xl ? 16 : 8);
-        if (xc->jp2c_xl) {
-            const uint64_t L = cs_len + 16;
-            for (int k = 0; k < 8; ++k) h[8 + k] = (uint8_t)(L >> (8 * (7 - k)));
-        } else if (!xc->jp2c_to_end) {
-            const uint64_t L = cs_len + 8;
-            if (L >= (1ull << 32)) throw GkError("transcode: the codestream no longer fits the jp2c box's 32-bit length");
-            for (int k = 0; k < 4; ++k) h[k] = (uint8_t)(L >> (8 * (3 - k)));
-        }
-        add_host(xc->suffix.data(), xc->suffix.size());
+    return co;
+}
+// One tile: (chain, band) units in parallel - a band's tag trees and code-blocks are its own, so
+// each codes its part of every layer's header as raw bits and its body segments; per (chain,
+// layer) the header is then the bit 1, the bands' bits in band order and a flush through the
+// stuffing writer (the same bit sequence write_packet writes), the body the bands' segments in
+// band order.  The top resolution's three bands (C2: 4,096 blocks each) do not run as one chain.
+static std::vector<ChainOut> chain_packets_by_band(T2Enc& T2, const TileG& T, const std::vector<PkChain>& chains) {
+    const uint32_t L = T2.L;
+    std::vector<ChainOut> co(chains.size());
+    struct BandU { uint32_t q, bi; };
+    std::vector<BandU> bu;
+    std::vector<uint32_t> bu0(chains.size() + 1, 0);
+    for (size_t q = 0; q < chains.size(); ++q) {
+        const ResG& R = T.comps[chains[q].c].res[chains[q].r];
+        for (uint32_t bi = 0; bi < R.bands.size(); ++bi)
+            if (R.prc[bi][chains[q].pi].cw && R.prc[bi][chains[q].pi].ch) bu.push_back({(uint32_t)q, bi});
+        bu0[q + 1] = (uint32_t)bu.size();
     }
-    const size_t total = pos;
-    if (quant.mode == GK_QUANT_BYTES && total > q_target) {
+    std::vector<std::vector<RawBits>> ubit(bu.size(), std::vector<RawBits>(L));
+    std::vector<std::vector<uint32_t>> useg(bu.size());     // (block, first byte, length)
+    std::vector<std::vector<uint32_t>> uend(bu.size(), std::vector<uint32_t>(L));   // useg end per layer
+    const size_t nu = bu.size();
+    host_pool().run(nu, [&](size_t j) {
+        const size_t u = nu - 1 - j;   // largest first
+        const PkChain& ch = chains[bu[u].q];
+        const ResG& R = T.comps[ch.c].res[ch.r];
+        const PrecG& PG = R.prc[bu[u].bi][ch.pi];
+        T2.band_init(PG, R.bands[bu[u].bi].numbps);
+        std::vector<uint32_t>& sg = useg[u];
+        for (uint32_t l = 0; l < L; ++l) {
+            RawBits& rb = ubit[u][l];
+            T2.band_header(PG, l, rb); rb.finish();
+            T2.band_body(PG, l, &sg);
+            uend[u][l] = (uint32_t)sg.size();
+        }
+    });
+    host_pool().run(chains.size(), [&](size_t q) {
+        ChainOut& C = co[q];
+        for (uint32_t l = 0; l < L; ++l) {
+            const uint32_t h0 = (uint32_t)C.phdr.size();
+            PktBitWriter bw(C.phdr);
+            bw.putbit(1);
+            for (uint32_t u = bu0[q]; u < bu0[q + 1]; ++u) {
+                const RawBits& rb = ubit[u][l];
+                const size_t full = (size_t)(rb.n / 64); const uint32_t rem = (uint32_t)(rb.n % 64);
+                for (size_t i = 0; i < full; ++i) { bw.put((uint32_t)(rb.w[i] >> 32), 32); bw.put((uint32_t)rb.w[i], 32); }
+                if (rem) {
+                    const uint64_t x = rb.w[full] >> (64 - rem);
+                    if (rem > 32) { bw.put((uint32_t)(x >> 32), rem - 32); bw.put((uint32_t)x, 32); }
+                    else bw.put((uint32_t)x, rem);
+                }
+            }
+            bw.flush();
+            const uint32_t hlen = (uint32_t)C.phdr.size() - h0;
+            Pk k{h0, hlen, (uint32_t)C.bsegs.size(), 0, hlen};
+            for (uint32_t u = bu0[q]; u < bu0[q + 1]; ++u) {
+                const uint32_t s0 = l ? uend[u][l - 1] : 0, s1 = uend[u][l];
+                for (uint32_t i = s0; i < s1; i += 3) k.len += useg[u][i + 2];
+                C.bsegs.insert(C.bsegs.end(), useg[u].begin() + s0, useg[u].begin() + s1);
+            }
+            k.s1 = (uint32_t)C.bsegs.size();
+            C.pk.push_back(k);
+        }
+    });
+    return co;
+}
+// The chains' packets in the progression order, with SOP / EPH, and each packet's tile part
+static void order_packets(const Plan& P, const TileG& T, const TilePartSplit& TPS, const std::vector<ChainOut>& co,
+                          const std::vector<uint32_t>& chain_at, TileOut& O) {
+    std::vector<uint32_t> entry;
+    const std::vector<PacketRef> order = packet_order(P, T, P.p.nlayers, &P.p.pocs, TPS.poc ? &entry : nullptr);
+    for (size_t oi = 0; oi < order.size(); ++oi) {
+        const PacketRef& pr = order[oi];
+        O.pkey.push_back(TPS.poc ? entry[2 * oi] : TPS.key(pr));
+        const ChainOut& C = co[chain_at[pr.r * P.nc + pr.c] + pr.pi];
+        Pk k = C.pk[pr.l];
+        const uint32_t h0 = (uint32_t)O.phdr.size(), s0 = (uint32_t)O.bsegs.size();
+        if (P.p.sop_eph & 2) {   // SOP: FF91, Lsop 4, Nsop = the packet's index in the tile (T2Compress.cpp:286-303)
+            const uint32_t nsop = (TPS.poc ? entry[2 * oi + 1] : (uint32_t)O.pk.size()) & 0xffff;
+            const uint8_t sop[6] = {0xff, 0x91, 0, 4, (uint8_t)(nsop >> 8), (uint8_t)nsop};
+            O.phdr.insert(O.phdr.end(), sop, sop + 6);
+        }
+        O.phdr.insert(O.phdr.end(), C.phdr.begin() + k.hoff, C.phdr.begin() + k.hoff + k.hlen);
+        if (P.p.sop_eph & 4) { O.phdr.push_back(0xff); O.phdr.push_back(0x92); }   // EPH (:312-319)
+        k.hlen += sop_eph_bytes(P.p); k.len += sop_eph_bytes(P.p);
+        O.bsegs.insert(O.bsegs.end(), C.bsegs.begin() + k.s0, C.bsegs.begin() + k.s1);
+        k.hoff = h0; k.s1 = s0 + (k.s1 - k.s0); k.s0 = s0;
+        O.pk.push_back(k);
+    }
+}
+// Tile parts: SOT [POC] [PLT] SOD (CodeStreamCompress::writeTilePart :858-900); the PLT of every
+// packet of the tile goes into the first part's header (TileProcessor::writeTilePartT2)
+static void tile_part_headers(const Plan& P, uint32_t t, const T2Enc::Swallow& sw, const TilePartSplit& TPS,
+                              const std::vector<ChainOut>& co, const std::vector<uint32_t>& chain_at, TileOut& O) {
+    std::vector<uint8_t>& tp = O.tp;
+    size_t pk0 = 0;
+    for (uint32_t part = 0; part < TPS.n; ++part) {
+        size_t pk1 = pk0;
+        while (pk1 < O.pk.size() && O.pkey[pk1] == part) ++pk1;
+        const size_t h0 = tp.size();
+        O.tp_off.push_back((uint32_t)h0); O.pk_first.push_back((uint32_t)pk0);
+        put16(tp, 0xff90); put16(tp, 10); put16(tp, t); put32(tp, 0); tp.push_back((uint8_t)part); tp.push_back((uint8_t)TPS.n);
+        // POC in the tile's first tile part (writeTilePart :870-875): writePoc writes tile 0's
+        // list (tcp = m_cp.tcps) as the main header's writePoc clamped it, each entry's
+        // progression being what tile 0's last PacketManager left: for tile 0 its own
+        // rate-control simulation (THRESH_CALC: tcp->prg), for later tiles tile 0's final pass
+        // (the given progressions)
+        if (part == 0 && !P.p.pocs.empty()) write_poc(tp, P.p.pocs, P.nc, &P, t == 0 ? P.p.prog : ~0u);
+        if (P.p.plt && part == 0) {   // PacketLengthMarkers::write (PacketLengthMarkers.cpp:107-175): Zplt 0, 7-bit groups MSB first
+            // the lengths come from the final simulation (compressPacketSimulate :427-428):
+            // with progression order changes they are listed in the tile's own progression,
+            // and a swallowed failure there counted its packet's header as Grok's BitIO did
+            std::vector<uint8_t> v;
+            for (const PacketRef& pr : packet_order(P, P.tiles[t], P.p.nlayers)) {
+                uint32_t len = co[chain_at[pr.r * P.nc + pr.c] + pr.pi].pk[pr.l].len + sop_eph_bytes(P.p);
+                if (sw.on && pr.c == sw.c && pr.r == sw.r && pr.pi == sw.pi && pr.l == sw.l)
+                    len = (uint32_t)(len + sw.hcnt - sw.hreal);
+                const int nbits = floorlog2(len) + 1, nbytes = (nbits + 6) / 7;
+                for (int q = nbytes - 1; q >= 0; --q) v.push_back((uint8_t)(((len >> (7 * q)) & 0x7F) | (q ? 0x80 : 0)));
+            }
+            if (3 + v.size() > 65535) throw GkError("PLT marker overflow (too many packets in one tile)");
+            put16(tp, 0xff58); put16(tp, (uint32_t)(3 + v.size())); tp.push_back(0);
+            tp.insert(tp.end(), v.begin(), v.end());
+        }
+        put16(tp, 0xff93);
+        uint64_t psot = tp.size() - h0;
+        for (size_t q = pk0; q < pk1; ++q) psot += O.pk[q].len;
+        // a tile in one part with one progression writes the length TileProcessor precalculated
+        // from the final simulation (canPreCalculateTileLen, TileProcessor.cpp:54-57, 243-259)
+        if (TPS.n == 1 && sw.on) psot = psot + sw.hcnt - sw.hreal;
+        if (psot > 0xffffffffull) throw GkError("tile part exceeds 4 GiB");
+        store_be(&tp[h0 + 6], psot, 4); O.psots.push_back(psot);
+        pk0 = pk1;
+    }
+    if (pk0 != O.pk.size()) throw GkError("tile-part split out of packet order");
+    O.tp_off.push_back((uint32_t)tp.size()); O.pk_first.push_back((uint32_t)pk0);
+}
+// One tile's packets (T2Compress::compressPackets) and tile-part headers into O.  by_band: the call
+// has one tile, whose chains use the pool (many tiles are built side by side instead)
+static void build_tile_packets(const Plan& P, T2Enc& T2, uint32_t t, const T2Enc::Swallow& sw, const TilePartSplit& TPS, bool by_band,
+                               TileOut& O) {
+    const TileG& T = P.tiles[t];
+    const std::vector<PkChain> chains = tile_chains(P, T);
+    const std::vector<ChainOut> co = by_band && chains.size() > 1 ? chain_packets_by_band(T2, T, chains) : chain_packets_serial(T2, T, chains);
+    std::vector<uint32_t> chain_at(P.p.numres * P.nc + 1, 0);   // the first chain of each (resolution, component)
+    for (uint32_t r = 0, q = 0; r < P.p.numres; ++r)
+        for (uint32_t c = 0; c < P.nc; ++c) { chain_at[r * P.nc + c] = q; q += T.comps[c].res[r].pw * T.comps[c].res[r].ph; }
+    order_packets(P, T, TPS, co, chain_at, O);
+    tile_part_headers(P, t, sw, TPS, co, chain_at, O);
+}
+
+// The stream as gather segments (source offset in the byte arena, position in the stream, length);
+// hdrs: all host bytes, in order, staged behind the range's slots; prefix: the boxes before the codestream
+struct EncLayout {
+    std::vector<uint64_t> seg; std::vector<uint8_t> hdrs;
+    uint64_t pos = 0, slot_span = 0; size_t prefix = 0;
+};
+static void add_host(EncLayout& Y, const uint8_t* p, size_t n) {
+    if (!n) return;
+    Y.seg.push_back(Y.slot_span + Y.hdrs.size()); Y.seg.push_back(Y.pos); Y.seg.push_back(n);
+    Y.hdrs.insert(Y.hdrs.end(), p, p + n); Y.pos += n;
+}
+// packets [pa, pe) of a tile: each one's header, then its bodies from their blocks' slots
+static void layout_packets(EncLayout& Y, const Plan& P, const EncRange& R, const uint32_t* hinfo, const TileOut& O, uint32_t pa,
+                           uint32_t pe) {
+    for (uint32_t pq = pa; pq < pe; ++pq) {
+        const Pk& k = O.pk[pq];
+        add_host(Y, O.phdr.data() + k.hoff, k.hlen);
+        for (uint32_t q = k.s0; q < k.s1; q += 3) {
+            const uint32_t b = O.bsegs[q], off = O.bsegs[q + 1], n = O.bsegs[q + 2];
+            const GkBlock& G = P.blocks[b];
+            const uint64_t so = G.data_off - R.slot0;   // the block's slot in this call's byte arena
+            if (P.p.ht()) {   // MagSgn head at the slot start, MEL+VLC tail at the slot end
+                const uint32_t ms = hinfo[4 * (size_t)b + 3], tl = n - ms;
+                if (ms) { Y.seg.push_back(so); Y.seg.push_back(Y.pos); Y.seg.push_back(ms); Y.pos += ms; }
+                Y.seg.push_back(so + G.data_cap - tl); Y.seg.push_back(Y.pos); Y.seg.push_back(tl); Y.pos += tl;
+                continue;
+            }
+            Y.seg.push_back(so + off); Y.seg.push_back(Y.pos); Y.seg.push_back(n); Y.pos += n;
+        }
+    }
+}
+// The same arrays filled in parallel per packet (not HT): a packet's triples, header bytes and
+// stream position follow from the ones before it (C2 / C3: 49 k body segments per layer)
+static void layout_packets_parallel(EncLayout& Y, const Plan& P, const EncRange& R, const TileOut& O, uint32_t pa, uint32_t pe) {
+    const uint32_t np = pe - pa;
+    std::vector<size_t> sb(np + 1), hb(np + 1); std::vector<uint64_t> pb(np + 1);
+    sb[0] = Y.seg.size(); hb[0] = Y.hdrs.size(); pb[0] = Y.pos;
+    for (uint32_t i = 0; i < np; ++i) {
+        const Pk& k = O.pk[pa + i];
+        sb[i + 1] = sb[i] + (k.hlen ? 3 : 0) + (k.s1 - k.s0); hb[i + 1] = hb[i] + k.hlen; pb[i + 1] = pb[i] + k.len;
+    }
+    Y.seg.resize(sb[np]); Y.hdrs.resize(hb[np]);
+    host_pool().run(np, [&](size_t i) {
+        const Pk& k = O.pk[pa + i];
+        uint64_t *w = Y.seg.data() + sb[i], p = pb[i];
+        if (k.hlen) {
+            w[0] = Y.slot_span + hb[i]; w[1] = p; w[2] = k.hlen; w += 3;
+            memcpy(Y.hdrs.data() + hb[i], O.phdr.data() + k.hoff, k.hlen);
+            p += k.hlen;
+        }
+        for (uint32_t q = k.s0; q < k.s1; q += 3) {
+            const uint32_t b = O.bsegs[q], off = O.bsegs[q + 1], n = O.bsegs[q + 2];
+            w[0] = P.blocks[b].data_off - R.slot0 + off; w[1] = p; w[2] = n; w += 3; p += n;
+        }
+    });
+    Y.pos = pb[np];
+}
+// The whole stream: the boxes before the codestream (J), the main header (H, its TLM entries
+// filled in), every tile part and EOC; for a transcode of a JP2 file the new jp2c length (its
+// form kept) and the boxes behind the codestream.  One non-HT tile with 3 x 8,192 body triples or
+// more takes the per-packet parallel arm.
+static EncLayout layout_segments(const Plan& P, const EncRange& R, const uint32_t* hinfo, const std::vector<TileOut>& tout,
+                                 uint32_t nparts, const std::vector<uint8_t>& J, const std::vector<uint8_t>& H, size_t tlm_pos,
+                                 const EncReq& req, const Xcode* xc) {
+    EncLayout Y; Y.slot_span = R.slot_span; Y.prefix = J.size();
+    Y.seg.reserve(3 * (P.blocks.size() * (P.p.ht() ? 2 : 1) + 64));
+    add_host(Y, J.data(), J.size()); add_host(Y, H.data(), H.size());   // the main header is hdrs[prefix ..)
+    for (uint32_t t = R.tb; t < R.te; ++t) {
+        const TileOut& O = tout[t - R.tb];
+        if (req.part_lens) req.part_lens[t - R.tb] = (uint32_t)O.psots[0];
+        for (uint32_t part = 0; part < nparts; ++part) {
+            if (P.p.tlm && req.with_header) {   // one TLM entry per tile part, in stream order
+                uint8_t* e = Y.hdrs.data() + Y.prefix + tlm_pos + 6 * ((size_t)t * nparts + part);
+                store_be(e, t, 2); store_be(e + 2, O.psots[part], 4);
+            }
+            add_host(Y, O.tp.data() + O.tp_off[part], O.tp_off[part + 1] - O.tp_off[part]);
+            const uint32_t pa = O.pk_first[part], pe = O.pk_first[part + 1];
+            if (!P.p.ht() && R.te - R.tb == 1 && O.bsegs.size() >= 3 * 8192) layout_packets_parallel(Y, P, R, O, pa, pe);
+            else layout_packets(Y, P, R, hinfo, O, pa, pe);
+        }
+    }
+    if (const uint8_t eoc[2] = {0xff, 0xd9}; req.with_header) add_host(Y, eoc, 2);
+    if (xc && xc->jp2) {
+        const uint64_t cs_len = Y.pos - Y.prefix;
+        uint8_t* h = Y.hdrs.data() + Y.prefix - (xc->jp2c_xl ? 16 : 8);
+        if (xc->jp2c_xl) store_be(h + 8, cs_len + 16, 8);
+        else if (!xc->jp2c_to_end) {
+            if (cs_len + 8 >= (1ull << 32)) throw GkError("transcode: the codestream no longer fits the jp2c box's 32-bit length");
+            store_be(h, cs_len + 8, 4);
+        }
+        add_host(Y, xc->suffix.data(), xc->suffix.size());
+    }
+    return Y;
+}
+// Device assembly: the host bytes behind the slots, the segments, one gather into the output
+static void assemble(gk_ctx* ctx, const EncT1& A, const EncLayout& Y, const EncReq& req) {
+    hipStream_t st = ctx->st; const size_t total = Y.pos;
+    if (Y.hdrs.size() > (64u << 20)) throw GkError("packet headers exceed staging");
+    uint8_t* hh = (uint8_t*)ctx->hhdr.get(Y.hdrs.size()); memcpy(hh, Y.hdrs.data(), Y.hdrs.size());
+    HIPCHK(hipMemcpyAsync(A.dbytes + Y.slot_span, hh, Y.hdrs.size(), hipMemcpyHostToDevice, st));
+    uint64_t* hs = (uint64_t*)ctx->hseg.get(Y.seg.size() * 8); memcpy(hs, Y.seg.data(), Y.seg.size() * 8);
+    uint64_t* ds = (uint64_t*)ctx->dseg.get(Y.seg.size() * 8);
+    HIPCHK(hipMemcpyAsync(ds, hs, Y.seg.size() * 8, hipMemcpyHostToDevice, st));
+    uint8_t* dst = req.out_on_device ? req.out : (uint8_t*)ctx->dout.get(total);
+    gk_launch_gather(st, A.dbytes, dst, ds, (uint32_t)(Y.seg.size() / 3));
+    enc_mark(ctx, 6, __LINE__);
+    if (!req.out_on_device) HIPCHK(hipMemcpyAsync(req.out, dst, total, hipMemcpyDeviceToHost, st));
+    enc_mark(ctx, 7, __LINE__);
+    HIPCHK(hipStreamSynchronize(st));
+}
+// The times and counts of an encode that ran to its output (events 0 .. 8 of the call)
+static void encode_timings(gk_ctx* ctx, const EncRange& R, const uint32_t* hinfo, size_t total, bool region) {
+    gk_timings& tm = ctx->tm;
+    tm.mct_ms = ev_ms(ctx, 1, 2); tm.dwt_ms = ev_ms(ctx, 2, 3); tm.t1_ms = ev_ms(ctx, 3, 4);
+    tm.t1_cm_ms = ev_ms(ctx, 3, 8); tm.t1_coder_ms = ev_ms(ctx, 8, 4);
+    tm.roi_ms = 0.f;
+    if (region) (void)hipEventElapsedTime(&tm.roi_ms, ctx->roi_ev[0], ctx->roi_ev[1]);
+    tm.cs_bytes = total;
+    uint64_t tbytes = 0;
+    for (uint32_t b = R.b0; b < R.b1; ++b) tbytes += hinfo[4 * (size_t)b + 2];
+    tm.t1_bytes = tbytes;
+    tm.t2_ms = ev_ms(ctx, 4, 5); tm.assemble_ms = ev_ms(ctx, 5, 7); tm.total_ms = ev_ms(ctx, 0, 7);
+    tm.t1_blocks = R.nbr;
+}
+
+static EncLen encode_impl(gk_ctx* ctx, const gk_image_info* info, const gk_cparameters* cp, const EncSrc& src, const EncReq& req) {
+    const Xcode* xc = src.xc;   // (a transcode: the call starts at T1 and writes the header the transcode keeps)
+    if (!xc) setup_plan(ctx, info, cp, src.cv, req.blocks_only ? QC_BLOCKS : req.part_lens ? QC_TILES : QC_ENCODE);
+    Plan& P = ctx->plan;
+    // gk_set_encode_quant (a transcode keeps its source's QCD): STEP is in the plan already
+    const EncQuant quant = xc ? EncQuant() : ctx->enc_quant;
+    ctx->quant_res = gk_quant_result(); ctx->quant_res.mode = quant.mode;
+    const EncRange R = enc_range(P, req.tb, req.te);
+    hipStream_t st = ctx->st;
+    enc_mark(ctx, 0, __LINE__);
+    int32_t* arena = (int32_t*)ctx->arena.get(R.RG.plane * P.nc * 2 * sizeof(int32_t));
+    if (xc) {
+        HIPCHK(hipEventRecord(ctx->ev[1], st)); HIPCHK(hipEventRecord(ctx->ev[2], st));
+    } else {
+        const EncPlanes E = stage_samples(ctx, info, src, R.RG);
+        enc_mark(ctx, 1, __LINE__);
+        forward_transform(ctx, R, E, arena);
+    }
+    enc_mark(ctx, 3, __LINE__);
+    const bool region = !xc && P.p.region;
+    const XSym xsym = xc ? xcode_symbol_layout(P) : XSym();
+    const XSym* xs = xc ? &xsym : nullptr;
+    EncT1 A = enc_t1_arrays(ctx, R, arena, xs);
+    upload_blocks(ctx, R, A, xs);
+    HIPCHK(hipMemsetAsync(A.derr, 0, 64, st));
+    const uint32_t nsolo = []() { const char* v = getenv("GK_T1ENC_SOLO"); return v ? (uint32_t)atoi(v) : 0u; }();
+    if (P.p.ht()) A.mel = (uint8_t*)ctx->dsym.get((size_t)std::max(R.nbr, 1u) * GK_HT_MEL_CAP + 256);
+    const uint32_t q_top = quant_notches(P.prec) - 1;
+    QuantPick q;
+    if (quant.mode == GK_QUANT_PSNR) q = quant_pick_psnr(ctx, R, A, quant.value);
+    else if (quant.mode == GK_QUANT_BYTES) q = quant_pick_bytes(ctx, R, A, quant.value);
+    static const bool eprof = getenv("GK_PROFILE") != nullptr;   // host phase times of the encode's T2 (stderr)
+    HostClock::time_point h[4];
+    const uint32_t tb = R.tb, te = R.te;
+    T1Out F{};
+    std::unique_ptr<T2Enc> T2;     // T2's state and the tiles' packets live to the end of the call, as the
+    std::vector<TileOut> tout;    // stream's layout does: freeing them is no part of a timed phase
+    EncLayout Y;
+    for (;;) {   // T1, T2 and the exact length; BYTES mode goes round again while that is over the target
+        if (!q.have_pass) t1_encode(ctx, R, A, nsolo);
+        if (P.p.ht() && (quant.mode == GK_QUANT_STEP || quant.mode == GK_QUANT_BYTES)) {
+            // the estimates of the step in use and of the next coarser notch, for the result: queued
+            // behind the pass, so their read-back is the wait for the pass the T2 fetch needs anyway
+            const bool sg = P.sgnd != 0;
+            const double step = P.p.qstep > 0.0 ? P.p.qstep : quant_ladder(P.prec, sg, 0);
+            if (quant.mode == GK_QUANT_STEP) q.notch = quant_notch_of(P.prec, sg, step);
+            std::vector<double> two(1, step);
+            if (q.notch < q_top) two.push_back(quant_ladder(P.prec, sg, q.notch + 1));
+            q.mse = quant_estimate(ctx, arena, A.dblk, tb, te, R.b0, R.b1, two);
+        }
+        enc_mark(ctx, 4, __LINE__);
+        h[0] = HostClock::now();
+        F = fetch_t1(ctx, R, A);
+        if (req.blocks_only) {   // gk_encode_blocks: T1 results only (the host of a T1 plugin runs T2)
+            dump_blocks(ctx, F.hinfo, A.dps, F.npass_total, A.dbytes, R.slot0); return EncLen{0, true};
+        }
+        // ---- host T2 (T2Compress.cpp:113-240) with layer formation / rate allocation
+        std::vector<uint8_t> H, J;
+        H.reserve(1 << 12);
+        size_t tlm_pos = 0;
+        if (xc) write_xcode_header(H, P, *xc, &tlm_pos);
+        else write_main_header(H, P, &tlm_pos);
+        // updateRates' header bytes: the stream position after the main header (JP2 boxes and the
+        // jp2c box header come first in a .jp2), CodeStreamCompress.cpp:963
+        const size_t rc_header_size = H.size() + (P.p.jp2 ? jp2_prefix_size(P, ctx->enc_jp2h) : 0);
+        if (!req.with_header) H.clear();
+        h[1] = HostClock::now();
+        dump_t1_debug(P, R, A, F);
+        tout.clear();
+        T2.reset(); T2.reset(new T2Enc(P, F.hinfo, F.hpasses, tb, te));   // (a round before this one: its state goes first)
+        const std::vector<T2Enc::Swallow> tsw = allocate_layers(P, *T2, F, tb, te, rc_header_size);
+        h[2] = HostClock::now();
+        // JP2 boxes before the codestream (the jp2c length is written once the size is known); a JP2
+        // source's boxes as they are, up to the jp2c header
+        if (P.p.jp2 && req.with_header) write_jp2_prefix(J, P, 0, ctx->enc_jp2h);
+        if (xc && xc->jp2) J = xc->prefix;
+        const TilePartSplit TPS = tile_part_split(P);
+        if (req.part_lens && TPS.n > 1) throw GkError("tile-part generation is not supported with tile sharding");
+        // tiles are independent: built in parallel host threads (one tile: its chains run in parallel
+        // instead, no nested pool call)
+        tout.resize(te - tb);
+        if (te - tb == 1) build_tile_packets(P, *T2, tb, tsw[0], TPS, true, tout[0]);
+        else host_pool().run(te - tb, [&](size_t k) { build_tile_packets(P, *T2, tb + (uint32_t)k, tsw[k], TPS, false, tout[k]); });
+        h[3] = HostClock::now();
+        Y = layout_segments(P, R, F.hinfo, tout, TPS.n, J, H, tlm_pos, req, xc);
+        if (quant.mode != GK_QUANT_BYTES || Y.pos <= q.target) break;
         // the exact length is over the target (the probe's header bits were a lower bound): this
         // notch overshoots too, so the next coarser one is coded and measured the same way
-        if (q_notch >= q_top)
-            throw GkError("quant: max_bytes " + std::to_string(q_target) + " is below what the coarsest notch (" +
-                          std::to_string(q_top) + ") still needs, " + std::to_string(total) + " bytes");
-        q_step_to(++q_notch);
-        q_have_pass = false;
-        goto quant_retry;
+        if (q.notch >= q_top) throw quant_too_small(q.target, q_top, std::to_string(Y.pos));
+        quant_step_to(ctx, R, A, ++q.notch);
+        q.have_pass = false;
     }
+    const size_t total = Y.pos;
     if (quant.mode) {
         // the result: the step used and the estimates for it and for the next coarser notch (PSNR
         // mode holds the whole ladder's, the other modes the two steps')
-        const size_t at = quant.mode == GK_QUANT_PSNR ? q_notch : 0;
-        qres.notch = q_notch;
+        gk_quant_result& qres = ctx->quant_res;
+        const size_t at = quant.mode == GK_QUANT_PSNR ? q.notch : 0;
+        qres.notch = q.notch; qres.bytes = total;
         qres.base_step = P.p.qstep > 0.0 ? P.p.qstep : quant_ladder(P.prec, P.sgnd != 0, 0);
-        qres.est_mse = q_mse[at];
-        qres.est_psnr = quant_psnr(P.prec, q_mse[at]);
-        qres.est_psnr_next = at + 1 < q_mse.size() ? quant_psnr(P.prec, q_mse[at + 1]) : 0.0;
-        qres.bytes = total;
+        qres.est_mse = q.mse[at]; qres.est_psnr = quant_psnr(P.prec, q.mse[at]);
+        qres.est_psnr_next = at + 1 < q.mse.size() ? quant_psnr(P.prec, q.mse[at + 1]) : 0.0;
     }
-    if (jp2) {
-        const size_t prefix = J.size();
-        J.clear();
-        write_jp2_prefix(J, P, total - prefix, ctx->enc_jp2h);
-        memcpy(hdrs.data(), J.data(), J.size());
+    if (P.p.jp2 && req.with_header) {   // the jp2c length
+        std::vector<uint8_t> J; write_jp2_prefix(J, P, total - Y.prefix, ctx->enc_jp2h);
+        memcpy(Y.hdrs.data(), J.data(), J.size());
     }
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[5], st));
-    if (eprof)
-        fprintf(stderr, "encode t2: fetch %.2f ms, allocate %.2f ms, packets %.2f ms, segments %.2f ms\n", ems(te0, te1),
-                ems(te1, te2), ems(te2, te3), ems(te3, eclk::now()));
-    if (total > cap) { *rc = -2; return total; }
-    // ---- device assembly
-    if (hdrs.size() > (64u << 20)) throw GkError("packet headers exceed staging");
-    uint8_t* hh = (uint8_t*)ctx->hhdr.get(hdrs.size());
-    memcpy(hh, hdrs.data(), hdrs.size());
-    HIPCHK(hipMemcpyAsync(dbytes + slot_span, hh, hdrs.size(), hipMemcpyHostToDevice, st));
-    uint64_t* hs = (uint64_t*)ctx->hseg.get(seg.size() * 8);
-    memcpy(hs, seg.data(), seg.size() * 8);
-    uint64_t* ds = (uint64_t*)ctx->dseg.get(seg.size() * 8);
-    HIPCHK(hipMemcpyAsync(ds, hs, seg.size() * 8, hipMemcpyHostToDevice, st));
-    uint8_t* dst = out_on_device ? out : (uint8_t*)ctx->dout.get(total);
-    gk_launch_gather(st, dbytes, dst, ds, (uint32_t)(seg.size() / 3));
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[6], st));
-    if (!out_on_device) HIPCHK(hipMemcpyAsync(out, dst, total, hipMemcpyDeviceToHost, st));
-    launch_check(__LINE__);
-    HIPCHK(hipEventRecord(ctx->ev[7], st));
-    HIPCHK(hipStreamSynchronize(st));
-    ctx->tm.mct_ms = ev_ms(ctx, 1, 2);
-    ctx->tm.dwt_ms = ev_ms(ctx, 2, 3);
-    ctx->tm.t1_ms = ev_ms(ctx, 3, 4);
-    ctx->tm.t1_cm_ms = ev_ms(ctx, 3, 8);
-    ctx->tm.t1_coder_ms = ev_ms(ctx, 8, 4);
-    ctx->tm.roi_ms = 0.f;
-    if (region) (void)hipEventElapsedTime(&ctx->tm.roi_ms, ctx->roi_ev[0], ctx->roi_ev[1]);
-    ctx->tm.cs_bytes = total;
-    {
-        uint64_t tbytes = 0;
-        for (uint32_t b = b0; b < b1; ++b) tbytes += hinfo[4 * (size_t)b + 2];
-        ctx->tm.t1_bytes = tbytes;
+    enc_mark(ctx, 5, __LINE__);
+    if (eprof) {
+        auto ms = [](HostClock::time_point a, HostClock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        fprintf(stderr, "encode t2: fetch %.2f ms, allocate %.2f ms, packets %.2f ms, segments %.2f ms\n", ms(h[0], h[1]),
+                ms(h[1], h[2]), ms(h[2], h[3]), ms(h[3], HostClock::now()));
     }
-    ctx->tm.t2_ms = ev_ms(ctx, 4, 5);
-    ctx->tm.assemble_ms = ev_ms(ctx, 5, 7);
-    ctx->tm.total_ms = ev_ms(ctx, 0, 7);
-    ctx->tm.t1_blocks = nbr;
-    *rc = 0;
-    return total;
+    if (total > req.cap) return EncLen{total, false};
+    assemble(ctx, A, Y, req);
+    encode_timings(ctx, R, F.hinfo, total, region);
+    return EncLen{total, true};
 }
+}  // namespace
 
 // ---------------------------------------------------------------------------
 // Decode
@@ -5736,7 +5805,6 @@ static void merge_tile_parts(Header& Hd) {
 // and the chain only goes down: decode_call (or view_call, which resolves a view first and runs
 // k_view last) -> decode_opened -> decode_output -> decode_planes -> decode_display or
 // decode_colour -> decode_components -> decode_core.
-using HostClock = std::chrono::steady_clock;
 namespace {
 // the bytes as the caller gave them
 struct DecSrc { const uint8_t* cs; size_t len; bool on_device; };
@@ -7825,8 +7893,7 @@ static void xcode_probe(const uint8_t* cs, size_t len, const gk_transcode_params
         xcode_check_part(P, TP, st2);
     }
 }
-static size_t xcode_call(gk_ctx* ctx, const DecSrc& src, const gk_transcode_params& tp, uint8_t* out, size_t cap,
-                         int out_on_device, int* rc) {
+static EncLen xcode_call(gk_ctx* ctx, const DecSrc& src, const gk_transcode_params& tp, const EncReq& dst) {
     if (ctx->dec_layers) throw GkError("transcode: gk_set_decode_layers is set (a transcode takes every layer)");
     if (ctx->dec_reduce) throw GkError("transcode: gk_set_decode_reduce is set (a transcode takes every resolution)");
     hipStream_t st = ctx->st;
@@ -7865,8 +7932,8 @@ static size_t xcode_call(gk_ctx* ctx, const DecSrc& src, const gk_transcode_para
     } restore{P, P.p};
     P.p = xcode_target_params(restore.keep, X);
     gk_image_info info{};
-    size_t n = encode_impl(ctx, &info, nullptr, nullptr, 1, nullptr, out, cap, out_on_device, rc, 0, 0, true, nullptr, false,
-                           nullptr, nullptr, &X);
+    EncSrc es; es.xc = &X;
+    const EncLen n = encode_impl(ctx, &info, nullptr, es, dst);
     // the call's times: T1 is the source coder's decode (t1_cm_ms) and the target coder's encode
     // (t1_coder_ms); T2 is the packet-header parse and the packet write; no DWT, no sample stage
     gk_timings& tm = ctx->tm;
@@ -7876,6 +7943,22 @@ static size_t xcode_call(gk_ctx* ctx, const DecSrc& src, const gk_transcode_para
     tm.total_ms += X.t2_parse_ms + X.stage_ms + X.t1_dec_ms;
     tm.mct_ms = 0.f; tm.dwt_ms = 0.f; tm.dwt_launches = 0; tm.dwt_bytes = 0;
     return n;
+}
+
+// the encode entry points and gk_transcode: call() makes the entry's own refusals and runs the core
+template <class F> static int encode_entry(gk_ctx* ctx, size_t* out_len, const F& call) {
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
+        const EncLen n = call();
+        if (out_len) *out_len = n.n;
+        if (!n.fits) ctx->err = "output capacity too small";
+        return n.fits ? 0 : -2;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -7979,35 +8062,24 @@ int gk_encode(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, 
               int comps_on_device, const gk_cparameters* p, uint8_t* out, size_t cap, size_t* out_len,
               int out_on_device) {
     if (!ctx || !info || !comps || !strides || !out) return -1;
-    try {
-        (void)hipSetDevice(ctx->device);
-        DevBusy busy(ctx->device);
-        ctx->tm.t1_shared = 0;
-        int rc = 0;
+    return encode_entry(ctx, out_len, [&]() {
         EncConvCall cv;
-        const bool conv = enc_convert_call(ctx, info, cv);
-        size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc, 0, 0, true,
-                               nullptr, false, nullptr, conv ? &cv : nullptr);
-        if (out_len) *out_len = n;
-        if (rc == -2) ctx->err = "output capacity too small";
-        return rc;
-    } catch (const GkError& e) {
-        ctx->err = e.msg;
-        return -1;
-    }
+        EncSrc src; src.comps = comps; src.strides = strides; src.on_device = comps_on_device != 0;
+        if (enc_convert_call(ctx, info, cv)) src.cv = &cv;
+        EncReq req; req.out = out; req.cap = cap; req.out_on_device = out_on_device != 0;
+        return encode_impl(ctx, info, p, src, req);
+    });
 }
 
 int gk_encode_pixels(gk_ctx* ctx, const gk_image_info* info, const void* pixels, size_t row_bytes, int pixels_on_device,
                      const gk_cparameters* p, uint8_t* out, size_t cap, size_t* out_len, int out_on_device) {
     if (!ctx || !info || !pixels || !out) return -1;
-    try {
-        (void)hipSetDevice(ctx->device);
-        DevBusy busy(ctx->device);
-        ctx->tm.t1_shared = 0;
+    return encode_entry(ctx, out_len, [&]() {
         // what packed pixels cannot express; whatever gk_encode refuses follows in encode_impl
         // (setup_plan), which allocates nothing before it
         EncConvCall cv;
-        const bool conv = enc_convert_call(ctx, info, cv);
+        EncSrc src;
+        if (enc_convert_call(ctx, info, cv)) src.cv = &cv;
         for (size_t c = 0; c < ctx->enc_dx.size(); ++c)
             if (ctx->enc_dx[c] != 1 || ctx->enc_dy[c] != 1)
                 throw GkError("pixels: gk_set_subsampling is active (packed pixels have one grid; use the planar call)");
@@ -8017,64 +8089,45 @@ int gk_encode_pixels(gk_ctx* ctx, const gk_image_info* info, const void* pixels,
         if (row_bytes % es) throw GkError("pixels: row_bytes must be a multiple of the sample size");
         if ((uintptr_t)pixels % es) throw GkError("pixels: the buffer is not aligned to its sample size");
         const PixSrc px{pixels, row_bytes, pixels_on_device};
-        int rc = 0;
-        size_t n = encode_impl(ctx, info, nullptr, nullptr, 1, p, out, cap, out_on_device, &rc, 0, 0, true, nullptr, false, &px,
-                               conv ? &cv : nullptr);
-        if (out_len) *out_len = n;
-        if (rc == -2) ctx->err = "output capacity too small";
-        return rc;
-    } catch (const GkError& e) {
-        ctx->err = e.msg;
-        return -1;
-    }
+        src.pix = &px;
+        EncReq req; req.out = out; req.cap = cap; req.out_on_device = out_on_device != 0;
+        return encode_impl(ctx, info, p, src, req);
+    });
 }
 
 int gk_encode_tiles(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
                     int comps_on_device, const gk_cparameters* p, uint32_t tile_begin, uint32_t tile_end,
                     uint8_t* out, size_t cap, size_t* out_len, uint32_t* part_lens, int out_on_device) {
     if (!ctx || !info || !comps || !strides || !out || !part_lens || tile_end <= tile_begin) return -1;
-    try {
-        (void)hipSetDevice(ctx->device);
-        DevBusy busy(ctx->device);
-        ctx->tm.t1_shared = 0;
+    return encode_entry(ctx, out_len, [&]() {
         refuse_under_convert(ctx, "gk_encode_tiles");
         if (ctx->enc_roi.set)
             throw GkError("roi: gk_encode_tiles while gk_set_encode_roi is set (whole images only: use gk_encode / gk_encode_pixels, or clear it)");
-        int rc = 0;
-        size_t n = encode_impl(ctx, info, comps, strides, comps_on_device, p, out, cap, out_on_device, &rc,
-                               tile_begin, tile_end, false, part_lens);
-        if (out_len) *out_len = n;
-        if (rc == -2) ctx->err = "output capacity too small";
-        return rc;
-    } catch (const GkError& e) {
-        ctx->err = e.msg;
-        return -1;
-    }
+        EncSrc src; src.comps = comps; src.strides = strides; src.on_device = comps_on_device != 0;
+        EncReq req;
+        req.tb = tile_begin; req.te = tile_end; req.with_header = false; req.part_lens = part_lens;
+        req.out = out; req.cap = cap; req.out_on_device = out_on_device != 0;
+        return encode_impl(ctx, info, p, src, req);
+    });
 }
 
 int gk_encode_blocks(gk_ctx* ctx, const gk_image_info* info, const void* const* comps, const uint32_t* strides,
                      int comps_on_device, const gk_cparameters* p, uint32_t* nbands, uint32_t* nblocks,
                      uint64_t* nbytes, uint32_t* npasses) {
     if (!ctx || !info || !comps || !strides) return -1;
-    try {
-        (void)hipSetDevice(ctx->device);
-        DevBusy busy(ctx->device);
-        ctx->tm.t1_shared = 0;
+    return encode_entry(ctx, nullptr, [&]() {
         refuse_under_convert(ctx, "gk_encode_blocks");
         if (p && p->tile_size_on && (p->t_width < info->w || p->t_height < info->h))
             throw GkError("code-block results are produced for single-tile images only (Grok's plugin tile is one tile)");
-        int rc = 0;
-        uint8_t dummy = 0;
-        encode_impl(ctx, info, comps, strides, comps_on_device, p, &dummy, 0, 0, &rc, 0, 0, true, nullptr, true);
+        EncSrc src; src.comps = comps; src.strides = strides; src.on_device = comps_on_device != 0;
+        EncReq req; req.blocks_only = true;
+        const EncLen n = encode_impl(ctx, info, p, src, req);
         if (nbands) *nbands = (uint32_t)ctx->rb_bands.size();
         if (nblocks) *nblocks = (uint32_t)ctx->rb_blocks.size();
         if (nbytes) *nbytes = ctx->rb_data.size();
         if (npasses) *npasses = (uint32_t)ctx->rb_passes.size();
-        return rc;
-    } catch (const GkError& e) {
-        ctx->err = e.msg;
-        return -1;
-    }
+        return n;
+    });
 }
 
 int gk_encode_blocks_get(gk_ctx* ctx, gk_band_result* bands, gk_block_result* blocks, uint8_t* data,
@@ -8597,21 +8650,12 @@ void gk_set_default_transcode(gk_transcode_params* p) {
 int gk_transcode(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_transcode_params* p, uint8_t* out,
                  size_t cap, int out_on_device, size_t* out_len) {
     if (!ctx || !cs || !out) return -1;
-    try {
-        (void)hipSetDevice(ctx->device);
-        DevBusy busy(ctx->device);
-        ctx->tm.t1_shared = 0;
+    return encode_entry(ctx, out_len, [&]() {
         gk_transcode_params dp;
         gk_set_default_transcode(&dp);
-        int rc = 0;
-        const size_t n = xcode_call(ctx, DecSrc{cs, len, cs_on_device != 0}, p ? *p : dp, out, cap, out_on_device, &rc);
-        if (out_len) *out_len = n;
-        if (rc == -2) ctx->err = "output capacity too small";
-        return rc;
-    } catch (const GkError& e) {
-        ctx->err = e.msg;
-        return -1;
-    }
+        EncReq req; req.out = out; req.cap = cap; req.out_on_device = out_on_device != 0;
+        return xcode_call(ctx, DecSrc{cs, len, cs_on_device != 0}, p ? *p : dp, req);
+    });
 }
 int gk_probe_transcode(const uint8_t* cs, size_t len, const gk_transcode_params* p, char* msg, size_t msg_cap) {
     if (!cs) return -1;

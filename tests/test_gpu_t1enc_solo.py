@@ -58,3 +58,26 @@ def test_solo_chunked_large(eng, monkeypatch):
     for nsolo in (0, 48, 256):
         monkeypatch.setenv("GK_T1ENC_SOLO", str(nsolo))
         assert eng.encode(img, 12, params=_params(kw)) == ref, nsolo
+
+
+# The two thresholds the encode core's stages sit on, at the smallest images that reach them:
+# 8,192 blocks (t1_encode: the chunked arm from there, the one-pass arm below) and 3 x 8,192 body
+# triples of one tile (layout_segments: the per-packet parallel arm).  4 x 4 code-blocks, one
+# resolution, one component: 256 x 512 samples are exactly 8,192 blocks (cuts at 1,024 and 3,072
+# blocks; with rate control at 512 and 2,048, pass records through PCRD), 256 x 508 are 8,128.
+THRESHOLDS = [
+    ("8192_blocks", (256, 512), {}),
+    ("8128_blocks", (256, 508), {}),
+    ("8192_blocks_rc", (256, 512), dict(irreversible=True, layer_rate=[20.0, 5.0])),
+]
+
+
+@pytest.mark.parametrize("name,shape,extra", THRESHOLDS, ids=[c[0] for c in THRESHOLDS])
+def test_block_count_thresholds_vs_oracle(eng, name, shape, extra):
+    from grok_amd.synth import synth_image
+    h, w = shape
+    img = synth_image(h, w, 1, 8, 23).astype(np.int32)
+    kw = dict(cblk=(4, 4), numres=1, **extra)
+    ref = O.encode(img, 8, **kw)
+    cs = eng.encode(img, 8, params=_params(kw))
+    assert cs == ref, (name, len(cs), len(ref))
