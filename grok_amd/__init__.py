@@ -32,7 +32,9 @@ EXPORTS = ("gk_create", "gk_destroy", "gk_set_default_params", "gk_encode", "gk_
            "gk_set_encode_convert", "gk_probe_encode_convert", "gk_set_default_transcode", "gk_transcode",
            "gk_probe_transcode", "gk_set_encode_roi", "gk_probe_encode_roi", "gk_roi_band_mask",
            "gk_set_encode_quant", "gk_probe_encode_quant", "gk_get_encode_quant", "gk_probe_view",
-           "gk_decode_view_pixels", "gk_set_decode_render", "gk_probe_render", "gk_decode_levels")
+           "gk_decode_view_pixels", "gk_set_decode_render", "gk_probe_render", "gk_decode_levels",
+           "gk_probe_tensor", "gk_decode_view_tensor")
+GK_TENSOR_F32, GK_TENSOR_F16, GK_TENSOR_BF16 = 1, 2, 3   # gk_tensor::dtype
 GK_RENDER_WINDOW, GK_RENDER_MAP, GK_RENDER_BLEND = 1, 2, 3   # gk_render::mode
 GK_RENDER_MAX_CHANNELS, GK_LEVELS_MAX_BINS = 16, 4096
 GK_QUANT_STEP, GK_QUANT_BYTES, GK_QUANT_PSNR = 1, 2, 3   # gk_encode_quant::mode
@@ -229,6 +231,80 @@ class LevelsBins(ctypes.Structure):
 class ChannelLevels(ctypes.Structure):
     """gk_channel_levels: one channel's statistics."""
     _fields_ = [("min", ctypes.c_int32), ("max", ctypes.c_int32), ("sum", ctypes.c_int64), ("count", ctypes.c_uint64)]
+
+
+class Tensor(ctypes.Structure):
+    """gk_tensor (include/grok_amd.h): where and how a view is written as floats."""
+    _fields_ = [("data", ctypes.c_void_p), ("on_device", ctypes.c_int32), ("dtype", ctypes.c_uint32),
+                ("stride_c", ctypes.c_int64), ("stride_y", ctypes.c_int64), ("stride_x", ctypes.c_int64),
+                ("n", ctypes.c_uint32), ("scale", ctypes.POINTER(ctypes.c_float)), ("bias", ctypes.POINTER(ctypes.c_float))]
+
+
+_TENSOR_DTYPES = {"float32": GK_TENSOR_F32, "float16": GK_TENSOR_F16, "bfloat16": GK_TENSOR_BF16}
+
+
+def _tensor_dtype(dtype):
+    """gk_tensor::dtype of a name, a numpy dtype or a torch dtype."""
+    name = str(dtype).replace("torch.", "")
+    if name not in _TENSOR_DTYPES:
+        name = getattr(dtype, "__name__", name)   # (np.float32 and its like)
+    if name not in _TENSOR_DTYPES:
+        raise ValueError("tensor: dtype %r (float32, float16 or bfloat16)" % (dtype,))
+    return _TENSOR_DTYPES[name]
+
+
+def _tensor_affine(mean=None, std=None, unit=None, prec=None, sgnd=False):
+    """(scale, bias) as float32 arrays for x = (v / unit - mean_k) / std_k: scale_k = 1 / (unit std_k)
+    and bias_k = -mean_k / std_k, computed in float64 and rounded once to float32.  mean / std: a
+    number or one per channel (the shorter list's last entry repeats; None: 0 / 1).  unit: None is
+    2^prec - 1 of an unsigned view; a signed view has no such default."""
+    if unit is None:
+        if sgnd:
+            raise ValueError("tensor: a signed view has no default unit: give unit=")
+        if not prec:
+            raise ValueError("tensor: give unit= (the view's precision is not known)")
+        unit = 2 ** int(prec) - 1
+    as_list = lambda x, d: [float(e) for e in x] if isinstance(x, (list, tuple, np.ndarray)) else [float(d if x is None else x)]
+    m, s = as_list(mean, 0.0), as_list(std, 1.0)
+    if not m or not s:
+        raise ValueError("tensor: an empty mean or std")
+    n = max(len(m), len(s))
+    m = np.array([m[min(k, len(m) - 1)] for k in range(n)], np.float64)
+    s = np.array([s[min(k, len(s) - 1)] for k in range(n)], np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):   # (the engine names a result that is not finite)
+        return (1.0 / (np.float64(unit) * s)).astype(np.float32), (-m / s).astype(np.float32)
+
+
+def _tensor_description(dtype, strides, scale=None, bias=None, data=None, on_device=True):
+    """The gk_tensor of a dtype, (stride_c, stride_y, stride_x) in elements and scale / bias (a
+    number or one per channel; None: 1 / 0), and the arrays it points into."""
+    as_f32 = lambda x, d: np.ascontiguousarray(np.atleast_1d(np.asarray(d if x is None else x, np.float64)).astype(np.float32).reshape(-1))
+    if scale is None and bias is None:
+        n, sc, bi = 0, None, None
+    else:
+        sc, bi = as_f32(scale, 1.0), as_f32(bias, 0.0)
+        n = max(len(sc), len(bi))
+        if not len(sc) or not len(bi):
+            raise ValueError("tensor: an empty scale or bias")
+        sc, bi = (np.concatenate([a, np.repeat(a[-1:], n - len(a))]) for a in (sc, bi))
+    fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if a is not None else None
+    t = Tensor(data, int(bool(on_device)), _tensor_dtype(dtype), int(strides[0]), int(strides[1]), int(strides[2]), n, fp(sc), fp(bi))
+    return t, (sc, bi)
+
+
+def probe_tensor(view_result, dtype, strides, scale=None, bias=None, on_device=True):
+    """gk_probe_tensor: the extent in elements of a tensor of `dtype` ("float32", "float16",
+    "bfloat16", or a numpy / torch dtype) with strides = (stride_c, stride_y, stride_x) in
+    elements for a resolved view (probe_view's ViewResult), as Engine.decode_tensor would judge
+    it; no engine or GPU needed.  on_device=False asks about a host tensor, which must be dense.
+    Raises ValueError with the engine's refusal."""
+    lib = load_library()
+    t, keep = _tensor_description(dtype, strides, scale, bias, None, on_device)
+    extent, msg = ctypes.c_uint64(0), ctypes.create_string_buffer(512)
+    if lib.gk_probe_tensor(ctypes.byref(view_result), ctypes.byref(t), ctypes.byref(extent), msg, 512) != 0:
+        raise ValueError(msg.value.decode())
+    del keep
+    return extent.value
 
 
 def gamma_curve(g):
@@ -801,6 +877,12 @@ def load_library(build_if_missing=True):
         lib.gk_decode_levels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(View),
                                          P(LevelsBins), ctypes.c_uint32, ctypes.c_uint32, P(ChannelLevels),
                                          ctypes.c_void_p, ctypes.c_size_t, P(ViewResult)]
+    if hasattr(lib, "gk_probe_tensor") or not os.environ.get("GROK_AMD_LIB"):   # (as above: an older A side)
+        lib.gk_probe_tensor.restype = ctypes.c_int
+        lib.gk_probe_tensor.argtypes = [P(ViewResult), P(Tensor), P(ctypes.c_uint64), ctypes.c_char_p, ctypes.c_size_t]
+        lib.gk_decode_view_tensor.restype = ctypes.c_int
+        lib.gk_decode_view_tensor.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(View),
+                                              P(Tensor), P(ViewResult)]
     lib.gk_set_decode_layers.restype = ctypes.c_int
     lib.gk_set_decode_layers.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.gk_decode.restype = ctypes.c_int
@@ -1682,6 +1764,92 @@ class Engine:
             self._err("gk_decode_pixels")
         return res
 
+    def _view_pix_size(self, src, n, on_dev, v, fit, info):
+        """(pix_w, pix_h, None) of the image a view writes, or (0, 0, why).  Host bytes: the engine's
+        own answer (gk_probe_view under this engine's display flags and precision list).  Device
+        bytes cannot be probed: the size rule restated (_view_size; an all-0 region is the image, as
+        in the C ABI)."""
+        if not on_dev:
+            arr, np_ = _precision_array(self._precision)
+            msg = ctypes.create_string_buffer(512)
+            pr = ViewResult()
+            if self.lib.gk_probe_view(src, n, self._display_flags, arr, np_, ctypes.byref(v), ctypes.byref(pr), msg, 512) == 0:
+                return pr.pix_w, pr.pix_h, None
+            return 0, 0, msg.value.decode()
+        whole = not (v.x0 or v.y0 or v.x1 or v.y1)
+        bw, bh = (info.w, info.h) if whole else (v.x1 - v.x0, v.y1 - v.y0)
+        try:
+            ow, oh = _view_size(bw, bh, v.out_w, v.out_h, fit) if bw > 0 and bh > 0 else (0, 0)
+        except ValueError:
+            ow = oh = 0
+        if 0 < ow <= bw and 0 < oh <= bh:
+            return (oh, ow, None) if v.rotate in (90, 270) else (ow, oh, None)
+        return 0, 0, "the view has no size here"
+
+    def decode_tensor(self, cs, region=None, size=None, width=None, height=None, fit=False, rotate=0, mirror=False,
+                      dtype="float32", layout="chw", scale=None, bias=None, mean=None, std=None, unit=None,
+                      out=None, length=None):
+        """gk_decode_view_tensor: the view decode_view(cs, region, size, ...) returns as int32, written
+        by the GPU as normalised floats, x = float32(v) * scale_k + bias_k in two float32 roundings
+        and then rounded to the tensor's type (include/grok_amd.h has the exact rule).  region /
+        size / width / height / fit / rotate / mirror: as decode_view (none of the sizes: the
+        region's own).  scale / bias: a number or one per channel (None: 1 / 0); or mean / std (a
+        number or one per channel) with unit: scale_k = 1 / (unit std_k), bias_k = -mean_k / std_k
+        (_tensor_affine), unit defaulting to 2^prec - 1 of an unsigned view.  Without ``out`` it
+        returns a dense numpy array of dtype "float32" or "float16" and layout "chw" (C, H, W) or "hwc"
+        (H, W, C).  ``out``: a 3-d torch cuda tensor in float32 / float16 / bfloat16 of that shape
+        in `layout`; its dtype decides and its stride() values go to the engine as they are, so a
+        slice batch[i] of a batch tensor and a channels_last tensor both work.  Every sticky decode
+        setting is honoured, except that set_decode_reduce must be 0 and a render must be cleared.
+        The resolved view is kept as self.view_result."""
+        if layout not in ("chw", "hwc"):
+            raise ValueError("tensor: layout %r (chw or hwc)" % (layout,))
+        if (scale is not None or bias is not None) and (mean is not None or std is not None or unit is not None):
+            raise ValueError("tensor: give scale= / bias= or mean= / std= / unit=, not both")
+        if _is_torch_cuda(cs):
+            src, n, on_dev = ctypes.c_void_p(cs.data_ptr()), length, 1
+        else:
+            b = np.frombuffer(cs, np.uint8)
+            src, n, on_dev = ctypes.c_void_p(b.ctypes.data), len(cs), 0
+        info = self.read_header(cs, length)
+        if size is None and width is None and height is None:
+            size = (region[2] - region[0], region[3] - region[1]) if region is not None else (info.w, info.h)
+        v, vr = _view(region, size, width, height, fit, rotate, mirror), ViewResult()
+        w, h, why = self._view_pix_size(src, n, on_dev, v, fit, info)
+        if why is not None or getattr(self, "_render", False):
+            # The engine names its refusal itself.  It is asked with a host tensor of overlapping strides,
+            # which is refused after the refusals that concern the settings and the view.
+            one = np.zeros(1, np.int64)
+            t, keep = _tensor_description("float32", (1, 1, 1), None, None, one.ctypes.data, False)
+            self.lib.gk_decode_view_tensor(self.ctx, src, n, on_dev, ctypes.byref(v), ctypes.byref(t), ctypes.byref(vr))
+            err = self.lib.gk_last_error(self.ctx).decode()
+            raise RuntimeError("gk_decode_view_tensor failed: %s" % (why if why and "tensor: " in err else err))
+        if mean is not None or std is not None or unit is not None:
+            scale, bias = _tensor_affine(mean, std, unit, info.prec, info.sgnd)
+        c = info.numcomps
+        shape = (c, h, w) if layout == "chw" else (h, w, c)
+        if out is not None:
+            if not _is_torch_cuda(out) or out.dim() != 3 or tuple(out.shape) != shape:
+                raise ValueError("tensor: out must be a torch cuda tensor of shape %r (%s)" % (shape, layout))
+            st = out.stride()
+            strides = st if layout == "chw" else (st[2], st[0], st[1])
+            t, keep = _tensor_description(out.dtype, strides, scale, bias, out.data_ptr(), True)
+            res = out
+        else:
+            if _tensor_dtype(dtype) == GK_TENSOR_BF16:
+                raise ValueError("tensor: numpy has no bfloat16: give out= (a torch cuda tensor)")
+            res = np.empty(shape, np.float32 if _tensor_dtype(dtype) == GK_TENSOR_F32 else np.float16)
+            strides = (h * w, w, 1) if layout == "chw" else (1, w * c, c)
+            t, keep = _tensor_description(dtype, strides, scale, bias, res.ctypes.data, False)
+        if self.lib.gk_decode_view_tensor(self.ctx, src, n, on_dev, ctypes.byref(v), ctypes.byref(t), ctypes.byref(vr)) != 0:
+            self._err("gk_decode_view_tensor")
+        del keep
+        if (vr.pix_h, vr.pix_w, vr.channels) != (h, w, c):
+            raise RuntimeError("gk_decode_view_tensor wrote %d x %d x %d pixels into a tensor of %d x %d x %d"
+                               % (vr.pix_h, vr.pix_w, vr.channels, h, w, c))
+        self.view_result = vr
+        return res
+
     def decode_view(self, cs, region=None, size=None, width=None, height=None, fit=False, rotate=0, mirror=False,
                     out=None, sample_bytes=0, length=None):
         """gk_decode_view_pixels: region = (x0, y0, x1, y1) of the image (None: all of it) at exactly
@@ -1702,29 +1870,7 @@ class Engine:
             b = np.frombuffer(cs, np.uint8)
             src, n, on_dev = ctypes.c_void_p(b.ctypes.data), len(cs), 0
         vr = ViewResult()
-        # The size of the written image.  Host bytes: the engine's own answer (gk_probe_view under this
-        # engine's display flags and precision list).  Device bytes cannot be probed: the size rule
-        # restated (_view_size; an all-0 region is the image, as in the C ABI).
-        why = None
-        if not on_dev:
-            arr, np_ = _precision_array(self._precision)
-            msg = ctypes.create_string_buffer(512)
-            pr = ViewResult()
-            if self.lib.gk_probe_view(src, n, self._display_flags, arr, np_, ctypes.byref(v), ctypes.byref(pr), msg, 512) == 0:
-                w, h = pr.pix_w, pr.pix_h
-            else:
-                why = msg.value.decode()
-        else:
-            whole = not (v.x0 or v.y0 or v.x1 or v.y1)
-            bw, bh = (info.w, info.h) if whole else (v.x1 - v.x0, v.y1 - v.y0)
-            try:
-                ow, oh = _view_size(bw, bh, v.out_w, v.out_h, fit) if bw > 0 and bh > 0 else (0, 0)
-            except ValueError:
-                ow = oh = 0
-            if 0 < ow <= bw and 0 < oh <= bh:
-                w, h = (oh, ow) if v.rotate in (90, 270) else (ow, oh)
-            else:
-                why = "the view has no size here"
+        w, h, why = self._view_pix_size(src, n, on_dev, v, fit, info)
         if why is not None:
             # The engine names its refusal itself.  It is asked with row_bytes 0, which is below any row
             # and so is refused, after the refusals that concern the view, before a byte is written.

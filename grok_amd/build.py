@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, "libgrok_amd.so")
 # Grok's plugin loader opens <pluginPath>/libgrokj2k_plugin.so (grok.cpp:579-605)
 PLUGIN = os.path.join(HERE, "libgrokj2k_plugin.so")
 ENGINE = ["gk_kernels.hip", "gk_dwt97.hip", "gk_dwt_any.hip", "gk_t1enc.hip", "gk_t1dec.hip", "gk_t1ms.hip", "gk_ht.hip", "gk_htq.hip", "gk_colour.hip", "gk_icc.hip",
-          "gk_pixels.hip", "gk_view.hip", "gk_render.hip", "gk_unpixels.hip", "gk_rgbycc.hip", "gk_roi.hip", "gk_engine.cpp"]
+          "gk_pixels.hip", "gk_view.hip", "gk_render.hip", "gk_tensor.hip", "gk_unpixels.hip", "gk_rgbycc.hip", "gk_roi.hip", "gk_engine.cpp"]
 SOURCES = ENGINE + ["grk_shim.cpp", "grk_plugin.cpp"]
 
 

@@ -6585,6 +6585,91 @@ static void view_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, void* pi
     ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
     if (res) *res = R;
 }
+// ---- A view as a float tensor (gk_probe_tensor, gk_decode_view_tensor).  tensor_extent is the one
+// place where a description is judged against a resolved view; the probe and the decode share it.
+static uint32_t tensor_elem_size(uint32_t dtype) { return dtype == GK_TENSOR_F32 ? 4 : 2; }
+// the refusals of a description that need no view
+static void tensor_description(const gk_tensor& t) {
+    if (t.dtype < GK_TENSOR_F32 || t.dtype > GK_TENSOR_BF16)
+        throw GkError("tensor: dtype " + std::to_string(t.dtype) + " (1 float32, 2 float16, 3 bfloat16)");
+    if (t.n > GK_PIX_MAX_CH) throw GkError("tensor: " + std::to_string(t.n) + " scale / bias entries (at most " + std::to_string(GK_PIX_MAX_CH) + ")");
+    if (t.n && !t.scale) throw GkError("tensor: n = " + std::to_string(t.n) + " without scale");
+    if (t.n && !t.bias) throw GkError("tensor: n = " + std::to_string(t.n) + " without bias");
+    for (uint32_t k = 0; k < t.n; ++k) {
+        if (!std::isfinite(t.scale[k])) throw GkError("tensor: scale entry " + std::to_string(k) + " is not finite");
+        if (!std::isfinite(t.bias[k])) throw GkError("tensor: bias entry " + std::to_string(k) + " is not finite");
+    }
+}
+// the layout rule (include/grok_amd.h): the extent in elements, or the refusal
+static uint64_t tensor_extent(const gk_view_result& R, const gk_tensor& t) {
+    tensor_description(t);
+    struct Dim { uint64_t size; int64_t stride; const char* name; };
+    std::vector<Dim> dims;
+    for (const Dim& d : {Dim{R.channels, t.stride_c, "stride_c"}, Dim{R.pix_h, t.stride_y, "stride_y"}, Dim{R.pix_w, t.stride_x, "stride_x"}}) {
+        if (!d.size) throw GkError("tensor: a view without pixels");
+        if (d.size == 1) continue;   // its stride is never multiplied by anything but 0
+        if (d.stride <= 0)
+            throw GkError(std::string("tensor: ") + d.name + " is " + std::to_string(d.stride) + " on a dimension of size " +
+                          std::to_string(d.size) + " (a stride must be positive)");
+        dims.push_back(d);
+    }
+    std::stable_sort(dims.begin(), dims.end(), [](const Dim& a, const Dim& b) { return a.stride < b.stride; });
+    unsigned __int128 extent = 1;
+    for (size_t d = 0; d < dims.size(); ++d) {
+        if (d && (unsigned __int128)dims[d].stride < (unsigned __int128)dims[d - 1].stride * dims[d - 1].size)
+            throw GkError(std::string("tensor: overlapping strides: ") + dims[d].name + " " + std::to_string(dims[d].stride) + " is below " +
+                          dims[d - 1].name + " " + std::to_string(dims[d - 1].stride) + " times its size " + std::to_string(dims[d - 1].size));
+        extent += (unsigned __int128)(dims[d].size - 1) * (uint64_t)dims[d].stride;
+    }
+    if (extent >> 60) throw GkError("tensor: an extent of 2^60 elements or more");
+    const uint64_t count = (uint64_t)R.channels * R.pix_w * R.pix_h;   // (16 x 2^32 x 2^32 at the very most: the view's own bounds are far below)
+    if (!t.on_device && (uint64_t)extent != count)
+        throw GkError("tensor: a host tensor must be dense (an extent of " + std::to_string((uint64_t)extent) + " elements for " +
+                      std::to_string(count) + " samples)");
+    if (t.on_device && t.data && ((uintptr_t)t.data % tensor_elem_size(t.dtype)))
+        throw GkError("tensor: the device pointer is not aligned to its element size");
+    return (uint64_t)extent;
+}
+static void tensor_call(gk_ctx* ctx, const DecSrc& src, const gk_view& v, const gk_tensor* t, gk_view_result* res) {
+    if (!t) throw GkError("tensor: no description");
+    if (!t->data) throw GkError("tensor: no data");
+    if (ctx->dec_render.mode) throw GkError("tensor: gk_set_decode_render is set: clear it");
+    if (ctx->dec_reduce)
+        throw GkError("view: gk_set_decode_reduce is set (a view chooses the reduce level itself): set it to 0");
+    tensor_description(*t);   // (before the stream is touched; tensor_extent repeats it for the probe's sake)
+    hipStream_t st = ctx->st;
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    DecStream o;
+    open_stream(o, src, st, true);
+    const ViewPlan V = resolve_view(o, ctx->dec_colour, ctx->dec_display, ctx->dec_prec, v);
+    const gk_view_result& R = V.res;
+    const uint64_t extent = tensor_extent(R, *t);
+    if ((uint64_t)((R.out_w + 15) / 16) * ((R.out_h + 15) / 16) > GK_VIEW_MAX_TILES) throw GkError("view: an output of 2^24 tiles of 16 x 16 pixels or more is too large for one launch");
+    const size_t bytes = (size_t)extent * tensor_elem_size(t->dtype);
+    GkTensorArgs a{};
+    a.v.src = view_region(ctx, o, V);
+    a.v.rw = R.rx1 - R.rx0; a.v.rh = R.ry1 - R.ry0; a.v.ow = R.out_w; a.v.oh = R.out_h; a.v.nch = R.channels;
+    a.v.mirror = v.mirror; a.v.rot = v.rotate / 90;
+    a.v.dst = t->on_device ? t->data : ctx->dpix_out.get(bytes);   // host: staged in the same strides
+    // a dimension of size 1 only ever meets index 0: its stride, which may be anything, is dropped
+    a.stride_c = R.channels > 1 ? t->stride_c : 0;
+    a.stride_y = R.pix_h > 1 ? t->stride_y : 0;
+    a.stride_x = R.pix_w > 1 ? t->stride_x : 0;
+    for (uint32_t k = 0; k < R.channels; ++k) {
+        a.scale[k] = t->n ? t->scale[std::min(k, t->n - 1)] : 1.0f;
+        a.bias[k] = t->n ? t->bias[std::min(k, t->n - 1)] : 0.0f;
+    }
+    HIPCHK(hipEventRecord(ctx->ev[24], st));
+    if (gk_launch_tensor(st, t->dtype, a)) throw GkError("internal: tensor geometry");
+    launch_check(__LINE__);
+    HIPCHK(hipEventRecord(ctx->ev[25], st));
+    if (!t->on_device) HIPCHK(hipMemcpyAsync(t->data, a.v.dst, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const float ms = ev_ms(ctx, 24, 25);   // the tensor pass counts as sample stage, as the view pass does
+    ctx->tm.mct_ms += ms; ctx->tm.total_ms += ms;
+    if (res) *res = R;
+}
 // gk_decode_levels: the view's int32 pixels are never written; k_levels (gk_render.hip) folds them
 // into ctx->dlevels, 16 GkLevelsStat and then channels * bins uint64 counters, which this call
 // initialises, reads back and leaves behind as scratch
@@ -8877,6 +8962,33 @@ int gk_decode_levels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
         DevBusy busy(ctx->device);
         ctx->tm.t1_shared = 0;
         levels_call(ctx, DecSrc{cs, len, cs_on_device != 0}, *v, q, nq, bins, stats, hist, hist_cap, res);
+        return 0;
+    } catch (const GkError& e) {
+        ctx->err = e.msg;
+        return -1;
+    }
+}
+
+int gk_probe_tensor(const gk_view_result* view, const gk_tensor* t, uint64_t* extent, char* msg, size_t msg_cap) {
+    try {
+        if (!view) throw GkError("tensor: no view");
+        if (!t) throw GkError("tensor: no description");
+        const uint64_t e = tensor_extent(*view, *t);
+        if (extent) *extent = e;
+        return 0;
+    } catch (const GkError& e) {
+        if (msg && msg_cap) snprintf(msg, msg_cap, "%s", e.msg.c_str());
+        return -1;
+    }
+}
+int gk_decode_view_tensor(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_view* v, const gk_tensor* t,
+                          gk_view_result* res) {
+    if (!ctx || !cs || !v) return -1;
+    try {
+        (void)hipSetDevice(ctx->device);
+        DevBusy busy(ctx->device);
+        ctx->tm.t1_shared = 0;
+        tensor_call(ctx, DecSrc{cs, len, cs_on_device != 0}, *v, t, res);
         return 0;
     } catch (const GkError& e) {
         ctx->err = e.msg;

@@ -281,6 +281,19 @@ struct GkLevelsArgs {
     uint32_t bins;
 };
 int gk_launch_levels(hipStream_t st, const GkLevelsArgs& args);
+// The view's last stage as a float tensor (gk_tensor.hip, k_tensor): the geometry and the area
+// average of k_view, then per channel k the int32 v the view would return becomes
+//     z = (float)v * scale[k] + bias[k]     two float32 roundings to nearest even, never one fused
+// and is written as float32, float16 or bfloat16 (z rounded to nearest even) at element
+// k * stride_c + y * stride_y + x * stride_x of v.dst, (x, y) a pixel of the written image.  The
+// strides are in elements and the caller's to vouch for: the launcher checks the geometry only.
+enum GkTensorType { GK_TT_F32 = 1, GK_TT_F16 = 2, GK_TT_BF16 = 3 };   // gk_tensor::dtype (grok_amd.h)
+struct GkTensorArgs {
+    GkViewArgs v;              // (row_bytes unused)
+    int64_t stride_c, stride_y, stride_x;
+    float scale[GK_PIX_MAX_CH], bias[GK_PIX_MAX_CH];
+};
+int gk_launch_tensor(hipStream_t st, uint32_t dtype, const GkTensorArgs& args);
 // Input stage of an encode from packed pixels (gk_unpixels.hip): sample k of pixel (x, y) is read
 // at src + y * row_bytes + (x * nch + k) * es and written to plane k, dst + k * plane samples on,
 // row stride ds samples, in the same sample type.  The planes are the engine's own: dst, ds and

@@ -755,6 +755,61 @@ int gk_decode_levels(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_devic
                      const gk_levels_bins* q, uint32_t nq, uint32_t bins, gk_channel_levels* stats, uint64_t* hist,
                      size_t hist_cap, gk_view_result* res /* may be NULL */);
 
+/* Decode a view to a float tensor: the view is resolved and decoded exactly as
+ * gk_decode_view_pixels does, and its last pass (k_tensor, gk_tensor.hip) writes normalised
+ * float32, float16 or bfloat16 elements in the caller's strides, planar (C, H, W), packed
+ * (H, W, C), with padded rows, or as one image of a batch the caller owns.
+ * The rule.  The input is the int32 sample v of channel k of written pixel (x, y), exactly as
+ * gk_decode_view_pixels delivers it for the same gk_view with sample_bytes 0 and no render: after
+ * layers, colour boxes, display flags, the precision list, the reduce level the view chooses, the
+ * area average, mirror and rotation.  The output element is
+ *   f = float32(v)          int32 -> float32, round to nearest even (exact for |v| <= 2^24)
+ *   g = f * scale_k         one float32 multiplication, round to nearest even
+ *   z = g + bias_k          one float32 addition, round to nearest even; never fused with the multiplication
+ *   out = z                                     GK_TENSOR_F32
+ *         float16(z), round to nearest even     GK_TENSOR_F16
+ *         bfloat16(z), round to nearest even    GK_TENSOR_BF16
+ * Channel k takes entry min(k, n - 1) of scale and bias; n = 0 means scale 1 and bias 0.  Overflow
+ * gives an infinity, as IEEE says.  A result that is subnormal in the output type (or a subnormal
+ * g or z on the way) follows the device's default float mode: nothing is promised about it.
+ * The element is written at data + (k * stride_c + y * stride_y + x * stride_x) * es, es = 4, 2 or
+ * 2 bytes, and no other byte is touched.
+ * The layout.  The three dimensions are (channels, stride_c), (pix_h, stride_y) and (pix_w,
+ * stride_x), strides in elements.  A dimension of size 1 is left out and its stride ignored.  The
+ * rest are sorted by stride: the smallest must be >= 1 and each next one >= the previous stride
+ * times the previous size, so no two elements share an address.  extent = 1 + sum((size_d - 1) *
+ * stride_d) is the span in elements from data on.  A host tensor (on_device = 0) must also be
+ * dense, extent == channels * pix_w * pix_h: it is written on the device in the same strides and
+ * brought back by one copy of extent * es bytes.
+ * Refused, each by name, before anything is allocated or launched, and changing no setting: no t or
+ * no data; a dtype outside 1..3; n above 16; n > 0 without scale or without bias; a scale or bias
+ * entry that is NaN or infinite (the entry is named); a render that is set (a rendered tensor is
+ * out of scope: clear it); a zero or negative stride on a dimension of size above 1; overlapping
+ * strides; a host tensor that is not dense; a device pointer not aligned to es; everything
+ * gk_decode_view_pixels refuses of the view (and its one late refusal, a stream that holds only
+ * some of its tiles, stays where that call makes it).  gk_get_timings afterwards: the decode's,
+ * with the tensor pass added to mct_ms and total_ms as the view pass is.  *res: the view's. */
+#define GK_TENSOR_F32 1u
+#define GK_TENSOR_F16 2u
+#define GK_TENSOR_BF16 3u
+typedef struct gk_tensor {
+    void* data;
+    int32_t on_device;
+    uint32_t dtype;
+    int64_t stride_c, stride_y, stride_x;   /* in elements, of the written image (after rotation) */
+    uint32_t n;                             /* entries of scale and bias, 0..16 */
+    const float* scale;
+    const float* bias;
+} gk_tensor;
+int gk_decode_view_tensor(gk_ctx* ctx, const uint8_t* cs, size_t len, int cs_on_device, const gk_view* v,
+                          const gk_tensor* t, gk_view_result* res /* may be NULL */);
+/* What gk_decode_view_tensor would say of this description for a resolved view (gk_probe_view's
+ * result), no device needed and data never read (it may be NULL here; when it is not, a device
+ * pointer's alignment is judged too): 0 and *extent in elements, or -1 with the refusal in msg.
+ * The decode call runs the same check through the same function.  (The sticky render and reduce
+ * are the decode's to judge.) */
+int gk_probe_tensor(const gk_view_result* view, const gk_tensor* t, uint64_t* extent, char* msg, size_t msg_cap);
+
 /* Inverse 5/3 rule of later gk_decode_window calls.  whole_tile = 0 (default): Grok's partial-tile
  * inverse, which a window set through setDecompressWindow selects for every tile
  * (CodeStreamDecompress.cpp:389; a one-sample-wide resolution on an odd coordinate shifts its
